@@ -59,6 +59,51 @@ WORKLOADS = {
 }
 
 
+DUMP_BYTES = 64 * 10**6  # --dump-outputs: every file of the job together, headers included
+#: --dump-outputs: the cell axis of each array of a band's result (`marex_amd.dist.shard_step`) and whether its land cells are
+#: left out -- they hold NaN by definition (no data), and `mask` itself says which cells they are
+DUMP_CELL_AXIS = {"dat_anomaly": (1, True), "thr_doy_major": (1, True), "thresholds": (0, True), "extreme_events": (1, True),
+                  "mask": (0, False), "invalid_count": (0, False)}
+
+
+def dump_outputs(outdir, arrays, budget, suffix=""):
+    """`--dump-outputs`: `arrays` maps a name to `(tensor, axis, cells)`; the tensor is written as `<outdir>/<name><suffix>.npy`
+    with only the entries `cells` (an index tensor on the tensor's device) selects along `axis` (all of them when `cells` is
+    None).  float32 for data that float32 holds exactly (float32, 8- and 16-bit integers, bool), float64 for the rest.  The
+    files share `budget` bytes: small arrays are written whole, and one too large for its share is cut to a seeded, evenly
+    spread sample of its elements, written flat.  The sample depends only on the name and the selected shape, so two builds run
+    with the same arguments write comparable files."""
+    import zlib
+
+    import torch
+
+    def selected_shape(spec):
+        t, axis, cells = spec
+        return [cells.numel() if cells is not None and d == axis else s for d, s in enumerate(t.shape)]
+
+    narrow = (torch.float32, torch.float16, torch.bfloat16, torch.bool, torch.uint8, torch.int8, torch.int16)
+    os.makedirs(outdir, exist_ok=True)
+    items = sorted(arrays.items(), key=lambda kv: int(np.prod(selected_shape(kv[1]))))
+    left = budget - 256 * len(items)  # room for the .npy headers
+    for i, (name, (t, axis, cells)) in enumerate(items):
+        shape = selected_shape((t, axis, cells))
+        dtype = torch.float32 if t.dtype in narrow else torch.float64
+        size = 4 if dtype == torch.float32 else 8
+        n, k = int(np.prod(shape)), max(1, left // (len(items) - i) // size)
+        if n <= k:
+            a = (t if cells is None else t.index_select(axis, cells)).to(dtype).cpu().numpy()
+        else:
+            rng = np.random.default_rng([zlib.crc32(name.encode()), *shape])
+            idx = np.minimum(((np.arange(k) + rng.random(k)) * (n / k)).astype(np.int64), n - 1)  # one element per 1/k of the array
+            sub = torch.from_numpy(np.stack(np.unravel_index(idx, shape))).to(t.device)
+            if cells is not None:
+                sub[axis] = cells[sub[axis]]
+            a = t[tuple(sub)].to(dtype).cpu().numpy()
+        np.save(os.path.join(outdir, f"{name}{suffix}.npy"), a)
+        left -= a.nbytes
+    return [name for name, _ in items]
+
+
 def algorithmic_bytes(T, T_out, C):
     """read 4T (x) + write 4T' (anomaly) + T' (mask) + 4*366 (thresholds) + 1 (mask) per cell."""
     return C * (4 * T + 5 * T_out + 4 * 366 + 1)
@@ -271,7 +316,13 @@ def main():
     ap.add_argument("--no-extra", action="store_true", help="skip the untimed extra measurements (single-stream pass, seasonally drifting thresholds)")
     ap.add_argument("--hobday-path", default=None, choices=["tails", "bins"],
                     help="force the representation of the dayofyear histograms (default: the engine's own choice)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (the last band's arrays over its owned cells -- "
+                         "ocean cells only where land is NaN --, the summary counts) as DIR/<name>.npy, at most 64 MB in all; with "
+                         "several ranks each writes <name>.rank<r>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -414,6 +465,21 @@ def main():
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax.item())
+    if args.dump_outputs:  # before the untimed extras below, which reuse the workspaces these arrays live in
+        # r is the last band's result: of its cell axes a caller keeps the owned cells (marex_amd.dist.stitch_cells) -- the
+        # kernels leave the overlap rows of thresholds and extremes unwritten -- and of those the ocean cells where land is NaN
+        own = shards[-1].own_cell_slice()
+        own_cells = torch.arange(own.start, own.stop, device=r["mask"].device)
+        ocean = own_cells[r["mask"][own].bool()]
+        arrays = {"summary": (local, None, None), "max_invalid": (mx, None, None)}
+        for k, v in r.items():
+            if isinstance(v, torch.Tensor):
+                axis, ocean_only = DUMP_CELL_AXIS.get(k, (None, False))
+                if axis is not None and v.shape[axis] != r["mask"].numel():
+                    raise SystemExit(f"bench.py: {k} {tuple(v.shape)} has no cell axis {axis} of {r['mask'].numel()} cells")
+                arrays[k] = (v, axis, None if axis is None else ocean if ocean_only else own_cells)
+        names = dump_outputs(args.dump_outputs, arrays, DUMP_BYTES // world, f".rank{rank}" if world > 1 else "")
+        print(f"bench.py: rank {rank} wrote {', '.join(names)} to {args.dump_outputs}", file=sys.stderr, flush=True)
 
     kern = {k: timers.timing_get(k) for k in ("shifting", "detrend", "fixed", "tails", "thresholds", "mask", "transpose")}
     kern = {k: v for k, v in kern.items() if v[1]}

@@ -95,3 +95,44 @@ def test_band_count_tiles_the_field_in_whole_tile_rows():
     for n in (1, 2, 3, 4, 6, 8, 12, 24):
         nb = b.band_count(n)
         assert nb % n == 0 and 720 % nb == 0 and (720 // nb) % 30 == 0
+
+
+def test_dump_outputs_fit_their_budget_and_repeat(tmp_path):
+    """`--dump-outputs`: float32 / float64 files within the byte budget, small arrays whole and exact, a large one cut to a
+    sample of its own elements that is the same from run to run; only the selected cells of a cell axis are written."""
+    import numpy as np
+    import torch
+
+    b = _bench_module()
+    g = torch.Generator().manual_seed(0)
+    cells = torch.arange(0, 3000, 3)  # the other cells are NaN ("land") and must not reach the files
+    big = torch.full((1000, 3000), float("nan"))
+    big[:, cells] = torch.randn(1000, cells.numel(), generator=g)
+    thr = torch.full((3000, 4), float("nan"))
+    thr[cells] = torch.randn(cells.numel(), 4, generator=g)
+    arrays = {"big": (big, 1, cells), "thr": (thr, 0, cells),
+              "mask": (torch.randint(0, 2, (3000,), dtype=torch.uint8, generator=g), None, None),
+              "counts": (torch.arange(7, dtype=torch.int64) * (1 << 40), None, None)}
+    budget = 2_000_000
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), arrays, budget)
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == ["big.npy", "counts.npy", "mask.npy", "thr.npy"]
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= budget
+
+    def load(d, name):
+        return np.load(tmp_path / d / f"{name}.npy")
+
+    assert load("a", "mask").dtype == np.float32 and np.array_equal(load("a", "mask"), arrays["mask"][0].numpy())
+    assert load("a", "counts").dtype == np.float64 and np.array_equal(load("a", "counts"), arrays["counts"][0].numpy())
+    assert np.array_equal(load("a", "thr"), thr[cells].numpy())  # small: whole, in the selected cells' order
+    s = load("a", "big")
+    assert s.dtype == np.float32 and s.ndim == 1 and 0.9 * budget / 4 < s.size < budget / 4 and np.isfinite(s).all()
+    assert np.array_equal(s, load("b", "big")) and np.isin(s, big[:, cells].numpy()).all()
+
+
+def test_steps_must_be_at_least_one():
+    import subprocess
+    import sys
+
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True)
+    assert out.returncode == 2 and "--steps" in out.stderr

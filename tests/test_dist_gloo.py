@@ -92,7 +92,7 @@ def _worker(rank, world, port, ny, nx, W, out_dir):
     np.savez(os.path.join(out_dir, f"rank{rank}.npz"), anom=r["dat_anomaly"].numpy(), thr=r["thr_doy_major"].numpy(),
              ext=r["extreme_events"].numpy().astype(bool), thr_all=thr_all.numpy(),
              summ=np.array([int(local[0]), int(local[1]), int(mx[0]), int(local[3])]))
-    dist.barrier()
+    dist.monitored_barrier()  # not dist.barrier(): that asks for an accelerator, which opens the GPU device in every rank
     dist.destroy_process_group()
 
 
@@ -145,7 +145,7 @@ def _bcast_worker(rank, world, port, out_dir):
              prec=np.array([got["bins.precision"]]), empty_shape=np.array(got["empty"].shape),
              objs_ok=np.array([got["objs"].dtype == object and list(got["objs"]) == ["1999-03-01", None, 3]
                                and got["zero_d"].shape == () and float(got["zero_d"]) == 2.5]))
-    dist.barrier()
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 
@@ -200,7 +200,7 @@ def _bands_worker(rank, world, port, ny, nx, W, nbands, out_dir):
     local, mx = allreduce_step(local, mx, host_collectives=True)
     np.savez(os.path.join(out_dir, f"b{rank}.npz"), summ=np.array([int(v) for v in local.tolist()] + [int(mx[0])]),
              keys=np.array(SUMMARY_KEYS), **{f"thr{i}": p for i, p in zip(range(rank, nbands, world), parts)})
-    dist.barrier()
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 

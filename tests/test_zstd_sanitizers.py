@@ -1,5 +1,5 @@
-"""CPU only (listed in .gpurunignore: the GPU pool refuses sanitizer builds, and this one never touches a GPU): the HOST build
-of the Zstandard decoder under AddressSanitizer + UBSan."""
+"""CPU only: the HOST build of the Zstandard decoder under AddressSanitizer + UBSan.  No device code is compiled
+(``--cuda-host-only``) and none is instrumented (``-fno-gpu-sanitize``): sanitizers belong on host code only."""
 import numpy as np
 import pytest
 
@@ -20,8 +20,9 @@ def test_decoder_under_address_and_ub_sanitizers(tmp_path):
     if not os.path.exists(hipcc):
         pytest.skip("no hipcc")
     exe = str(tmp_path / "zasan")
-    subprocess.check_call([hipcc, "--cuda-host-only", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-g", "-O1", "-std=c++17",
-                           "-I" + os.path.join(root, "include"), os.path.join(root, "marex_amd", "csrc", "marex_zstd.hip"),
+    subprocess.check_call([hipcc, "--cuda-host-only", "-fsanitize=address,undefined", "-fno-gpu-sanitize",
+                           "-fno-omit-frame-pointer", "-g", "-O1", "-std=c++17", "-I" + os.path.join(root, "include"),
+                           os.path.join(root, "marex_amd", "csrc", "marex_zstd.hip"),
                            os.path.join(root, "tests", "host", "zstd_sanitizer_harness.cpp"), "-o", exe],
                           cwd=os.path.join(root, "marex_amd", "csrc"), stderr=subprocess.DEVNULL)
     rng = np.random.default_rng(5)
