@@ -365,6 +365,14 @@ int marex_time_closing_u8(marex_ctx* ctx, const uint8_t* data, int64_t T, int64_
 int marex_label2d_i32(marex_ctx* ctx, const uint8_t* data, int64_t T, int ny, int nx, int wrap_x, int32_t* labels,
                       int32_t* areas);
 
+/* Connected components in (time, y, x) (track.py:2006-2048, structured grid, time_connectivity = True): 26-connected,
+ * periodic in x when wrap_x; connect_t = 0 drops the links to t-1 (time_connectivity = False, one labelling per step).
+ * ids[i] = 1 + rank of the component's first cell in C order among all components (IDs 1..N, scipy.ndimage.label's
+ * scan order, which the reference's dask_image labelling keeps), 0 = background; areas[id - 1] = cells of component id
+ * (capacity: T * ny * nx entries, the first N written); *n_out = N.  Fewer than 2^31 - 1 cells. */
+int marex_label3d_i32(marex_ctx* ctx, const uint8_t* data, int64_t T, int ny, int nx, int wrap_x, int connect_t, int32_t* ids,
+                      int32_t* areas, int32_t* n_out);
+
 /* out[i] = labels[i] > 0 && labels[i] != drop_label && areas[labels[i] - 1] >= area_threshold (track.py:1891-1903;
  * drop_label = the reference's `object_ids_keep[0] = -1`, which removes the first object of the list) */
 int marex_filter_by_area_u8(marex_ctx* ctx, const int32_t* labels, const int32_t* areas, int64_t n,

@@ -17,14 +17,17 @@ from .exceptions import (
     DependencyError,
     MarExError,
     ProcessingError,
+    TrackingError,
     create_data_validation_error,
 )
 from .dask_adapter import preprocess_data_lazy
+from .track import tracker
 from .xr_compat import DataArray, Dataset
 
 __all__ = [
     "preprocess_data", "preprocess_data_lazy", "compute_normalised_anomaly", "identify_extremes", "rolling_climatology",
     "smoothed_rolling_climatology", "MarExError", "DataValidationError", "ConfigurationError",
     "ProcessingError", "DependencyError", "create_data_validation_error", "DataArray", "Dataset",
+    "tracker", "TrackingError",
 ]
 __version__ = "0.1.0"

@@ -62,6 +62,7 @@ PROTOTYPES = {
     "marex_fill_holes_u8": (_i32, [_p, _p, _p, _i64, _i32, _i32, _i32, _i32, _p]),
     "marex_time_closing_u8": (_i32, [_p, _p, _i64, _i64, _i32, _p]),
     "marex_label2d_i32": (_i32, [_p, _p, _i64, _i32, _i32, _i32, _p, _p]),
+    "marex_label3d_i32": (_i32, [_p, _p, _i64, _i32, _i32, _i32, _i32, _p, _p, _p]),
     "marex_filter_by_area_u8": (_i32, [_p, _p, _p, _i64, _f64, _i32, _p]),
     "marex_fill_holes_mesh_u8": (_i32, [_p, _p, _p, _p, _i64, _i64, _i32, _p]),
     "marex_label_mesh_i32": (_i32, [_p, _p, _p, _p, _i64, _i64, _p, _p]),

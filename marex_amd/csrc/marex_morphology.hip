@@ -419,6 +419,174 @@ extern "C" int marex_label2d_i32(marex_ctx* ctx, const uint8_t* data, int64_t T,
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Connected components in (time, y, x) (track.py:2006-2048 structured branch with time_connectivity = True: the 3x3x3
+// structure of ones, periodic in x unless regional) with compact IDs in the reference's order.
+//
+// Same union-find as above.  A cell's neighbourhood at t-1 is three more "rows above" -- (t-1, y-1), (t-1, y),
+// (t-1, y+1) -- each seen through the same N / NW / NE window as the row (t, y-1), so the one-union-per-overlap rule
+// carries over unchanged: the W / E cell of the current row sees the same row through a window shifted by one.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void ccl_link_row(const unsigned char* __restrict__ data, int* __restrict__ parent, long i,
+                                             long up, int x, int xw, int xe, bool okw, bool oke, bool chain, bool w_,
+                                             bool e_) {
+    const bool n_ = data[up + x] != 0;
+    const bool nw = okw && data[up + xw] != 0, ne = oke && data[up + xe] != 0;
+    if (n_) {
+        if (!(chain && w_ && nw)) uf_union(parent, (int)i, (int)(up + x));
+    } else {
+        if (nw && !(chain && w_)) uf_union(parent, (int)i, (int)(up + xw));
+        if (ne && !e_) uf_union(parent, (int)i, (int)(up + xe));
+    }
+}
+
+// connect_t = 0: the rows at t-1 are skipped (the per-timestep labelling of time_connectivity = False)
+__global__ void __launch_bounds__(256)
+k_ccl_merge3d(const unsigned char* __restrict__ data, long T, int ny, int nx, int wrap_x, int connect_t,
+              int* __restrict__ parent) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    const long C = (long)ny * nx;
+    if (i >= T * C || !data[i]) return;
+    const int x = (int)(i % nx);
+    const long ty = i / nx;
+    const int y = (int)(ty % ny);
+    const long t = ty / ny;
+    const long base = i - x;
+    const bool wrap = wrap_x && nx > 1;
+    if (x > 0) {
+        if ((threadIdx.x & 63) == 0 && data[i - 1]) uf_union(parent, (int)i, (int)(i - 1));
+    } else if (wrap && data[base + nx - 1]) {
+        uf_union(parent, (int)i, (int)(base + nx - 1));
+    }
+    const bool has_up = y > 0, has_prev = connect_t && t > 0;
+    if (!has_up && !has_prev) return;
+    int xw = x - 1, xe = x + 1;
+    bool okw = true, oke = true;
+    if (xw < 0) {
+        okw = wrap;
+        xw += nx;
+    }
+    if (xe >= nx) {
+        oke = wrap;
+        xe -= nx;
+    }
+    const bool w_ = okw && data[base + xw] != 0, e_ = oke && data[base + xe] != 0;
+    const bool chain = x > 0;  // x == 0 always links on its own account (a periodic overlap may have no beginning)
+    if (has_up) ccl_link_row(data, parent, i, base - nx, x, xw, xe, okw, oke, chain, w_, e_);
+    if (has_prev) {
+        const long prev = base - C;  // (t-1, y)
+        if (y > 0) ccl_link_row(data, parent, i, prev - nx, x, xw, xe, okw, oke, chain, w_, e_);
+        ccl_link_row(data, parent, i, prev, x, xw, xe, okw, oke, chain, w_, e_);
+        if (y + 1 < ny) ccl_link_row(data, parent, i, prev + nx, x, xw, xe, okw, oke, chain, w_, e_);
+    }
+}
+
+// Compact numbering: after compression a root is the component's smallest linear index (hooks always go to the
+// smaller root), i.e. its first voxel in C order, and ID = 1 + rank of the root among all roots -- scipy.ndimage.label's
+// scan order, which dask_image keeps by offsetting the block labels in time order and relabelling through
+// connected_components (components numbered by their smallest provisional label).
+// One workgroup counts (RANK = false) or ranks (RANK = true) the roots of CCL_TILE consecutive cells: a ballot and a
+// popcount per wave and 256 cells, the four wave counts combined in LDS, in index order.
+#define CCL_TILE 4096
+template <bool RANK>
+__global__ void __launch_bounds__(256)
+k_ccl_roots(const int* __restrict__ parent, long n, const int* __restrict__ tile_off, int* __restrict__ tile_cnt,
+            int* __restrict__ rank) {
+    __shared__ int wcnt[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long tile0 = (long)blockIdx.x * CCL_TILE;
+    int run = RANK ? tile_off[blockIdx.x] : 0;
+    for (int k = 0; k < CCL_TILE / 256; ++k) {
+        const long i = tile0 + k * 256 + threadIdx.x;
+        const bool root = i < n && parent[i] == (int)i;
+        const unsigned long long b = __ballot(root);
+        if (lane == 0) wcnt[wave] = __popcll(b);
+        __syncthreads();
+        if (RANK && root) {
+            int before = run + __popcll(b & ((1ull << lane) - 1ull));
+            for (int w = 0; w < wave; ++w) before += wcnt[w];
+            rank[i] = before;
+        }
+        run += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+        __syncthreads();
+    }
+    if (!RANK && threadIdx.x == 0) tile_cnt[blockIdx.x] = run;
+}
+
+// exclusive scan of the tile counts by one workgroup (a few hundred thousand tiles at most); n_out = the total
+__global__ void __launch_bounds__(1024)
+k_ccl_scan_tiles(const int* __restrict__ cnt, long ntiles, int* __restrict__ off, int* __restrict__ n_out) {
+    __shared__ int part[1024];
+    const long per = (ntiles + 1023) / 1024;
+    const long a = threadIdx.x * per, b = a + per < ntiles ? a + per : ntiles;
+    int s = 0;
+    for (long j = a; j < b; ++j) s += cnt[j];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (int d = 1; d < 1024; d <<= 1) {  // Hillis-Steele inclusive scan of the 1024 partial sums
+        const int v = threadIdx.x >= (unsigned)d ? part[threadIdx.x - d] : 0;
+        __syncthreads();
+        part[threadIdx.x] += v;
+        __syncthreads();
+    }
+    int run = part[threadIdx.x] - s;
+    for (long j = a; j < b; ++j) {
+        const int c = cnt[j];
+        off[j] = run;
+        run += c;
+    }
+    if (threadIdx.x == 1023) *n_out = part[1023];
+}
+
+// ids[i] = 1 + rank[root of i] in place (each thread reads and writes only its own element), areas[id - 1] += cells
+// with one atomic per (wave, id)
+__global__ void __launch_bounds__(256)
+k_ccl_relabel(long n, const int* __restrict__ rank, int* __restrict__ ids, int* __restrict__ areas) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    int id = 0;
+    if (i < n) {
+        const int r = ids[i];
+        id = r < 0 ? 0 : rank[r] + 1;
+        ids[i] = id;
+    }
+    unsigned long long todo = __ballot(id > 0);
+    while (todo) {
+        const int lead = __ffsll((long long)todo) - 1;
+        const int il = __shfl(id, lead, 64);
+        const unsigned long long same = __ballot(id == il) & todo;
+        if ((int)(threadIdx.x & 63) == lead) atomicAdd(&areas[il - 1], __popcll(same));
+        todo &= ~same;
+    }
+}
+
+extern "C" int marex_label3d_i32(marex_ctx* ctx, const uint8_t* data, int64_t T, int ny, int nx, int wrap_x, int connect_t,
+                                 int32_t* ids, int32_t* areas, int32_t* n_out) {
+    if (!ctx) return -1;
+    if (!data || !ids || !areas || !n_out || T <= 0 || ny <= 0 || nx <= 0) return fail(ctx, -1, "marex_label3d_i32: null pointer or empty shape");
+    const long n = (long)T * ny * nx;
+    if (n >= 2147483647L) return fail(ctx, -4, "marex_label3d_i32: more than 2^31 - 1 cells; label the series in time blocks");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    LaunchTimer lt(ctx, MAREX_K_MORPH);
+    const unsigned g = (unsigned)((n + 255) / 256);
+    const long ntiles = (n + CCL_TILE - 1) / CCL_TILE;
+    // scratch: rank [n] (written at the roots only), tile counts and tile offsets [ntiles] each
+    if (int rc = ensure_scratch(ctx, (size_t)(n + 2 * ntiles) * sizeof(int))) return rc;
+    int* rank = reinterpret_cast<int*>(ctx->morph_scratch);
+    int* tile_cnt = rank + n;
+    int* tile_off = tile_cnt + ntiles;
+    HIP_TRY(ctx, hipMemsetAsync(areas, 0, (size_t)n * sizeof(int), ctx->stream));
+    // `ids` is the parent array until the relabelling
+    hipLaunchKernelGGL(k_ccl_init, dim3(g), dim3(256), 0, ctx->stream, data, n, nx, ids);
+    hipLaunchKernelGGL(k_ccl_merge3d, dim3(g), dim3(256), 0, ctx->stream, data, (long)T, ny, nx, wrap_x, connect_t, ids);
+    hipLaunchKernelGGL(k_ccl_compress, dim3(g), dim3(256), 0, ctx->stream, n, ids);
+    hipLaunchKernelGGL(k_ccl_roots<false>, dim3((unsigned)ntiles), dim3(256), 0, ctx->stream, ids, n, tile_off, tile_cnt, rank);
+    hipLaunchKernelGGL(k_ccl_scan_tiles, dim3(1), dim3(1024), 0, ctx->stream, tile_cnt, ntiles, tile_off, n_out);
+    hipLaunchKernelGGL(k_ccl_roots<true>, dim3((unsigned)ntiles), dim3(256), 0, ctx->stream, ids, n, tile_off, tile_cnt, rank);
+    hipLaunchKernelGGL(k_ccl_relabel, dim3(g), dim3(256), 0, ctx->stream, n, rank, ids, areas);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
 extern "C" int marex_filter_by_area_u8(marex_ctx* ctx, const int32_t* labels, const int32_t* areas, int64_t n,
                                        double area_threshold, int drop_label, uint8_t* out) {
     if (!ctx) return -1;

@@ -748,6 +748,22 @@ class HotPath:
         self.ctx.check(rc, "marex_label2d_i32")
         return {"labels": labels, "areas": areas}
 
+    def label_objects_3d(self, data_bin: torch.Tensor, ny: int, nx: int, wrap_x: bool = True, connect_t: bool = True,
+                         wsp: Optional[dict] = None) -> Dict[str, torch.Tensor]:
+        """26-connected components in (time, y, x) (track.py:2006-2048, ``time_connectivity=True``; ``connect_t=False``:
+        one labelling per timestep).  ``ids`` int32 ``[T, C]``: IDs 1..N numbered by the component's first cell in C order,
+        0 = background; ``areas`` int32 (cells of ID ``k`` at ``k - 1``, the first N entries); ``n`` int32 ``[1]`` = N."""
+        self._bind_stream()
+        T, Cn = data_bin.shape
+        assert Cn == ny * nx
+        ids = self._buf(wsp, "ids3d", (T, Cn), torch.int32, self.device)
+        areas = self._buf(wsp, "areas3d", (T * Cn,), torch.int32, self.device)
+        n = self._buf(wsp, "n3d", (1,), torch.int32, self.device)
+        rc = self.lib.marex_label3d_i32(self.ctx.handle, data_bin.data_ptr(), T, int(ny), int(nx), int(bool(wrap_x)),
+                                        int(bool(connect_t)), ids.data_ptr(), areas.data_ptr(), n.data_ptr())
+        self.ctx.check(rc, "marex_label3d_i32")
+        return {"ids": ids, "areas": areas, "n": n}
+
     def filter_small_objects(self, data_bin: torch.Tensor, ny: int, nx: int, area_filter_quartile: float = 0.5,
                              area_filter_absolute: Optional[float] = None, regional_mode: bool = False,
                              wsp: Optional[dict] = None) -> Dict[str, object]:

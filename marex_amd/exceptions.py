@@ -81,6 +81,12 @@ class DependencyError(MarExError):
     default_code = "DEPENDENCY"
 
 
+class TrackingError(MarExError):
+    """Object identification / tracking failed (reference: marEx/exceptions.py:255)."""
+
+    default_code = "TRACKING"
+
+
 def create_data_validation_error(
     message: str, data_info: Optional[Dict[str, Any]] = None, **kwargs: Any
 ) -> DataValidationError:
