@@ -418,6 +418,35 @@ int marex_unshuffle_place(marex_ctx* ctx, const uint8_t* planes, const int64_t* 
                           const int32_t* blk_ne, const int32_t* blk_valid, int n_blocks, int max_ne, int typesize, int shuffled,
                           uint8_t* out);
 
+/* Object properties and time overlaps of an int32 ID field ids[T][C] (C = ny * nx; values <= 0 are background; C and T
+ * below 2^31 - 1).  Used by tracker.calculate_object_properties / find_overlapping_objects (marEx/track.py:2109-2504).
+ *
+ * marex_ids_minmax_i32: minmax[0] = min, minmax[1] = max of ids[0 .. n).
+ * marex_object_spans_i32: tmin[id] / tmax[id] = first / last timestep with a cell of id (INT_MAX / -1 when absent), for
+ *   id = 0 .. max_id (max_id >= every ID); off[id] = exclusive prefix sum in ID order of the spans tmax - tmin + 1, so that
+ *   slot off[id] + t - tmin[id] belongs to (t, id); *total = the number of slots.  work: int64 [2 * ceil((max_id + 1) / 4096)].
+ * marex_object_moments_i32: acc[slot][0..4] = cell count, sum of y, sum of x, cells with x > nx / 2, flags (bit 0: a cell
+ *   with x < 100, bit 1: a cell with x >= nx - 100) of every slot; acc [n_slots][5] is zeroed first.  Integer atomics
+ *   only: bitwise reproducible.
+ * marex_object_compact: the slots with a non-zero count -> out_tid[p] = (t, id), out_mom[p][0..4] = acc[slot], in no
+ *   particular order; *n_out = how many.  out_tid [n_slots][2], out_mom [n_slots][5].
+ * marex_overlap_count_i32: over the cells of slices t < T - 1, stats[0] = cells with ids[t] > 0 and ids[t + 1] > 0,
+ *   stats[1] = the runs of equal (ids[t], ids[t + 1]) pairs the device folds together (>= the distinct pairs);
+ *   stats[2], stats[3] = 0.
+ * marex_overlap_pairs_i32: the distinct pairs and their cell counts.  keys / counts: a table of cap (a power of two,
+ *   >= 2 * stats[1] recommended) u64 entries each, zeroed here; out_keys[p] = id_t << 32 | id_t+1, out_counts[p] = cells,
+ *   p < stats[3], in no particular order (at most out_cap written); stats[2] != 0 when the table overflowed. */
+int marex_ids_minmax_i32(marex_ctx* ctx, const int32_t* ids, int64_t n, int32_t* minmax);
+int marex_object_spans_i32(marex_ctx* ctx, const int32_t* ids, int64_t T, int64_t C, int max_id, int32_t* tmin, int32_t* tmax,
+                           int64_t* off, int64_t* work, int64_t* total);
+int marex_object_moments_i32(marex_ctx* ctx, const int32_t* ids, int64_t T, int ny, int nx, const int32_t* tmin,
+                             const int64_t* off, int64_t n_slots, uint64_t* acc);
+int marex_object_compact(marex_ctx* ctx, int64_t n_slots, int max_id, const int32_t* tmin, const int64_t* off,
+                         const uint64_t* acc, uint64_t* n_out, int32_t* out_tid, uint64_t* out_mom);
+int marex_overlap_count_i32(marex_ctx* ctx, const int32_t* ids, int64_t T, int64_t C, uint64_t* stats);
+int marex_overlap_pairs_i32(marex_ctx* ctx, const int32_t* ids, int64_t T, int64_t C, int64_t cap, uint64_t* keys,
+                            uint64_t* counts, uint64_t* stats, int64_t out_cap, uint64_t* out_keys, uint64_t* out_counts);
+
 /* out[c, r] = in[r, c]  (thresholds [366, C] -> the reference's (cells, dayofyear) order) */
 int marex_transpose_f32(marex_ctx* ctx, const float* in, int64_t rows, int64_t cols, float* out);
 

@@ -86,6 +86,12 @@ PROTOTYPES = {
     "marex_blosc_compress_h": (_i32, [_p, _i64, _i32, _i32, _i64, _p, _i64, _p]),
     "marex_lz4_decode_streams": (_i32, [_p, _p, _p, _p, _p, _p, _i32, _i32, _p, _p]),
     "marex_unshuffle_place": (_i32, [_p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _p]),
+    "marex_ids_minmax_i32": (_i32, [_p, _p, _i64, _p]),
+    "marex_object_spans_i32": (_i32, [_p, _p, _i64, _i64, _i32, _p, _p, _p, _p, _p]),
+    "marex_object_moments_i32": (_i32, [_p, _p, _i64, _i32, _i32, _p, _p, _i64, _p]),
+    "marex_object_compact": (_i32, [_p, _i64, _i32, _p, _p, _p, _p, _p, _p]),
+    "marex_overlap_count_i32": (_i32, [_p, _p, _i64, _i64, _p]),
+    "marex_overlap_pairs_i32": (_i32, [_p, _p, _i64, _i64, _i64, _p, _p, _p, _i64, _p, _p]),
 }
 
 KERNEL_IDS = {

@@ -764,6 +764,128 @@ class HotPath:
         self.ctx.check(rc, "marex_label3d_i32")
         return {"ids": ids, "areas": areas, "n": n}
 
+    # ------------------------------------------------------------------ object properties and overlaps (track.py:2109-2504)
+    def ids_minmax(self, ids: torch.Tensor) -> tuple:
+        """``(min, max)`` of an int32 ID field (synchronises)."""
+        self._bind_stream()
+        mm = self._buf(None, "ids_minmax", (2,), torch.int32, self.device)
+        self.ctx.check(self.lib.marex_ids_minmax_i32(self.ctx.handle, ids.data_ptr(), ids.numel(), mm.data_ptr()),
+                       "marex_ids_minmax_i32")
+        lo, hi = (int(v) for v in mm.cpu().numpy())
+        if lo < 0:
+            from .exceptions import create_data_validation_error
+
+            raise create_data_validation_error("Object IDs must be non-negative", details=f"smallest ID {lo}; 0 is background",
+                                               data_info={"min_id": lo, "max_id": hi})
+        return lo, hi
+
+    def _check_fits(self, nbytes: int, what: str, details: str) -> None:
+        """Raise instead of allocating past the free device memory (buffers are sized up front, never truncated)."""
+        free, _ = torch.cuda.mem_get_info(self.device)
+        if nbytes > free:
+            raise ProcessingError(f"{what}: needs {nbytes / 1e9:.3f} GB of device memory, {free / 1e9:.3f} GB are free",
+                                  details=details)
+
+    def _ids_check(self, ids: torch.Tensor) -> tuple:
+        if ids.dtype != torch.int32 or ids.dim() != 2 or not ids.is_contiguous() or ids.device != self.device:
+            raise ProcessingError("object IDs must be a contiguous int32 [T, C] tensor on the engine's device",
+                                  details=f"got {ids.dtype} {tuple(ids.shape)} on {ids.device}")
+        return tuple(int(k) for k in ids.shape)
+
+    def object_moments(self, ids: torch.Tensor, ny: int, nx: int, wrap: bool = True) -> Dict[str, np.ndarray]:
+        """Area and centroid of every ID in every timestep of ``ids`` int32 ``[T, ny * nx]`` (values <= 0: background):
+        ``t``, ``id`` (int64), ``area`` (float64 cells) and ``centroid`` (float64 ``[2, n]``: mean row, mean column), rows in
+        (t, id) order.  With ``wrap`` the column mean of an object with cells in both the first and the last 100 columns
+        is taken with the columns x > nx // 2 shifted by -nx, and nx is added when that mean is negative
+        (calculate_centroid, track.py:2050-2107).  The device accumulates integer sums; the division is NumPy's float64."""
+        self._bind_stream()
+        T, Cn = self._ids_check(ids)
+        if Cn != ny * nx:
+            raise ProcessingError(f"object_moments: {Cn} cells per slice, ny * nx = {ny * nx}")
+        _, hi = self.ids_minmax(ids)
+        out = {"t": np.zeros(0, np.int64), "id": np.zeros(0, np.int64), "area": np.zeros(0, np.float64),
+               "centroid": np.zeros((2, 0), np.float64)}
+        if hi <= 0:
+            return out
+        nid = hi + 1
+        ntiles = (nid + 4095) // 4096
+        self._check_fits(16 * nid + 16 * ntiles, "object properties",
+                         f"per-ID first / last timestep and slot offsets for IDs 0..{hi}; renumber sparse IDs densely")
+        tmin = self._buf(None, "obj_tmin", (nid,), torch.int32, self.device)
+        tmax = self._buf(None, "obj_tmax", (nid,), torch.int32, self.device)
+        off = self._buf(None, "obj_off", (nid,), torch.int64, self.device)
+        work = self._buf(None, "obj_work", (2 * ntiles,), torch.int64, self.device)
+        total = self._buf(None, "obj_total", (1,), torch.int64, self.device)
+        rc = self.lib.marex_object_spans_i32(self.ctx.handle, ids.data_ptr(), T, Cn, hi, tmin.data_ptr(), tmax.data_ptr(),
+                                             off.data_ptr(), work.data_ptr(), total.data_ptr())
+        self.ctx.check(rc, "marex_object_spans_i32")
+        n_slots = int(total.item())
+        del work
+        self._check_fits(88 * n_slots, "object properties",
+                         f"{n_slots} (timestep, ID) slots between each ID's first and last timestep, 88 bytes each")
+        acc = self._buf(None, "obj_acc", (n_slots, 5), torch.int64, self.device)
+        rc = self.lib.marex_object_moments_i32(self.ctx.handle, ids.data_ptr(), T, int(ny), int(nx), tmin.data_ptr(),
+                                               off.data_ptr(), n_slots, acc.data_ptr())
+        self.ctx.check(rc, "marex_object_moments_i32")
+        n_out = self._buf(None, "obj_n", (1,), torch.int64, self.device)
+        tid = self._buf(None, "obj_tid", (n_slots, 2), torch.int32, self.device)
+        mom = self._buf(None, "obj_mom", (n_slots, 5), torch.int64, self.device)
+        rc = self.lib.marex_object_compact(self.ctx.handle, n_slots, hi, tmin.data_ptr(), off.data_ptr(), acc.data_ptr(),
+                                           n_out.data_ptr(), tid.data_ptr(), mom.data_ptr())
+        self.ctx.check(rc, "marex_object_compact")
+        n = int(n_out.item())
+        if not 0 < n <= n_slots:
+            raise ProcessingError(f"object_moments: {n} non-empty slots of {n_slots} (internal sizing error)")
+        tid_h = tid[:n].cpu().numpy().astype(np.int64)
+        mom_h = mom[:n].cpu().numpy()
+        order = np.argsort((tid_h[:, 0] << 32) | tid_h[:, 1])  # (t, id) order: the device compacts in no particular order
+        tid_h, mom_h = tid_h[order], mom_h[order]
+        cnt, sy, sx, nr, fl = (mom_h[:, k] for k in range(5))
+        c1 = sx / cnt
+        if wrap:
+            seam = fl == 3
+            c = (sx[seam] - int(nx) * nr[seam]) / cnt[seam]
+            c1[seam] = np.where(c < 0, c + nx, c)
+        out.update(t=tid_h[:, 0], id=tid_h[:, 1], area=cnt.astype(np.float64), centroid=np.stack([sy / cnt, c1]))
+        return out
+
+    def overlap_pairs(self, ids: torch.Tensor) -> np.ndarray:
+        """``(n, 3)`` int32 ``[id at t, id at t + 1, cells]`` over every t < T - 1 of ``ids`` int32 ``[T, C]``, summed over
+        time and sorted lexicographically (check_overlap_slice / find_overlapping_objects, track.py:2396-2504)."""
+        self._bind_stream()
+        T, Cn = self._ids_check(ids)
+        _, hi = self.ids_minmax(ids)
+        empty = np.zeros((0, 3), np.int32)
+        if T < 2 or hi <= 0:
+            return empty
+        stats = self._buf(None, "ovl_stats", (4,), torch.int64, self.device)
+        self.ctx.check(self.lib.marex_overlap_count_i32(self.ctx.handle, ids.data_ptr(), T, Cn, stats.data_ptr()),
+                       "marex_overlap_count_i32")
+        runs = int(stats[1].item())
+        if runs == 0:
+            return empty
+        cap = max(64, 1 << (2 * runs - 1).bit_length())  # load factor <= 1/2 even if every run were a distinct pair
+        self._check_fits(16 * cap + 16 * runs, "overlap pairs", f"a hash table of {cap} entries for {runs} runs of equal pairs")
+        keys = self._buf(None, "ovl_keys", (cap,), torch.int64, self.device)
+        counts = self._buf(None, "ovl_counts", (cap,), torch.int64, self.device)
+        out_k = self._buf(None, "ovl_out_keys", (runs,), torch.int64, self.device)
+        out_c = self._buf(None, "ovl_out_counts", (runs,), torch.int64, self.device)
+        rc = self.lib.marex_overlap_pairs_i32(self.ctx.handle, ids.data_ptr(), T, Cn, cap, keys.data_ptr(), counts.data_ptr(),
+                                              stats.data_ptr(), runs, out_k.data_ptr(), out_c.data_ptr())
+        self.ctx.check(rc, "marex_overlap_pairs_i32")
+        s = stats.cpu().numpy()
+        n = int(s[3])
+        if s[2] != 0 or not 0 < n <= runs:
+            raise ProcessingError(f"overlap pairs: hash table overflow ({n} pairs, {runs} runs, {cap} entries)")
+        k = out_k[:n].cpu().numpy()
+        c = out_c[:n].cpu().numpy()
+        order = np.argsort(k, kind="stable")
+        k, c = k[order], c[order]
+        if c.max() > np.iinfo(np.int32).max:
+            raise ProcessingError("overlap pairs: a pair overlaps in 2^31 or more cells, which int32 cannot hold",
+                                  details=f"largest overlap {int(c.max())} cells")
+        return np.stack([k >> 32, k & 0xFFFFFFFF, c], axis=1).astype(np.int32)
+
     def filter_small_objects(self, data_bin: torch.Tensor, ny: int, nx: int, area_filter_quartile: float = 0.5,
                              area_filter_absolute: Optional[float] = None, regional_mode: bool = False,
                              wsp: Optional[dict] = None) -> Dict[str, object]:

@@ -10,14 +10,22 @@ every time block with ``scipy.ndimage.label``, offsets the labels block by block
 """
 from __future__ import annotations
 
-from typing import Dict, Literal, Optional, Tuple, Union
+import logging
+from typing import Dict, List, Literal, Optional, Tuple, Union
 
 import numpy as np
 
 from .exceptions import ConfigurationError, TrackingError, create_data_validation_error
 
+logger = logging.getLogger("marex_amd")
+
 #: cells of one labelling (int32 parents; the limit of the 2-D labeller too)
 MAX_CELLS = 2**31 - 1
+
+#: regionprops names calculate_object_properties computes on the device
+SUPPORTED_PROPERTIES = ("label", "area", "centroid")
+
+_I32_MAX = 2**31 - 1
 
 
 def _tensor_of(da):
@@ -52,8 +60,13 @@ class tracker:  # noqa: N801 -- the reference's public name (marEx.tracker)
 
     Accepted and ignored: ``grid_resolution`` and ``cell_areas`` (validated like the reference does; for gridded data the
     reference counts areas in cells anyway, track.py:1499-1518, 2337), ``temp_dir``, ``nn_partitioning``,
-    ``overlap_threshold``, ``max_iteration`` (merge tracking and meshes only), ``debug``, ``verbose``, ``quiet``
-    (logging) and ``coordinate_units`` (the output carries the input's lat / lon unchanged).
+    ``max_iteration`` (merge tracking and meshes only), ``debug``, ``verbose``, ``quiet`` (logging) and
+    ``coordinate_units`` (the output carries the input's lat / lon unchanged).  ``overlap_threshold`` is stored and used
+    by :meth:`enforce_overlap_threshold`.
+
+    The object stages of the reference's merge tracker are public methods here too (track.py:1499-1518, 2050-2552):
+    :meth:`compute_area`, :meth:`calculate_centroid`, :meth:`calculate_object_properties` (on the device),
+    :meth:`check_overlap_slice` and :meth:`find_overlapping_objects` (on the device) and :meth:`enforce_overlap_threshold`.
 
     ``data_bin`` may be device resident -- a DataArray whose data is a torch tensor (bool or uint8) on the GPU, e.g. from
     ``zarr_io.open_dataarray_device`` -- and is then consumed without a host round trip.  ``device`` picks the GPU.
@@ -115,6 +128,7 @@ class tracker:  # noqa: N801 -- the reference's public name (marEx.tracker)
         self.T_fill = T_fill
         self._resolve_area_filtering_parameters(area_filter_quartile, area_filter_absolute)
         self.allow_merging = allow_merging
+        self.overlap_threshold = overlap_threshold
         self.unstructured_grid = unstructured_grid
         self.checkpoint = checkpoint
         self.data_attrs = dict(getattr(data_bin, "attrs", None) or {})
@@ -374,3 +388,214 @@ class tracker:  # noqa: N801 -- the reference's public name (marEx.tracker)
         out = Dataset({"ID_field": DataArray(v.values, dims=tuple(v.dims), coords=coords, name="ID_field")})
         out.attrs.update(events_ds.attrs)
         return out
+
+    # ------------------------------------------------------------------ object properties and overlaps (track.py:1499-1518, 2050-2552)
+    def compute_area(self, data_bin):
+        """Cells of ``data_bin`` per timestep (track.py:1499-1518, gridded: ``data_bin.sum(dim=[y, x])``), an int64
+        DataArray over time.  ``data_bin`` may be device resident."""
+        import torch
+
+        from .xr_compat import DataArray
+
+        dims = tuple(getattr(data_bin, "dims", ()) or ())
+        if not dims:
+            dims = self._out_dims() if len(data_bin.shape) == 3 else (self.ydim, self.xdim)
+        axes = tuple(i for i, d in enumerate(dims) if d in (self.ydim, self.xdim))
+        t = _tensor_of(data_bin)
+        if t is not None:
+            area = t.to(torch.int64).sum(dim=axes).cpu().numpy()
+        else:
+            area = np.asarray(data_bin.values if hasattr(data_bin, "values") else data_bin).sum(axis=axes, dtype=np.int64)
+        rest = tuple(d for d in dims if d not in (self.ydim, self.xdim))
+        coords = {}
+        c = getattr(data_bin, "coords", None) or {}
+        if self.timedim in rest and self.timecoord in c:
+            coords[self.timecoord] = (self.timedim, np.asarray(c[self.timecoord].values))
+        return DataArray(area, dims=rest, coords=coords)
+
+    def calculate_centroid(self, binary_mask, original_centroid: Optional[Tuple[float, float]] = None) -> Tuple[float, float]:
+        """Centroid ``(y, x)`` of one object's 2-D mask (track.py:2050-2107), in cell indices.  Unless ``regional_mode``, an
+        object with a cell in the first 100 columns and one in the last 100 (the two bands overlap when nx < 200) gets the
+        mean of its columns with those right of ``nx // 2`` shifted by ``-nx``, plus ``nx`` if that mean is negative.
+        Otherwise ``original_centroid`` is returned as given or, when it is None, the plain means are computed (the
+        reference returns None in regional mode without an ``original_centroid``)."""
+        m = np.asarray(binary_mask).astype(bool)
+        if self.regional_mode:
+            if original_centroid is not None:
+                return original_centroid
+            ys, xs = np.nonzero(m)
+            return (np.mean(ys), np.mean(xs))
+        near_left_BC = np.any(m[:, :100])
+        near_right_BC = np.any(m[:, -100:])
+        y_centroid = np.mean(np.nonzero(m)[0]) if original_centroid is None else original_centroid[0]
+        if near_left_BC and near_right_BC:
+            x = np.nonzero(m)[1]
+            x_adj = x.copy()
+            x_adj[x > m.shape[1] // 2] -= m.shape[1]
+            x_centroid = np.mean(x_adj)
+            if x_centroid < 0:
+                x_centroid += m.shape[1]
+        elif original_centroid is None:
+            x_centroid = np.mean(np.nonzero(m)[1])
+        else:
+            x_centroid = original_centroid[1]
+        return (y_centroid, x_centroid)
+
+    def _ids_perm(self, field):
+        """Axis order that brings an ID field to (time, y, x), or (y, x) for a single slice."""
+        nd = len(field.shape)
+        dims = getattr(field, "dims", None)
+        want = self._out_dims() if nd == 3 else (self.ydim, self.xdim)
+        if dims is not None and len(dims) > 0:
+            dims = tuple(dims)
+            if nd not in (2, 3) or set(dims) != set(want) or len(dims) != nd:
+                raise create_data_validation_error(
+                    "Invalid dimensions for an object ID field",
+                    details=f"Expected dimensions {self._out_dims()} or {(self.ydim, self.xdim)}, got {list(dims)}",
+                    data_info={"actual_dims": list(dims)})
+            return tuple(dims.index(k) for k in want)
+        if nd not in (2, 3):
+            raise create_data_validation_error("Invalid dimensions for an object ID field",
+                                               details=f"Expected a 3-D (time, y, x) or 2-D (y, x) array, got shape {tuple(field.shape)}")
+        return tuple(range(nd))
+
+    @staticmethod
+    def _id_range_error(lo, hi):
+        if lo < 0:
+            return create_data_validation_error("Object IDs must be non-negative", details=f"smallest ID {lo}; 0 is background",
+                                                data_info={"min_id": int(lo), "max_id": int(hi)})
+        return create_data_validation_error("Object IDs must fit int32", details=f"largest ID {hi} > {_I32_MAX}",
+                                            data_info={"min_id": int(lo), "max_id": int(hi)})
+
+    def _device_ids(self, field, eng):
+        """An ID field as a contiguous int32 ``[T, ny * nx]`` device tensor in (time, y, x) order (a 2-D field is one
+        slice): ``(tensor, T, ny, nx)``.  An int32 device tensor is used in place; other integer types are range-checked
+        and converted."""
+        import torch
+
+        perm = self._ids_perm(field)
+        t = _tensor_of(field)
+        if t is None:
+            a = np.asarray(field.values if hasattr(field, "values") else field)
+            if a.dtype.kind not in "iu":
+                raise create_data_validation_error("Object IDs must be integers", details=f"Found dtype {a.dtype}",
+                                                   data_info={"actual_dtype": str(a.dtype)})
+            if a.dtype != np.int32 and a.size:
+                lo, hi = int(a.min()), int(a.max())
+                if lo < 0 or hi > _I32_MAX:
+                    raise self._id_range_error(lo, hi)
+            t = torch.from_numpy(np.ascontiguousarray(np.transpose(a, perm), dtype=np.int32)).to(eng.device)
+        else:
+            if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+                raise create_data_validation_error("Object IDs must be integers", details=f"Found dtype {t.dtype}",
+                                                   data_info={"actual_dtype": str(t.dtype)})
+            if t.device != eng.device:
+                t = t.to(eng.device)
+            if t.dtype != torch.int32 and t.numel():
+                lo, hi = int(t.min().item()), int(t.max().item())
+                if lo < 0 or hi > _I32_MAX:
+                    raise self._id_range_error(lo, hi)
+                t = t.to(torch.int32)
+            t = t.permute(*perm).contiguous()
+        if t.dim() == 2:
+            t = t.unsqueeze(0)
+        T, ny, nx = (int(k) for k in t.shape)
+        return t.reshape(T, ny * nx), T, ny, nx
+
+    def calculate_object_properties(self, object_id_field, properties: Optional[List[str]] = None):
+        """Properties of the objects of an ID field (track.py:2109-2390, gridded branch), computed on the device.
+
+        ``properties`` defaults to ``["label", "area"]``; ``"label"`` is always added; ``"area"`` and ``"centroid"`` are
+        the other supported names.  Returns a Dataset indexed by ``ID`` (int64): per timeslice in time order, the IDs
+        present in that slice in ascending order -- an ID of a multi-day event appears once per timestep, as the
+        reference's concatenation of per-slice ``regionprops_table`` results does.  ``area`` is float64 cells;
+        ``centroid`` is float64 ``(component, ID)``: the mean row index and the mean column index, the latter with the
+        seam rule of :meth:`calculate_centroid` unless ``regional_mode``.  Values <= 0 are background; a negative ID or
+        one beyond int32 raises :class:`DataValidationError`."""
+        from .xr_compat import DataArray, Dataset
+
+        properties = ["label", "area"] if properties is None else list(properties)
+        if "label" not in properties:
+            properties = ["label"] + properties
+        bad = [p for p in properties if p not in SUPPORTED_PROPERTIES]
+        if bad:
+            raise ConfigurationError(f"Unsupported object properties: {bad}",
+                                     details=f"supported on the device: {list(SUPPORTED_PROPERTIES)}",
+                                     suggestions=[f"Pass a subset of {list(SUPPORTED_PROPERTIES)}"])
+        eng = self._engine()
+        ids, T, ny, nx = self._device_ids(object_id_field, eng)
+        if ids.numel() == 0:
+            r = {"id": np.zeros(0, np.int64), "area": np.zeros(0), "centroid": np.zeros((2, 0))}
+        else:
+            r = eng.object_moments(ids, ny, nx, wrap=not self.regional_mode)
+        coord = {"ID": ("ID", r["id"])}
+        data = {}
+        if "area" in properties:
+            data["area"] = DataArray(r["area"], dims=("ID",), coords=coord)
+        if "centroid" in properties:
+            data["centroid"] = DataArray(r["centroid"], dims=("component", "ID"), coords=coord)
+        return Dataset(data, coords=coord)
+
+    def check_overlap_slice(self, ids_t0, ids_next) -> np.ndarray:
+        """Overlaps of two ID slices (track.py:2396-2452): ``(n, 3)`` int32 ``[id_t0, id_next, cells]`` over the cells
+        where both are > 0, sorted lexicographically; ``(0, 3)`` when there are none.  Computed on the device."""
+        import torch
+
+        eng = self._engine()
+        a, Ta, nya, nxa = self._device_ids(ids_t0, eng)
+        b, Tb, nyb, nxb = self._device_ids(ids_next, eng)
+        if (Ta, nya, nxa) != (1, nyb, nxb) or Tb != 1:
+            raise create_data_validation_error("check_overlap_slice needs two 2-D slices of the same shape",
+                                               details=f"got {tuple(ids_t0.shape)} and {tuple(ids_next.shape)}")
+        if a.numel() == 0:
+            return np.zeros((0, 3), np.int32)
+        return eng.overlap_pairs(torch.cat([a, b], dim=0))
+
+    def find_overlapping_objects(self, object_id_field) -> np.ndarray:
+        """Overlaps of every slice t with slice t + 1, t < T - 1 (track.py:2454-2504), computed on the device: ``(n, 3)``
+        int32 ``[id at t, id at t + 1, cells]``, counts of equal pairs summed over time, sorted lexicographically.  A sum
+        that int32 cannot hold raises :class:`ProcessingError` instead of wrapping."""
+        eng = self._engine()
+        ids, T, ny, nx = self._device_ids(object_id_field, eng)
+        if ids.numel() == 0:
+            return np.zeros((0, 3), np.int32)
+        return eng.overlap_pairs(ids)
+
+    def enforce_overlap_threshold(self, overlap_objects_list, object_props) -> np.ndarray:
+        """Keep the pairs that overlap enough (track.py:2506-2552): pairs whose IDs are not both in ``object_props.ID``
+        are dropped; ``fraction = overlap / min(area_0, area_1)``; rows with ``fraction >= overlap_threshold`` are
+        returned in the input's dtype, ``(0, 3)`` int32 when none remain.  A fraction above 1 is logged as a warning on
+        the ``marex_amd`` logger.  Runs on the host.
+
+        Defined for unique IDs only -- object properties of per-timestep objects, e.g. of
+        ``identify_objects(..., time_connectivity=False)``: ``object_props`` with repeated IDs (those of multi-day events)
+        raises :class:`DataValidationError`."""
+        ov = np.asarray(overlap_objects_list)
+        empty = np.empty((0, 3), dtype=np.int32)
+        if len(ov) == 0:
+            return empty
+        ids = np.asarray(object_props["ID"].values)
+        area = np.asarray(object_props["area"].values, dtype=np.float64)
+        order = np.argsort(ids, kind="stable")
+        sid, sarea = ids[order], area[order]
+        if sid.size > 1 and np.any(sid[1:] == sid[:-1]):
+            raise create_data_validation_error(
+                "object_props has repeated IDs", details="enforce_overlap_threshold needs one area per ID",
+                suggestions=["Compute the properties of per-timestep objects (identify_objects(..., time_connectivity=False))"])
+
+        def lookup(col):
+            pos = np.clip(np.searchsorted(sid, col), 0, max(sid.size - 1, 0))
+            found = (sid[pos] == col) if sid.size else np.zeros(col.shape, dtype=bool)
+            return found, (sarea[pos] if sid.size else np.zeros(col.shape))
+
+        f0, a0 = lookup(ov[:, 0])
+        f1, a1 = lookup(ov[:, 1])
+        valid = f0 & f1
+        if not np.any(valid):
+            return empty
+        valid_overlaps = ov[valid]
+        overlap_fractions = valid_overlaps[:, 2].astype(float) / np.minimum(a0[valid], a1[valid])
+        if np.any(overlap_fractions > 1.0):
+            logger.warning(f"Found {np.sum(overlap_fractions > 1.0)} overlap fractions > 1.0")
+            logger.warning(f"Max overlap fraction: {overlap_fractions.max()}")
+        return valid_overlaps[overlap_fractions >= self.overlap_threshold]
