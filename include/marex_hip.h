@@ -405,6 +405,18 @@ int marex_zstd_decompress_h(const uint8_t* src, int64_t srclen, uint8_t* dst, in
 int marex_blosc_compress_h(const void* src, int64_t nbytes, int typesize, int shuffle, int64_t blocksize, void* dst,
                            int64_t dstcap, int64_t* out_len);
 
+/* Device-side inverse of marex_blosc_compress_h (the chunk format of `extremes_ds.to_zarr(...)`, examples/batch
+ * jobs/run_detect.py:83, for arrays held in HBM): n_chunks chunks of nbytes bytes, chunk i at src + i * nbytes (device),
+ * become frames byte-identical to marex_blosc_compress_h(chunk i, nbytes, typesize, shuffle, blocksize, dst, nbytes + 16,
+ * ...): frame i at dst + i * (nbytes + 16) (device), its length in out_len[i] (device int64).  work: device scratch of
+ * marex_blosc_compress_work_bytes(nbytes, typesize, shuffle, blocksize, n_chunks) bytes.  variant 0 encodes every LZ4
+ * stream with one wave (speculative hashing of 64 positions), 1 with one lane (the serial loop); both write the same bytes.
+ * Asynchronous on the context's stream. */
+int marex_blosc_compress_work_bytes(int64_t nbytes, int typesize, int shuffle, int64_t blocksize, int64_t n_chunks,
+                                    int64_t* out);
+int marex_blosc_compress_d(marex_ctx* ctx, const uint8_t* src, int64_t nbytes, int64_t n_chunks, int typesize, int shuffle,
+                           int64_t blocksize, int variant, uint8_t* work, int64_t work_bytes, uint8_t* dst, int64_t* out_len);
+
 /* Device-side chunk decoding (compressed bytes cross PCIe, the field is born in HBM): n_streams LZ4 block streams --
  * stream s = comp[src_off[s] .. +csize[s]) -> planes[dst_off[s] .. +rawsz[s]) (csize == rawsz: stored, copied) -- one
  * wave each; *status (device int, zeroed by the caller) counts malformed streams.  Then marex_unshuffle_place turns the

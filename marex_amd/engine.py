@@ -8,6 +8,7 @@
 
 from __future__ import annotations
 
+import ctypes as C
 from dataclasses import dataclass
 from typing import Dict, Optional
 
@@ -1046,3 +1047,40 @@ class HotPath:
         )
         self.ctx.check(rc, "marex_mask_ge_const_f32")
         return {"extreme": ext, "n_true": n_true}
+
+    # ------------------------------------------------------------------ Blosc / LZ4 chunk compression (zarr_io.write_array)
+    def blosc_work_bytes(self, nbytes: int, typesize: int, n_chunks: int, blocksize: int = 0, shuffle: int = 1) -> int:
+        """Device scratch ``blosc_compress`` needs for ``n_chunks`` chunks of ``nbytes`` bytes (byte planes, encoded
+        streams and per-stream integers)."""
+        out = C.c_int64(0)
+        rc = self.lib.marex_blosc_compress_work_bytes(int(nbytes), int(typesize), int(shuffle), int(blocksize), int(n_chunks),
+                                                      C.byref(out))
+        if rc != 0:
+            raise ProcessingError("marex_blosc_compress_work_bytes failed", details=f"nbytes {nbytes}, typesize {typesize}")
+        return int(out.value)
+
+    def blosc_compress(self, chunks: torch.Tensor, typesize: int, blocksize: int = 0, shuffle: int = 1, variant: int = 0,
+                       wsp: Optional[dict] = None):
+        """Compress every row of ``chunks`` (contiguous uint8 ``[B, nbytes]`` on this device) into a Blosc-1 / LZ4 frame
+        byte-identical to ``marex_blosc_compress_h`` with ``dstcap = nbytes + 16``.  Returns ``(frames, lengths)``:
+        frames uint8 ``[B, nbytes + 16]`` on the device (row i holds frame i in its first ``lengths[i]`` bytes) and
+        lengths int64 NumPy ``[B]`` (synchronises).  ``variant`` 0: one wave per LZ4 stream, 1: one lane per stream."""
+        self._bind_stream()
+        if chunks.dtype != torch.uint8 or chunks.dim() != 2 or not chunks.is_contiguous() or chunks.device != self.device:
+            raise ProcessingError("blosc_compress: chunks must be a contiguous uint8 [B, nbytes] tensor on the engine's device",
+                                  details=f"got {chunks.dtype} {tuple(chunks.shape)} on {chunks.device}")
+        B, nb = (int(k) for k in chunks.shape)
+        lengths = np.zeros(B, np.int64)
+        if B == 0:
+            return torch.empty((0, nb + 16), dtype=torch.uint8, device=self.device), lengths
+        wb = self.blosc_work_bytes(nb, typesize, B, blocksize, shuffle)
+        work = self._buf(wsp, "blosc_work", (max(wb, 1),), torch.uint8, self.device)
+        frames = self._buf(wsp, "blosc_frames", (B, nb + 16), torch.uint8, self.device)
+        lens = self._buf(wsp, "blosc_lens", (B,), torch.int64, self.device)
+        rc = self.lib.marex_blosc_compress_d(self.ctx.handle, chunks.data_ptr(), nb, B, int(typesize), int(shuffle), int(blocksize),
+                                             int(variant), work.data_ptr(), wb, frames.data_ptr(), lens.data_ptr())
+        self.ctx.check(rc, "marex_blosc_compress_d")
+        lengths[:] = lens.cpu().numpy()
+        if (lengths < 16).any() or (lengths > nb + 16).any():
+            raise ProcessingError("blosc_compress: frame length out of range (internal error)", details=str(lengths[:8]))
+        return frames, lengths

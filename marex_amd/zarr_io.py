@@ -10,12 +10,12 @@ import ctypes as C
 import itertools
 import json
 import os
-from typing import Dict
+from typing import Dict, Optional
 
 import numpy as np
 
 from . import _lib
-from .exceptions import DataValidationError, DependencyError
+from .exceptions import DataValidationError, DependencyError, ProcessingError
 
 
 def _decompress(raw: bytes, nbytes: int) -> bytes:
@@ -365,11 +365,16 @@ def _json_attr(v):
     return v
 
 
-def write_array(path: str, data, chunks=None, dims=None, attrs=None, compress: bool = True, threads: int = 8) -> Dict:
+def write_array(path: str, data, chunks=None, dims=None, attrs=None, compress: bool = True, threads: int = 8,
+                device_compress: Optional[bool] = None) -> Dict:
     """Write one Zarr v2 array directory.  ``data`` is a NumPy array or a torch tensor (host or device; a device tensor
     is brought over one chunk of its first dimension at a time, so a field that fills HBM never needs a host copy of
     itself).  ``chunks`` defaults to the whole array; chunks are compressed by a small thread pool (the C call releases the
-    GIL).  Returns ``{".zarray": ..., ".zattrs": ...}`` for the consolidated metadata."""
+    GIL).  Returns ``{".zarray": ..., ".zattrs": ...}`` for the consolidated metadata.
+
+    A tensor on a GPU is compressed on that GPU (``_write_chunks_device``): only the frames cross PCIe, and every file
+    holds the bytes the host encoder writes.  ``device_compress``: None = automatic (``DEVICE_COMPRESS_AUTO``), True /
+    False force the device / host encoder (True needs ``compress`` and a tensor on a GPU)."""
     from concurrent.futures import ThreadPoolExecutor
 
     is_torch = hasattr(data, "device") and hasattr(data, "cpu")
@@ -379,6 +384,12 @@ def write_array(path: str, data, chunks=None, dims=None, attrs=None, compress: b
     chunks = tuple(int(min(max(c, 1), max(n, 1))) for c, n in zip(shape if chunks is None else chunks, shape))
     if len(chunks) != len(shape):
         raise DataValidationError("chunks do not match the array rank", details=f"shape {shape}, chunks {chunks}")
+    on_gpu = is_torch and getattr(data.device, "type", "cpu") == "cuda"
+    if device_compress and not (compress and on_gpu and shape):
+        raise DataValidationError("device_compress=True needs compress=True and a tensor of rank >= 1 on a GPU",
+                                  details=f"compress {compress}, device {getattr(data, 'device', 'host')}, shape {shape}")
+    use_device = compress and on_gpu and bool(shape) and (
+        device_compress if device_compress is not None else DEVICE_COMPRESS_AUTO.get(dtype.kind, False))
     os.makedirs(path, exist_ok=True)
     fill = "NaN" if dtype.kind == "f" else None  # what xarray writes (see the reference's stores)
     zarray = {"zarr_format": 2, "shape": list(shape), "chunks": list(chunks), "dtype": zdtype, "order": "C", "filters": None,
@@ -408,6 +419,9 @@ def write_array(path: str, data, chunks=None, dims=None, attrs=None, compress: b
             f.write(payload)
 
     grid = [range((n + c - 1) // c) for n, c in zip(shape, chunks)]
+    if use_device:
+        _write_chunks_device(path, data, shape, chunks, dtype, grid, threads)
+        return {".zarray": zarray, ".zattrs": zattrs}
     with ThreadPoolExecutor(max_workers=max(1, threads)) as pool:
         for i0 in (grid[0] if shape else [0]):
             part = slab(i0)
@@ -421,6 +435,88 @@ def write_array(path: str, data, chunks=None, dims=None, attrs=None, compress: b
     return {".zarray": zarray, ".zattrs": zattrs}
 
 
+#: automatic choice of ``write_array`` for tensors on a GPU, per dtype kind (b bool, i / u integers, f floats): True =
+#: compress on the device.  DESIGN.md records the measurements behind it.
+DEVICE_COMPRESS_AUTO = {"b": True, "i": True, "u": True, "f": True}
+#: LZ4 encoder of the device path per dtype kind: 0 = one wave per stream (speculative hashing, 64-lane match extension;
+#: wins on the long zero runs of ID fields), 1 = one lane per stream (wins on masks and float fields, whose matches are
+#: short).  Both write the same bytes; DESIGN.md records the A/B.
+DEVICE_ENCODER_VARIANT = {"b": 1, "i": 0, "u": 0, "f": 1}
+#: raw chunk bytes compressed per device call: enough streams to fill the GPU, bounded pinned / device buffers
+DEVICE_BATCH_BYTES = 1 << 30
+
+
+def compress_chunks_device(chunks, typesize: int, eng=None, blocksize: int = 0, shuffle: int = 1, variant: int = 0):
+    """Blosc-1 / LZ4 frames of the rows of ``chunks`` (a uint8 ``[B, nbytes]`` tensor on a GPU), encoded on that GPU:
+    ``list`` of ``bytes``, each identical to what ``marex_blosc_compress_h`` writes for the row."""
+    if eng is None:
+        from .detect import get_engine
+
+        eng = get_engine(chunks.device.index or 0)
+    frames, lengths = eng.blosc_compress(chunks.contiguous(), typesize, blocksize, shuffle, variant)
+    host = frames.cpu().numpy()
+    return [host[i, : int(n)].tobytes() for i, n in enumerate(lengths)]
+
+
+def _write_chunks_device(path: str, data, shape, chunks, dtype: np.dtype, grid, threads: int) -> None:
+    """Device half of ``write_array``: chunks are cut out of ``data`` (padded as ``put`` pads them: NaN for floats, 0
+    otherwise) into a staging buffer in HBM, compressed there in batches (``HotPath.blosc_compress``), and only the
+    frames are copied to pinned host memory and written out by a small thread pool."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    import torch
+
+    from .detect import get_engine
+
+    eng = get_engine(data.device.index or 0)
+    ts = dtype.itemsize
+    nbytes = int(np.prod(chunks)) * ts
+    idxs = list(itertools.product(*grid))
+    per_chunk = 2 * nbytes + 16 + 8 + eng.blosc_work_bytes(nbytes, ts, 1)  # staging + frames + lengths + work
+    slack = 64 << 20
+    free, _ = torch.cuda.mem_get_info(eng.device)
+    fit = (int(free * 0.9) - slack) // per_chunk
+    if fit < 1:
+        raise ProcessingError(f"device compression: one chunk of {nbytes / 1e9:.3f} GB needs {per_chunk / 1e9:.3f} GB of device "
+                              f"memory, {free / 1e9:.3f} GB are free", details=f"chunks {chunks}, dtype {dtype}; pass "
+                              "device_compress=False or smaller chunks")
+    B = int(max(1, min(len(idxs), fit, DEVICE_BATCH_BYTES // max(nbytes, 1))))
+    fill = float("nan") if dtype.kind == "f" else 0
+    stage = torch.empty((B,) + tuple(chunks), dtype=data.dtype, device=eng.device)
+    wsp: dict = {}
+
+    def write(name, payload):
+        with open(os.path.join(path, name), "wb") as f:
+            f.write(payload)
+
+    with ThreadPoolExecutor(max_workers=max(1, threads)) as pool, torch.cuda.device(eng.device):
+        jobs = []
+        for b0 in range(0, len(idxs), B):
+            batch = idxs[b0: b0 + B]
+            for b, idx in enumerate(batch):
+                sel = tuple(slice(i * c, min((i + 1) * c, n)) for i, c, n in zip(idx, chunks, shape))
+                block = data[sel]
+                if tuple(block.shape) != tuple(chunks):
+                    stage[b].fill_(fill)
+                    stage[b][tuple(slice(0, k) for k in block.shape)] = block
+                else:
+                    stage[b].copy_(block)
+            raw = stage[: len(batch)].view(torch.uint8).reshape(len(batch), nbytes)
+            frames, lengths = eng.blosc_compress(raw, ts, variant=DEVICE_ENCODER_VARIANT.get(dtype.kind, 0), wsp=wsp)
+            offs = np.concatenate([[0], np.cumsum(lengths)])
+            host = torch.empty(int(offs[-1]), dtype=torch.uint8, pin_memory=True)
+            for b in range(len(batch)):
+                host[int(offs[b]): int(offs[b + 1])].copy_(frames[b, : int(lengths[b])], non_blocking=True)
+            torch.cuda.current_stream(eng.device).synchronize()
+            hn = host.numpy()
+            for j in jobs:
+                j.result()
+            jobs = [pool.submit(write, ".".join(str(i) for i in idx), hn[int(offs[b]): int(offs[b + 1])].tobytes())
+                    for b, idx in enumerate(batch)]
+        for j in jobs:
+            j.result()
+
+
 def encode_cf_time(values) -> tuple:
     """datetime64 axis -> (int64 ``days since`` the first day, CF attrs): the encoding xarray picks for a daily axis."""
     t = np.asarray(values).astype("datetime64[D]")
@@ -428,11 +524,13 @@ def encode_cf_time(values) -> tuple:
     return (t - t0).astype(np.int64), {"units": f"days since {t0} 00:00:00", "calendar": "proleptic_gregorian"}
 
 
-def write_dataset(store: str, ds, chunks: Dict[str, int] | None = None, compress: bool = True, threads: int = 8) -> None:
+def write_dataset(store: str, ds, chunks: Dict[str, int] | None = None, compress: bool = True, threads: int = 8,
+                  device_compress: Optional[bool] = None) -> None:
     """``ds.to_zarr(store, mode="w")`` for the Dataset ``preprocess_data`` returns (stand-in or device-resident variables):
     every data variable and coordinate becomes an array directory, attributes go to ``.zattrs``, and ``.zmetadata`` holds
     the consolidated copy that ``xr.open_zarr`` reads first.  ``chunks`` maps dimension names to chunk lengths (default:
-    ``time`` in steps of 25 -- the reference's output chunking, detect.py:785-792 -- everything else whole)."""
+    ``time`` in steps of 25 -- the reference's output chunking, detect.py:785-792 -- everything else whole).
+    ``device_compress`` applies to the variables held on a GPU (``write_array``); host variables take the host encoder."""
     import shutil
 
     chunks = dict({"time": 25}, **(chunks or {}))
@@ -461,7 +559,8 @@ def write_dataset(store: str, ds, chunks: Dict[str, int] | None = None, compress
             if aux:
                 attrs["coordinates"] = " ".join(aux)  # non-index coordinates (lat / lon of an unstructured mesh)
         ch = None if is_coord else tuple(chunks.get(d, n) for d, n in zip(dims, data.shape))
-        m = write_array(os.path.join(store, name), data, ch, dims, attrs, compress, threads)
+        on_gpu = hasattr(data, "cpu") and getattr(data.device, "type", "cpu") == "cuda" and data.dim() > 0
+        m = write_array(os.path.join(store, name), data, ch, dims, attrs, compress, threads, device_compress if on_gpu else None)
         meta[f"{name}/.zarray"] = m[".zarray"]
         meta[f"{name}/.zattrs"] = m[".zattrs"]
     json.dump({"zarr_consolidated_format": 1, "metadata": meta}, open(os.path.join(store, ".zmetadata"), "w"), indent=1)
