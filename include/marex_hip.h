@@ -459,6 +459,44 @@ int marex_overlap_count_i32(marex_ctx* ctx, const int32_t* ids, int64_t T, int64
 int marex_overlap_pairs_i32(marex_ctx* ctx, const int32_t* ids, int64_t T, int64_t C, int64_t cap, uint64_t* keys,
                             uint64_t* counts, uint64_t* stats, int64_t out_cap, uint64_t* out_keys, uint64_t* out_counts);
 
+/* Stages of the merge tracker on grids (tracker.split_and_merge_objects / consolidate_object_ids /
+ * cluster_rename_objects_and_props, marEx/track.py:2554-3802).  Slices are int32 [ny][nx], fields int32 [T][ny][nx];
+ * values <= 0 are background.  Distances are float64 sqrt(dy * dy + dx * dx), dx wrapped by +-nx when |dx| > nx / 2 and
+ * wrap != 0; the first nearest parent wins.
+ *
+ * marex_relabel_i32 (replaces the `where(data != child, first)` renames of track.py:2629-2631 and the apply_ufunc map of
+ *   2897-2924): ids[i] = vals[j] where keys[j] == ids[i] (keys ascending, distinct; IDs without an entry unchanged) or,
+ *   with keys == NULL, ids[i] = vals[ids[i]] for 0 < ids[i] < n_keys.  In place.
+ * marex_partition_centroid_i32 (wrapped_euclidian_distance_mask_parallel + argmin, track.py:3548-3553, 4826-4873): every
+ *   cell of child child_keys[k] (ascending) takes lab[j] of the parent entry j in off[k] .. off[k + 1] whose centroid
+ *   (pcy[j], pcx[j]) is nearest.  In place, all merging children of one iteration at once.
+ * marex_nn_bucket_count_i32 / marex_partition_nn_i32 (partition_nn_grid, track.py:4972-5113): parent entry j has bucket
+ *   size gs[j], ngy[j] x ngx[j] buckets at base[j] .. of n_buckets, search radius maxd[j]; parent ID par_keys[q]
+ *   (ascending) owns entries pent[poff[q] .. poff[q + 1]).  The count pass sets bstart[0 .. n_buckets] to the exclusive
+ *   scan of the (cell of prev, entry) counts per bucket (cnt: work, n_buckets); bstart[n_buckets] = n_cells.  The
+ *   partition pass sorts those cells into cells[n_cells] by bucket (cursor: work, n_buckets) and gives every child cell
+ *   of ids the label of the parent with the nearest cell in the 3 x 3 buckets around its own (bucket indices periodic in
+ *   y and x) within maxd, else of the nearest centroid.
+ * marex_event_moments_i32 (calculate_area_centroid_for_slice and process_timestep, track.py:2936-2976, 3140-3247): for
+ *   slot s = t * n_ev + e - 1 of the event field ev (1 .. n_ev): acc[s][0..4] = cells, sum y, sum x, sum of
+ *   (x > nx / 2 ? x - nx : x), flags (1: a cell with x < 100, 2: a cell with x >= nx - 100); gid[s] = the largest ID of
+ *   orig under the slot's cells (0 when empty); with w (float32 [ny][nx]) also wacc[s][0..3] = float64 sums of w, w y,
+ *   w x, w x_shifted.  acc, gid (and wacc) are zeroed first; integer sums are bitwise reproducible. */
+int marex_relabel_i32(marex_ctx* ctx, int32_t* ids, int64_t n, const int32_t* keys, const int32_t* vals, int n_keys);
+int marex_partition_centroid_i32(marex_ctx* ctx, int32_t* ids, int ny, int nx, const int32_t* child_keys, int n_child,
+                                 const int32_t* off, const double* pcy, const double* pcx, const int32_t* lab, int wrap);
+int marex_nn_bucket_count_i32(marex_ctx* ctx, const int32_t* prev, int ny, int nx, const int32_t* par_keys, int n_par,
+                              const int32_t* poff, const int32_t* pent, const int32_t* gs, const int32_t* ngy,
+                              const int32_t* ngx, const int64_t* base, int64_t n_buckets, int64_t* cnt, int64_t* bstart);
+int marex_partition_nn_i32(marex_ctx* ctx, int32_t* ids, const int32_t* prev, int ny, int nx, const int32_t* par_keys,
+                           int n_par, const int32_t* poff, const int32_t* pent, const int32_t* child_keys, int n_child,
+                           const int32_t* off, const double* pcy, const double* pcx, const int32_t* lab, const int32_t* gs,
+                           const int32_t* ngy, const int32_t* ngx, const int32_t* maxd, const int64_t* base,
+                           int64_t n_buckets, const int64_t* bstart, int64_t* cursor, int32_t* cells, int64_t n_cells,
+                           int wrap);
+int marex_event_moments_i32(marex_ctx* ctx, const int32_t* ev, const int32_t* orig, int64_t T, int ny, int nx, int n_ev,
+                            const float* w, uint64_t* acc, double* wacc, int32_t* gid);
+
 /* out[c, r] = in[r, c]  (thresholds [366, C] -> the reference's (cells, dayofyear) order) */
 int marex_transpose_f32(marex_ctx* ctx, const float* in, int64_t rows, int64_t cols, float* out);
 

@@ -94,6 +94,13 @@ PROTOTYPES = {
     "marex_object_compact": (_i32, [_p, _i64, _i32, _p, _p, _p, _p, _p, _p]),
     "marex_overlap_count_i32": (_i32, [_p, _p, _i64, _i64, _p]),
     "marex_overlap_pairs_i32": (_i32, [_p, _p, _i64, _i64, _i64, _p, _p, _p, _i64, _p, _p]),
+    "marex_relabel_i32": (_i32, [_p, _p, _i64, _p, _p, _i32]),
+    "marex_partition_centroid_i32": (_i32, [_p, _p, _i32, _i32, _p, _i32, _p, _p, _p, _p, _i32]),
+    "marex_nn_bucket_count_i32": (_i32, [_p, _p, _i32, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _i64, _p, _p]),
+    "marex_partition_nn_i32": (
+        _i32, [_p, _p, _p, _i32, _i32, _p, _i32, _p, _p, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p, _p, _p,
+               _i64, _i32]),
+    "marex_event_moments_i32": (_i32, [_p, _p, _p, _i64, _i32, _i32, _i32, _p, _p, _p, _p]),
 }
 
 KERNEL_IDS = {

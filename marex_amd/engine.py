@@ -887,6 +887,120 @@ class HotPath:
                                   details=f"largest overlap {int(c.max())} cells")
         return np.stack([k >> 32, k & 0xFFFFFFFF, c], axis=1).astype(np.int32)
 
+    # ------------------------------------------------------------------ merge tracker stages (track.py:2554-3802)
+    def _i32(self, a) -> torch.Tensor:
+        return self._dev(np.asarray(a, dtype=np.int32))
+
+    def relabel(self, ids: torch.Tensor, vals: np.ndarray, keys: Optional[np.ndarray] = None) -> None:
+        """In place: ``ids`` (contiguous int32 on the device) -> ``vals[j]`` where ``keys[j]`` equals the ID (``keys``
+        ascending; IDs without an entry stay), or with ``keys=None`` -> ``vals[id]`` for ``0 < id < len(vals)``."""
+        self._bind_stream()
+        if ids.dtype != torch.int32 or not ids.is_contiguous() or ids.device != self.device:
+            raise ProcessingError("relabel: ids must be a contiguous int32 tensor on the engine's device")
+        if ids.numel() == 0 or len(vals) == 0:
+            return
+        v = self._i32(vals)
+        k = self._i32(keys) if keys is not None else None
+        rc = self.lib.marex_relabel_i32(self.ctx.handle, ids.data_ptr(), ids.numel(), k.data_ptr() if k is not None else None,
+                                        v.data_ptr(), len(vals))
+        self.ctx.check(rc, "marex_relabel_i32")
+
+    def partition_centroid(self, cur: torch.Tensor, ny: int, nx: int, child_keys, off, pcy, pcx, lab, wrap: bool) -> None:
+        """In place on the slice ``cur`` (int32 ``ny * nx``): every cell of child ``child_keys[k]`` takes ``lab[j]`` of the
+        nearest parent centroid ``(pcy[j], pcx[j])``, ``off[k] <= j < off[k + 1]`` (first minimum)."""
+        self._bind_stream()
+        t = [self._i32(child_keys), self._i32(off), self._dev(np.asarray(pcy, np.float64)),
+             self._dev(np.asarray(pcx, np.float64)), self._i32(lab)]
+        rc = self.lib.marex_partition_centroid_i32(self.ctx.handle, cur.data_ptr(), int(ny), int(nx), t[0].data_ptr(),
+                                                   len(child_keys), t[1].data_ptr(), t[2].data_ptr(), t[3].data_ptr(),
+                                                   t[4].data_ptr(), int(bool(wrap)))
+        self.ctx.check(rc, "marex_partition_centroid_i32")
+
+    def partition_nn(self, cur: torch.Tensor, prev: torch.Tensor, ny: int, nx: int, child_keys, off, parents, pcy, pcx, lab,
+                     maxd, wrap: bool) -> None:
+        """In place on the slice ``cur``: every cell of child ``child_keys[k]`` takes ``lab[j]`` of the parent
+        ``parents[j]`` (``off[k] <= j < off[k + 1]``) with the nearest cell in ``prev`` among its cells in the 3 x 3
+        buckets of size ``max(2, maxd[j] // 4)`` around the child cell's bucket and within ``maxd[j]``, else of the
+        nearest parent centroid (partition_nn_grid, track.py:4972-5113)."""
+        self._bind_stream()
+        parents = np.asarray(parents, np.int64)
+        maxd = np.asarray(maxd, np.int64)
+        gs = np.maximum(2, maxd // 4)
+        ngy, ngx = (ny + gs - 1) // gs, (nx + gs - 1) // gs
+        nb = ngy * ngx
+        base = np.concatenate([[0], np.cumsum(nb)[:-1]]).astype(np.int64)
+        n_buckets = int(nb.sum())
+        order = np.argsort(parents, kind="stable")
+        par_keys, first = np.unique(parents[order], return_index=True)
+        poff = np.append(first, len(parents)).astype(np.int32)
+        t = {k: self._i32(v) for k, v in (("par", par_keys), ("poff", poff), ("pent", order), ("gs", gs), ("ngy", ngy),
+                                           ("ngx", ngx), ("maxd", maxd), ("ck", child_keys), ("off", off), ("lab", lab))}
+        base_d = self._dev(base)
+        pcy_d, pcx_d = self._dev(np.asarray(pcy, np.float64)), self._dev(np.asarray(pcx, np.float64))
+        cnt = torch.empty(n_buckets, dtype=torch.int64, device=self.device)
+        bstart = torch.empty(n_buckets + 1, dtype=torch.int64, device=self.device)
+        rc = self.lib.marex_nn_bucket_count_i32(self.ctx.handle, prev.data_ptr(), int(ny), int(nx), t["par"].data_ptr(),
+                                                len(par_keys), t["poff"].data_ptr(), t["pent"].data_ptr(), t["gs"].data_ptr(),
+                                                t["ngy"].data_ptr(), t["ngx"].data_ptr(), base_d.data_ptr(), n_buckets,
+                                                cnt.data_ptr(), bstart.data_ptr())
+        self.ctx.check(rc, "marex_nn_bucket_count_i32")
+        n_cells = int(bstart[n_buckets].item())
+        if n_cells <= 0:
+            raise ProcessingError("partition_nn: the parents have no cells in the previous slice")
+        cells = torch.empty(n_cells, dtype=torch.int32, device=self.device)
+        rc = self.lib.marex_partition_nn_i32(self.ctx.handle, cur.data_ptr(), prev.data_ptr(), int(ny), int(nx),
+                                             t["par"].data_ptr(), len(par_keys), t["poff"].data_ptr(), t["pent"].data_ptr(),
+                                             t["ck"].data_ptr(), len(child_keys), t["off"].data_ptr(), pcy_d.data_ptr(),
+                                             pcx_d.data_ptr(), t["lab"].data_ptr(), t["gs"].data_ptr(), t["ngy"].data_ptr(),
+                                             t["ngx"].data_ptr(), t["maxd"].data_ptr(), base_d.data_ptr(), n_buckets,
+                                             bstart.data_ptr(), cnt.data_ptr(), cells.data_ptr(), n_cells, int(bool(wrap)))
+        self.ctx.check(rc, "marex_partition_nn_i32")
+
+    def id_spans(self, ids: torch.Tensor):
+        """``(tmin, tmax)`` int32 host arrays over IDs 0..max of ``ids`` int32 ``[T, C]``: the first / last timestep of
+        every ID (INT_MAX / -1 when absent); ``None`` when the field has no ID > 0."""
+        self._bind_stream()
+        T, Cn = self._ids_check(ids)
+        _, hi = self.ids_minmax(ids)
+        if hi <= 0:
+            return None
+        nid = hi + 1
+        ntiles = (nid + 4095) // 4096
+        self._check_fits(16 * nid + 16 * ntiles, "ID spans", f"per-ID first / last timestep for IDs 0..{hi}")
+        tmin = torch.empty(nid, dtype=torch.int32, device=self.device)
+        tmax = torch.empty(nid, dtype=torch.int32, device=self.device)
+        off = torch.empty(nid, dtype=torch.int64, device=self.device)
+        work = torch.empty(2 * ntiles, dtype=torch.int64, device=self.device)
+        total = torch.empty(1, dtype=torch.int64, device=self.device)
+        rc = self.lib.marex_object_spans_i32(self.ctx.handle, ids.data_ptr(), T, Cn, hi, tmin.data_ptr(), tmax.data_ptr(),
+                                             off.data_ptr(), work.data_ptr(), total.data_ptr())
+        self.ctx.check(rc, "marex_object_spans_i32")
+        return tmin.cpu().numpy(), tmax.cpu().numpy()
+
+    def event_moments(self, ev: torch.Tensor, orig: torch.Tensor, ny: int, nx: int, n_ev: int,
+                      weights: Optional[torch.Tensor] = None) -> Dict[str, np.ndarray]:
+        """Per (timestep, event) of the event field ``ev`` (int32 ``[T, ny * nx]``, events 1..n_ev): ``mom`` int64
+        ``[T, n_ev, 5]`` (cells, sum y, sum x, sum of x shifted by -nx right of nx / 2, near-edge flags), ``gid`` int32
+        ``[T, n_ev]`` (largest ID of ``orig`` under the slot) and, with float32 ``weights`` of a slice, ``wmom`` float64
+        ``[T, n_ev, 4]`` (sums of w, w y, w x, w x_shifted)."""
+        self._bind_stream()
+        T, Cn = self._ids_check(ev)
+        self._ids_check(orig)
+        slots = T * int(n_ev)
+        self._check_fits(slots * (40 + 4 + (32 if weights is not None else 0)), "event properties",
+                         f"{T} x {n_ev} dense (timestep, event) slots")
+        acc = torch.empty((slots, 5), dtype=torch.int64, device=self.device)
+        gid = torch.empty(slots, dtype=torch.int32, device=self.device)
+        wacc = torch.empty((slots, 4), dtype=torch.float64, device=self.device) if weights is not None else None
+        rc = self.lib.marex_event_moments_i32(self.ctx.handle, ev.data_ptr(), orig.data_ptr(), T, int(ny), int(nx), int(n_ev),
+                                              weights.data_ptr() if weights is not None else None, acc.data_ptr(),
+                                              wacc.data_ptr() if wacc is not None else None, gid.data_ptr())
+        self.ctx.check(rc, "marex_event_moments_i32")
+        out = {"mom": acc.cpu().numpy().reshape(T, n_ev, 5), "gid": gid.cpu().numpy().reshape(T, n_ev)}
+        if wacc is not None:
+            out["wmom"] = wacc.cpu().numpy().reshape(T, n_ev, 4)
+        return out
+
     def filter_small_objects(self, data_bin: torch.Tensor, ny: int, nx: int, area_filter_quartile: float = 0.5,
                              area_filter_absolute: Optional[float] = None, regional_mode: bool = False,
                              wsp: Optional[dict] = None) -> Dict[str, object]:

@@ -1,5 +1,5 @@
-"""Event tracking without merging on the device: ``marEx.tracker(..., allow_merging=False).run()`` for gridded data
-(marEx/track.py:1162-1232, 1370-1497).
+"""Event tracking on the device: ``marEx.tracker(...).run()`` for gridded data, without merging (marEx/track.py:1162-1232,
+1370-1497) and with merging and splitting (track.py:2554-3802; see ``tracker.track_objects``).
 
 The pipeline stays in HBM from the extreme mask to the ID field: ``fill_holes`` -> ``fill_time_gaps`` ->
 ``filter_small_objects`` -> 26-connected labelling in (time, y, x), periodic in x unless ``regional_mode``
@@ -15,7 +15,7 @@ from typing import Dict, List, Literal, Optional, Tuple, Union
 
 import numpy as np
 
-from .exceptions import ConfigurationError, TrackingError, create_data_validation_error
+from .exceptions import ConfigurationError, ProcessingError, TrackingError, create_data_validation_error
 
 logger = logging.getLogger("marex_amd")
 
@@ -51,22 +51,135 @@ def _coord_dims(c, default):
     return tuple(d) if d else default
 
 
+def _time_chunk_layout(data_bin, dimensions, timechunks) -> Optional[List[int]]:
+    """Lengths of the time chunks the merge loop walks (track.py:3379-3382): the time chunk tuple of ``data_bin``
+    (``.chunks`` of a Dask-backed DataArray, else the store's regular chunk in ``encoding["chunks"]``), else regular chunks of
+    ``timechunks`` counted from t = 0 with the remainder last; None when none of them is known.  A ``timechunks`` that
+    disagrees with data_bin's own chunks is ignored with a warning: the merge results follow the chunks the loop walks."""
+    timedim = (dimensions or {}).get("time", "time")
+    dims = tuple(getattr(data_bin, "dims", ()) or ())
+    shape = tuple(getattr(data_bin, "shape", ()) or ())
+    if timedim not in dims or len(shape) != len(dims):
+        return None
+    k = dims.index(timedim)
+    T = int(shape[k])
+    regular = lambda step: [min(step, T - s) for s in range(0, T, step)]  # noqa: E731
+    if timechunks is not None and int(timechunks) <= 0:
+        raise ConfigurationError("timechunks must be a positive number of timesteps", details=f"timechunks={timechunks}")
+    own = None
+    ch = getattr(data_bin, "chunks", None)
+    if isinstance(ch, (tuple, list)) and len(ch) == len(dims) and isinstance(ch[k], (tuple, list)):
+        c = [int(v) for v in ch[k]]
+        if sum(c) == T and all(v > 0 for v in c):
+            own = c
+    enc = (getattr(data_bin, "encoding", None) or {}).get("chunks")
+    if own is None and isinstance(enc, (tuple, list)) and len(enc) == len(dims) and int(enc[k]) > 0:
+        own = regular(int(enc[k]))
+    if own is not None:
+        if timechunks is not None and own != regular(int(timechunks)):
+            logger.warning(f"timechunks={int(timechunks)} is ignored: data_bin's own time chunks {tuple(own)} decide the "
+                           "merge loop (and its results); rechunk data_bin to change them")
+        return own
+    return regular(int(timechunks)) if timechunks is not None else None
+
+
+def _components(n: int, a: np.ndarray, b: np.ndarray) -> np.ndarray:
+    """Connected components of nodes 0..n-1 under the edges (a, b): labels 0..N-1 numbered by each component's smallest
+    node (scipy's connected_components order): hooking the larger root under the smaller, then pointer jumping."""
+    lab = np.arange(n, dtype=np.int64)
+    while True:
+        ra, rb = lab[a], lab[b]
+        hi, lo = np.maximum(ra, rb), np.minimum(ra, rb)
+        ch = hi != lo
+        if not ch.any():
+            break
+        np.minimum.at(lab, hi[ch], lo[ch])
+        while True:
+            nxt = lab[lab]
+            if np.array_equal(nxt, lab):
+                break
+            lab = nxt
+    roots = np.unique(lab)
+    return np.searchsorted(roots, lab)
+
+
+class _Props:
+    """Area and centroid of the live object IDs, indexed densely by ID (the reference's object_props Dataset)."""
+
+    def __init__(self, ids, area, cy, cx):
+        n = int(ids.max()) + 1 if len(ids) else 1
+        self.area = np.zeros(n)
+        self.cy = np.zeros(n)
+        self.cx = np.zeros(n)
+        self.alive = np.zeros(n, dtype=bool)
+        self.set(ids, area, cy, cx)
+
+    def _grow(self, hi: int) -> None:
+        if hi < self.alive.size:
+            return
+        n = max(hi + 1, 2 * self.alive.size)
+        for k in ("area", "cy", "cx", "alive"):
+            a = getattr(self, k)
+            b = np.zeros(n, dtype=a.dtype)
+            b[:a.size] = a
+            setattr(self, k, b)
+
+    def set(self, ids, area, cy, cx) -> None:
+        ids = np.asarray(ids, dtype=np.int64)
+        if ids.size:
+            self._grow(int(ids.max()))
+            self.area[ids], self.cy[ids], self.cx[ids] = area, cy, cx
+            self.alive[ids] = True
+
+    def has(self, i) -> np.ndarray:
+        i = np.asarray(i, dtype=np.int64)
+        ok = (i >= 0) & (i < self.alive.size)
+        return ok & self.alive[np.where(ok, i, 0)]
+
+    def ids(self) -> np.ndarray:
+        return np.nonzero(self.alive)[0]
+
+    def max_id(self) -> int:
+        i = self.ids()
+        return int(i[-1]) if i.size else 0
+
+    def dataset(self):
+        from .xr_compat import DataArray, Dataset
+
+        i = self.ids()
+        coord = {"ID": ("ID", i.astype(np.int64))}
+        return Dataset({"area": DataArray(self.area[i], dims=("ID",), coords=coord),
+                        "centroid": DataArray(np.stack([self.cy[i], self.cx[i]]), dims=("component", "ID"), coords=coord)},
+                       coords=coord)
+
+    @classmethod
+    def of(cls, object_props) -> "_Props":
+        if isinstance(object_props, _Props):
+            return object_props
+        ids = np.asarray(object_props["ID"].values, dtype=np.int64)
+        c = np.asarray(object_props["centroid"].values, dtype=np.float64)
+        return cls(ids, np.asarray(object_props["area"].values, dtype=np.float64), c[0], c[1])
+
+
 class tracker:  # noqa: N801 -- the reference's public name (marEx.tracker)
     """Identify extreme events as connected regions in (time, y, x) of a binary field on a grid.
 
-    The constructor takes the reference's arguments (track.py:323-348).  Supported here: gridded data with
-    ``allow_merging=False`` -- the reference's "basic" tracker.  ``allow_merging=True`` (the reference's default),
-    ``unstructured_grid=True`` and ``checkpoint="save"`` / ``"load"`` raise :class:`ConfigurationError`.
+    The constructor takes the reference's arguments (track.py:323-348).  Supported here: gridded data, with
+    ``allow_merging=False`` (the reference's "basic" tracker) and with ``allow_merging=True`` (the default: merging and
+    splitting, centroid or ``nn_partitioning``).  Merge results depend on the time chunks the per-timestep loop walks: they
+    are taken from ``data_bin.chunks`` (Dask), from ``data_bin.encoding["chunks"]`` (a store's chunks) or from the
+    ``timechunks`` keyword (regular chunks from t = 0); with none of them ``allow_merging=True`` raises
+    :class:`ConfigurationError`.  ``unstructured_grid=True`` and ``checkpoint="save"`` / ``"load"`` raise too.
 
-    Accepted and ignored: ``grid_resolution`` and ``cell_areas`` (validated like the reference does; for gridded data the
-    reference counts areas in cells anyway, track.py:1499-1518, 2337), ``temp_dir``, ``nn_partitioning``,
-    ``max_iteration`` (merge tracking and meshes only), ``debug``, ``verbose``, ``quiet`` (logging) and
-    ``coordinate_units`` (the output carries the input's lat / lon unchanged).  ``overlap_threshold`` is stored and used
-    by :meth:`enforce_overlap_threshold`.
+    ``grid_resolution`` and ``cell_areas`` weight the final area and centroid of merge tracking (object properties count
+    cells, as the reference's do, track.py:1499-1518, 2337).  Accepted and ignored: ``temp_dir``,
+    ``max_iteration`` (meshes only), ``debug``, ``verbose`` and ``quiet`` (logging).  ``coordinate_units`` is resolved as
+    the reference does (track.py:919-976) when merging; the basic tracker carries the input's lat / lon unchanged.
 
-    The object stages of the reference's merge tracker are public methods here too (track.py:1499-1518, 2050-2552):
-    :meth:`compute_area`, :meth:`calculate_centroid`, :meth:`calculate_object_properties` (on the device),
-    :meth:`check_overlap_slice` and :meth:`find_overlapping_objects` (on the device) and :meth:`enforce_overlap_threshold`.
+    The stages of the reference's merge tracker are public methods here too (track.py:1499-1518, 2050-3802):
+    :meth:`compute_area`, :meth:`calculate_centroid`, :meth:`calculate_object_properties`, :meth:`check_overlap_slice`,
+    :meth:`find_overlapping_objects`, :meth:`enforce_overlap_threshold`, :meth:`consolidate_object_ids`,
+    :meth:`split_and_merge_objects`, :meth:`cluster_rename_objects_and_props` and :meth:`track_objects`, on the device.
 
     ``data_bin`` may be device resident -- a DataArray whose data is a torch tensor (bool or uint8) on the GPU, e.g. from
     ``zarr_io.open_dataarray_device`` -- and is then consumed without a host round trip.  ``device`` picks the GPU.
@@ -98,12 +211,19 @@ class tracker:  # noqa: N801 -- the reference's public name (marEx.tracker)
         regional_mode: bool = False,
         coordinate_units: Optional[Literal["degrees", "radians"]] = None,
         device: int = 0,
+        timechunks: Optional[int] = None,
     ) -> None:
-        supported = "gridded data with allow_merging=False and no checkpointing"
-        if allow_merging:
-            raise ConfigurationError("allow_merging=True is not supported on the device path",
-                                     details=f"supported: {supported} (the reference's basic tracker)",
-                                     suggestions=["Pass allow_merging=False"])
+        supported = "gridded data without checkpointing"
+        self._time_chunks = None
+        if allow_merging and not unstructured_grid:
+            # merge results depend on the time chunks the per-timestep loop walks (track.py:3379-3382, 3602-3615)
+            self._time_chunks = _time_chunk_layout(data_bin, dimensions, timechunks)
+            if self._time_chunks is None:
+                raise ConfigurationError("allow_merging=True is not supported without a time chunking of data_bin",
+                                         details="the reference refuses unchunked input (track.py:411-418), and merges "
+                                                 "depend on the time chunks",
+                                         suggestions=["Pass timechunks=<steps per chunk>", "Chunk data_bin in time",
+                                                      "Pass allow_merging=False"])
         if unstructured_grid:
             raise ConfigurationError("unstructured_grid=True is not supported by the device tracker",
                                      details=f"supported: {supported}; the reference tracks meshes with the merge tracker only")
@@ -128,6 +248,7 @@ class tracker:  # noqa: N801 -- the reference's public name (marEx.tracker)
         self.T_fill = T_fill
         self._resolve_area_filtering_parameters(area_filter_quartile, area_filter_absolute)
         self.allow_merging = allow_merging
+        self.nn_partitioning = bool(nn_partitioning)
         self.overlap_threshold = overlap_threshold
         self.unstructured_grid = unstructured_grid
         self.checkpoint = checkpoint
@@ -136,6 +257,10 @@ class tracker:  # noqa: N801 -- the reference's public name (marEx.tracker)
         self.lat_init = data_bin.coords[self.ycoord]
         self.lon_init = data_bin.coords[self.xcoord]
         self.time_values = np.asarray(data_bin.coords[self.timecoord].values)
+        self.coordinate_units = coordinate_units
+        if self.allow_merging:
+            self._unify_coordinates()
+            self._cell_weights = self._merge_cell_weights(cell_areas, grid_resolution)
 
     # ------------------------------------------------------------------ validation (track.py:493-749)
     def _resolve_area_filtering_parameters(self, area_filter_quartile, area_filter_absolute) -> None:
@@ -293,12 +418,15 @@ class tracker:  # noqa: N801 -- the reference's public name (marEx.tracker)
 
     # ------------------------------------------------------------------ pipeline (track.py:1162-1497)
     def run(self, return_merges: bool = False, checkpoint: Optional[str] = None):
-        """``run_preprocess`` -> ``run_tracking`` -> ``run_stats_attributes``; returns the events Dataset
-        (``return_merges`` has nothing to return without merging)."""
+        """``run_preprocess`` -> ``run_tracking`` -> ``run_stats_attributes``; returns the events Dataset, and with
+        ``return_merges`` and merging also the merge events: ``(events_ds, merges_ds)`` (track.py:1162-1232)."""
         self._check_size(self.data_bin.shape)
         data_bin_preprocessed, object_stats = self.run_preprocess(checkpoint=checkpoint)
         events_ds, merges_ds, N_events_final = self.run_tracking(data_bin_preprocessed)
-        return self.run_stats_attributes(events_ds, merges_ds, object_stats, N_events_final)
+        events_ds = self.run_stats_attributes(events_ds, merges_ds, object_stats, N_events_final)
+        if return_merges and self.allow_merging:
+            return events_ds, merges_ds
+        return events_ds
 
     def run_preprocess(self, checkpoint: Optional[str] = None) -> Tuple[object, Tuple[float, int, int, float, float, float]]:
         """Fill holes, fill time gaps and remove small objects (track.py:1234-1368), on the device.  Returns the filtered
@@ -345,6 +473,8 @@ class tracker:  # noqa: N801 -- the reference's public name (marEx.tracker)
         coordinate gets its own name back when it differs from the time dimension."""
         from .xr_compat import DataArray, Dataset
 
+        if self.allow_merging:  # track.py:1388-1390
+            return self.track_objects(data_bin_preprocessed)
         ids, _, N_events_final = self.identify_objects(data_bin_preprocessed, time_connectivity=True)
         # IDs are >= 0 by construction (the reference's `where(ID_field > 0, other=0)` is a no-op here)
         da = DataArray(ids.values, dims=self._out_dims(), coords={self.timecoord: (self.timedim, self.time_values)},
@@ -366,6 +496,11 @@ class tracker:  # noqa: N801 -- the reference's public name (marEx.tracker)
         at["area_threshold (cells)"] = area_threshold
         at["accepted_area_fraction"] = accepted_area_fraction
         at["preprocessed_area_fraction"] = preprocessed_area_fraction
+        if self.allow_merging:  # track.py:1477-1484 (the attrs are set before the summary is printed here)
+            at["overlap_threshold"] = self.overlap_threshold
+            at["nn_partitioning"] = int(self.nn_partitioning)
+            at["total_merges"] = int(len(merges_ds["n_parents"].values))
+            at["multi_parent_merges"] = int((np.asarray(merges_ds["n_parents"].values) > 2).sum())
         print("Tracking Statistics:")
         print(f"   Binary Hobday to Processed Area Fraction: {preprocessed_area_fraction}")
         print(f"   Total Object Area IDed (cells): {total_area_IDed}")
@@ -374,6 +509,8 @@ class tracker:  # noqa: N801 -- the reference's public name (marEx.tracker)
         print(f"   Area Cutoff Threshold (cells): {int(area_threshold)}")
         print(f"   Accepted Area Fraction: {accepted_area_fraction}")
         print(f"   Total Events Tracked: {N_events_final}")
+        if self.allow_merging:
+            print(f"   Total Merging Events Recorded: {at['total_merges']}")
         at.update(self.data_attrs)
         return self._remap_coordinates(events_ds)
 
@@ -381,6 +518,8 @@ class tracker:  # noqa: N801 -- the reference's public name (marEx.tracker)
         """Re-assign the input's lat / lon coordinates (track.py:978-983)."""
         from .xr_compat import DataArray, Dataset
 
+        if "centroid" in events_ds.data_vars:
+            return self._remap_merge_coordinates(events_ds)
         v = events_ds["ID_field"]
         coords = {self.timecoord: (self.timedim, self.time_values),
                   self.ycoord: (_coord_dims(self.lat_init, (self.ydim,)), _host(self.lat_init)),
@@ -599,3 +738,410 @@ class tracker:  # noqa: N801 -- the reference's public name (marEx.tracker)
             logger.warning(f"Found {np.sum(overlap_fractions > 1.0)} overlap fractions > 1.0")
             logger.warning(f"Max overlap fraction: {overlap_fractions.max()}")
         return valid_overlaps[overlap_fractions >= self.overlap_threshold]
+
+    # ------------------------------------------------------------------ merge tracking on grids (track.py:2554-3802)
+    def _unify_coordinates(self) -> None:
+        """Coordinate units (track.py:919-976): ``coordinate_units`` is required in regional mode, else detected from the
+        longitude range (~360: degrees, ~2 pi: radians).  ``self.lat`` / ``self.lon`` hold the coordinates in degrees."""
+        units = self.coordinate_units
+        lon = _host(self.lon_init)
+        if self.regional_mode and units is None:
+            raise create_data_validation_error("coordinate_units must be specified when regional_mode=True",
+                                               suggestions=["Set coordinate_units='degrees' for degree-based coordinates",
+                                                            "Set coordinate_units='radians' for radian-based coordinates"])
+        if units is not None and units not in ("degrees", "radians"):
+            raise create_data_validation_error(f"Invalid coordinate_units '{units}'",
+                                               details="coordinate_units must be either 'degrees' or 'radians'")
+        if units is None:
+            rng = float(lon.max()) - float(lon.min())
+            if abs(rng - 360.0) <= 1.0:
+                units = "degrees"
+            elif abs(rng - 2 * np.pi) <= 0.02:
+                units = "radians"
+            else:
+                raise create_data_validation_error(
+                    f"Cannot auto-detect coordinate units from range {rng:.3f}",
+                    details=f"Expected ranges: ~360 degrees or ~{2 * np.pi:.3f} radians. Found range: {rng:.3f}",
+                    suggestions=["Use regional_mode=True with coordinate_units specified for regional data",
+                                 "Specify coordinate_units='degrees' or coordinate_units='radians' explicitly"])
+        self.coordinate_units = units
+        lat = _host(self.lat_init)
+        if units == "radians":
+            self.lon, self.lat = lon * 180.0 / np.pi, lat * 180.0 / np.pi
+        else:
+            self.lon, self.lat = lon, lat
+
+    def _merge_cell_weights(self, cell_areas, grid_resolution):
+        """float32 ``[ny, nx]`` cell areas of the final area / centroid pass (track.py:433-470), or None for unit areas
+        (cell counts, summed as integers)."""
+        d = self.data_bin
+        ny, nx = d.shape[self._perm[1]], d.shape[self._perm[2]]
+        if grid_resolution is not None:
+            if cell_areas is not None:
+                logger.warning("grid_resolution parameter overrides provided cell_areas for structured grid")
+            lat_r = np.radians(self.lat)
+            dl = np.radians(grid_resolution)
+            g = (6378.0 ** 2 * np.abs(np.sin(lat_r + dl / 2) - np.sin(lat_r - dl / 2)) * dl).astype(np.float32)
+            return np.ascontiguousarray(np.broadcast_to(g[:, None], (ny, nx)), dtype=np.float32)
+        if cell_areas is None:
+            return None
+        a = _host(cell_areas).astype(np.float32)
+        if a.ndim == 2 and tuple(getattr(cell_areas, "dims", ())) == (self.xdim, self.ydim):
+            a = a.T
+        return np.ascontiguousarray(np.broadcast_to(a if a.ndim == 2 else a[:, None], (ny, nx)), dtype=np.float32)
+
+    def _enforce(self, ov: np.ndarray, props: _Props) -> np.ndarray:
+        """enforce_overlap_threshold (track.py:2506-2552) against the live props."""
+        ov = np.asarray(ov)
+        if len(ov) == 0:
+            return np.empty((0, 3), dtype=np.int32)
+        ok = props.has(ov[:, 0]) & props.has(ov[:, 1])
+        if not ok.any():
+            return np.empty((0, 3), dtype=np.int32)
+        v = ov[ok]
+        frac = v[:, 2].astype(float) / np.minimum(props.area[v[:, 0]], props.area[v[:, 1]])
+        if np.any(frac > 1.0):
+            logger.warning(f"Found {np.sum(frac > 1.0)} overlap fractions > 1.0")
+            logger.warning(f"Max overlap fraction: {frac.max()}")
+        return v[frac >= self.overlap_threshold]
+
+    def _slice_props(self, eng, ids, t, nx):
+        r = eng.object_moments(ids[t:t + 1], ids.shape[1] // nx, nx, wrap=not self.regional_mode)
+        return r["id"], r["area"], r["centroid"]
+
+    def _consolidate(self, eng, ids, t: int, props: _Props, nx: int) -> None:
+        """consolidate_object_ids of slice t against t - 1 (track.py:2554-2656), in place.  Every rename of the reference's
+        loop is applied to a host table first (an ID renamed to a child that is renamed later follows it); the slice is
+        then relabelled once.  The props the reference recomputes after each parent equal those of the final slice for
+        the same IDs: after its last recomputation an ID's cells change only when it is renamed away, which drops it."""
+        bo = eng.overlap_pairs(ids[t - 1:t + 1])
+        if len(bo) == 0:
+            return
+        bo = self._enforce(bo, props)
+        if len(bo) == 0:
+            return
+        pids, pc = np.unique(bo[:, 0], return_counts=True)
+        members: Dict[int, List[int]] = {}
+        firsts = []
+        for p in pids[pc > 1].tolist():
+            if not props.has(p):
+                continue
+            ch = bo[bo[:, 0] == p, 1].astype(np.int64).tolist()
+            first = ch[0]
+            if not props.has(first):
+                continue
+            for c in ch[1:]:
+                if not props.has(c):
+                    continue
+                members.setdefault(first, [first]).extend(members.pop(c, [c]))
+                props.alive[c] = False
+            firsts.append(first)
+        pairs = sorted((o, lab) for lab, grp in members.items() for o in grp if o != lab)
+        if not pairs:
+            return
+        keys = np.array([o for o, _ in pairs], dtype=np.int32)
+        vals = np.array([lab for _, lab in pairs], dtype=np.int32)
+        eng.relabel(ids[t], vals, keys)
+        sid, sa, sc = self._slice_props(eng, ids, t, nx)
+        f = np.unique(np.asarray(firsts, dtype=np.int64))
+        f = f[props.has(f)]
+        pos = np.searchsorted(sid, f)
+        props.set(f, sa[pos], sc[0][pos], sc[1][pos])
+
+    def _merge_step(self, eng, ids, t: int, props: _Props, nx: int, state: dict) -> None:
+        """The merges at step t (track.py:3438-3600): up to 10 iterations of partitioning every child with several
+        parents at t - 1.
+
+        All merging children of one iteration are partitioned in ONE launch, which gives the reference's result because
+        (1) the parents' props at t - 1 do not change inside an iteration (only IDs at t are updated), (2) the child masks
+        are disjoint, so one child's relabelling never touches another's cells, (3) the new IDs are fresh, so no cell of
+        another child carries one, and (4) the props the reference writes after each child are those of the slice for
+        that child's IDs, which later children of the same iteration do not touch: they equal the props of the final
+        slice for those IDs."""
+        ny = ids.shape[1] // nx
+        wrap = not self.regional_mode
+        tv = self.time_values[t]
+        ov = self._enforce(eng.overlap_pairs(ids[t - 1:t + 1]), props)
+        it = 0
+        while it < 10:
+            if len(ov) == 0:
+                break
+            uc, cc = np.unique(ov[:, 1], return_counts=True)
+            merging = uc[cc > 1]
+            if merging.size == 0:
+                break
+            off, par, lab, maxd, news, children = [0], [], [], [], [], []
+            for child in merging.tolist():
+                rows = ov[:, 1] == child
+                parents = ov[rows, 0].astype(np.int64)
+                k = parents.size
+                nid = state["next_id"]
+                if nid + k - 2 > _I32_MAX:
+                    raise ProcessingError("new object IDs overflow int32", details=f"next ID {nid}, {k - 1} more needed")
+                new = np.arange(nid, nid + k - 1, dtype=np.int64)
+                state["next_id"] = nid + k - 1
+                cids = np.concatenate([[child], new]).astype(np.int32)
+                state["merges"].append((t, tv, parents.astype(np.int32), cids, ov[rows, 2].astype(np.int32)))
+                par.extend(parents.tolist())
+                lab.extend(cids.tolist())
+                off.append(len(par))
+                if self.nn_partitioning:
+                    md = max(int(np.sqrt(np.max(props.area[parents])) * 3.0), 40)
+                    maxd.extend([md] * k)
+                news.append(new)
+                children.append(child)
+            par = np.asarray(par, dtype=np.int64)
+            if self.nn_partitioning:
+                eng.partition_nn(ids[t], ids[t - 1], ny, nx, merging, off, par, props.cy[par], props.cx[par], lab, maxd, wrap)
+            else:
+                eng.partition_centroid(ids[t], ny, nx, merging, off, props.cy[par], props.cx[par], lab, wrap)
+            sid, sa, sc = self._slice_props(eng, ids, t, nx)
+            for child, new in zip(children, news):
+                j = np.searchsorted(sid, child)
+                if j < sid.size and sid[j] == child:
+                    props.set([child], sa[j], sc[0][j], sc[1][j])
+                else:
+                    props.alive[child] = False
+                    logger.info(f"Deleted child_id {child} because parents have split/morphed")
+                pos = np.minimum(np.searchsorted(sid, new), max(sid.size - 1, 0))
+                got = (sid[pos] == new) if sid.size else np.zeros(new.size, bool)
+                props.set(new[got], sa[pos[got]], sc[0][pos[got]], sc[1][pos[got]])
+                if not got.all():
+                    logger.warning(f"Missing newly created child_ids {set(new[~got].tolist())} "
+                                   "because parents have split/morphed in the meantime...")
+            ov = self._enforce(eng.overlap_pairs(ids[t - 1:t + 1]), props)
+            it += 1
+        if it == 10:
+            logger.warning(f"Resolving mergers at timestep {t} did not converge after 10 iterations")
+
+    def _split_and_merge(self, eng, ids, props: _Props, nx: int):
+        """split_and_merge_objects (track.py:3337-3802) on the device field ``ids`` int32 [T, C], in place: returns the
+        final overlap pairs (n, 2) and the merge records.  After the merges of step u, step u is consolidated against
+        u - 1 (at relative step u + 1 of its chunk, or by the end-of-chunk pass), except when u is alone in its chunk."""
+        T = ids.shape[0]
+        chunks = self._time_chunks or [T]
+        if sum(chunks) != T:
+            raise ConfigurationError("the time chunks do not cover the time axis", details=f"{chunks} for {T} steps")
+        state = {"next_id": props.max_id() + 1, "merges": []}
+        start = 0
+        for L in chunks:
+            for r in range(L):
+                t = start + r
+                if r > 0 and t >= 2:
+                    self._consolidate(eng, ids, t - 1, props, nx)
+                if t > 0:
+                    self._merge_step(eng, ids, t, props, nx, state)
+            if L >= 2:
+                self._consolidate(eng, ids, start + L - 1, props, nx)
+            start += L
+        ov = self._enforce(eng.overlap_pairs(ids), props)
+        if len(ov):
+            uc, cc = np.unique(ov[:, 1], return_counts=True)
+            if (cc > 1).any():
+                logger.warning(f"Tracker Warning: {int((cc > 1).sum())} children have multiple parents after splitting/merging")
+        return ov[:, :2], state["merges"]
+
+    def _merges_dataset(self, merges):
+        """merge_events of track.py:3758-3794."""
+        from .xr_compat import DataArray, Dataset
+
+        mp = max((len(m[2]) for m in merges), default=1)
+        mc = max((len(m[3]) for m in merges), default=1)
+        P = np.full((len(merges), mp), -1, np.int32)
+        Cc = np.full((len(merges), mc), -1, np.int32)
+        A = np.full((len(merges), mp), -1, np.int32)
+        for i, (_, _, p, c, a) in enumerate(merges):
+            P[i, :len(p)], Cc[i, :len(c)], A[i, :len(a)] = p, c, a
+        times = np.array([m[1] for m in merges], dtype=self.time_values.dtype) if merges else np.array([], dtype=np.float64)
+        ds = Dataset({"parent_IDs": DataArray(P, dims=("merge_ID", "parent_idx")),
+                      "child_IDs": DataArray(Cc, dims=("merge_ID", "child_idx")),
+                      "overlap_areas": DataArray(A, dims=("merge_ID", "parent_idx")),
+                      "merge_time": DataArray(times, dims=("merge_ID",)),
+                      "n_parents": DataArray(np.array([len(m[2]) for m in merges], np.int8), dims=("merge_ID",)),
+                      "n_children": DataArray(np.array([len(m[3]) for m in merges], np.int8), dims=("merge_ID",))},
+                     attrs={"fill_value": -1})
+        return ds
+
+    def _merge_time_index(self, merges_ds) -> np.ndarray:
+        """Timestep of every merge of ``merges_ds``: the position of its ``merge_time`` on the time axis."""
+        tpos = {v: i for i, v in enumerate(self.time_values.tolist())}
+        return np.array([tpos[v] for v in np.asarray(merges_ds["merge_time"].values).tolist()], dtype=np.int64)
+
+    def _cluster_rename(self, eng, ids, ny: int, nx: int, overlaps, merges_ds, merge_tidx):
+        """cluster_rename_objects_and_props (track.py:2809-3335), grids, with ``ids`` on the device (relabelled in place
+        to event IDs)."""
+        import torch
+
+        from .xr_compat import DataArray, Dataset
+
+        T = ids.shape[0]
+        sp = eng.id_spans(ids)
+        present = np.nonzero(sp[1] >= 0)[0] if sp is not None else np.zeros(0, np.int64)
+        present = present[present > 0]
+        ov = np.asarray(overlaps, dtype=np.int64).reshape(-1, 2)
+        valid = np.unique(np.concatenate([present, ov.reshape(-1)]))
+        valid = valid[valid > 0]
+        comp = _components(valid.size, np.searchsorted(valid, ov[:, 0]), np.searchsorted(valid, ov[:, 1]))
+        N = int(comp.max()) + 1 if comp.size else 0
+        lut = np.zeros(int(present[-1]) + 1 if present.size else 1, np.int32)
+        keep = valid < lut.size
+        lut[valid[keep]] = comp[keep] + 1
+        coords = {self.timecoord: (self.timedim, self.time_values), "ID": ("ID", np.arange(1, N + 1, dtype=np.int32))}
+        if N == 0:
+            mom = np.zeros((T, 0, 5), np.int64)
+            gid = np.zeros((T, 0), np.int32)
+            ev = ids
+        else:
+            orig = ids.clone()
+            eng.relabel(ids, lut)
+            ev = ids
+            w = None if self._cell_weights is None else torch.from_numpy(self._cell_weights.reshape(-1)).to(eng.device)
+            r = eng.event_moments(ev, orig, ny, nx, N, w)
+            mom, gid = r["mom"], r["gid"]
+            del orig
+        pres = gid > 0
+        t_first = np.argmax(pres, axis=0)
+        t_last = T - 1 - np.argmax(pres[::-1], axis=0)
+        cnt = mom[..., 0]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            if self._cell_weights is None:
+                tot = cnt.astype(np.float64)
+                sy, sx, sxs = mom[..., 1], mom[..., 2], mom[..., 3]
+                area = np.where(pres, cnt.astype(np.float32), np.float32(np.nan))
+            else:
+                wm = r["wmom"] if N else np.zeros((T, 0, 4))
+                tot = wm[..., 0].astype(np.float32).astype(np.float64)  # the reference's float32 np.sum of the cell areas
+                sy, sx, sxs = wm[..., 1], wm[..., 2], wm[..., 3]
+                area = np.where(pres, wm[..., 0].astype(np.float32), np.float32(np.nan))
+            cy = sy / tot
+            cx = sx / tot
+            if not self.regional_mode:
+                seam = (mom[..., 4] & 3) == 3
+                cxs = sxs / tot
+                cxs = np.where(cxs < 0, cxs + nx, cxs)
+                cx = np.where(seam, cxs, cx)
+        lat, lon = np.asarray(self.lat), np.asarray(self.lon)
+        cen = np.full((2, T, N), np.nan, np.float32)
+        cen[0][pres] = np.interp(cy[pres], np.arange(len(lat)), lat)
+        cen[1][pres] = np.interp(cx[pres], np.arange(len(lon)), lon)
+        P = np.asarray(merges_ds["parent_IDs"].values)
+        ledger = np.full((T, N + 1, P.shape[1]), -1, np.int32)
+        newP = lut[np.clip(np.where(P > 0, P, 0), 0, lut.size - 1)]
+        for row, t in zip(newP, np.asarray(merge_tidx).tolist()):
+            p = row[row > 0]
+            ledger[t, p, :] = p[:, None]  # the reference's broadcast: [t, P, :] = P (track.py:3106-3112)
+        tc = {self.timecoord: coords[self.timecoord]}
+        idc = {"ID": coords["ID"]}
+        tid = dict(tc, **idc)
+        data = {
+            "ID_field": DataArray(ev.cpu().numpy().reshape(T, ny, nx), dims=self._out_dims(), coords=tc),
+            "global_ID": DataArray(gid, dims=(self.timedim, "ID"), coords=tid),
+            "area": DataArray(area, dims=(self.timedim, "ID"), coords=tid),
+            "centroid": DataArray(cen, dims=("component", self.timedim, "ID"),
+                                  coords=dict(tid, component=("component", np.array([0, 1])))),
+            "presence": DataArray(pres, dims=(self.timedim, "ID"), coords=tid),
+            "time_start": DataArray(self.time_values[t_first], dims=("ID",), coords=idc),
+            "time_end": DataArray(self.time_values[t_last], dims=("ID",), coords=idc),
+            "merge_ledger": DataArray(ledger[:, 1:, :], dims=(self.timedim, "ID", "sibling_ID"), coords=tid),
+        }
+        return Dataset(data), N
+
+    def _remap_merge_coordinates(self, events_ds):
+        """_remap_coordinates (track.py:978-1021) of the merge tracker's Dataset: the input's lat / lon as coordinates and
+        the centroids from degrees into the input's units and longitude range."""
+        from .xr_compat import DataArray, Dataset
+
+        lon0 = _host(self.lon_init)
+        lo, hi = float(lon0.min()), float(lon0.max())
+        cen = np.asarray(events_ds["centroid"].values)
+        clat, clon = cen[0], cen[1]
+        if self.coordinate_units == "radians":
+            clat = clat * np.pi / 180.0
+            clon = clon * np.pi / 180.0
+            if lo >= 0 and hi > np.pi:
+                clon = np.where(clon < 0, clon + 2 * np.pi, clon)
+        elif lo >= 0 and hi > 180:
+            clon = np.where(clon < 0, clon + 360, clon)
+        cen = np.stack([clat, clon]).astype(np.float32)
+        extra = {self.ycoord: (_coord_dims(self.lat_init, (self.ydim,)), _host(self.lat_init)),
+                 self.xcoord: (_coord_dims(self.lon_init, (self.xdim,)), lon0)}
+        data = {}
+        for k, v in events_ds.data_vars.items():
+            c = {n: (tuple(cv.dims), np.asarray(cv.values)) for n, cv in v.coords.items()}
+            if k == "ID_field":
+                c.update(extra)
+            data[k] = DataArray(cen if k == "centroid" else v.values, dims=tuple(v.dims), coords=c, name=k)
+        out = Dataset(data)
+        out.attrs.update(events_ds.attrs)
+        return out
+
+    def track_objects(self, data_bin):
+        """Events with merging and splitting (track.py:2734-2807), gridded data, on the device: per-timestep objects,
+        their properties, split_and_merge_objects and cluster_rename_objects_and_props.  Returns ``(events_ds, merges_ds,
+        N_events)``."""
+        import time
+
+        eng = self._engine()
+        st = self._stage_times = {}
+        t0 = time.perf_counter()
+        x, T, ny, nx = self._device_u8(data_bin, eng)
+        r = eng.label_objects_3d(x, ny, nx, wrap_x=not self.regional_mode, connect_t=False)
+        ids = r["ids"].reshape(T, ny * nx)
+        del x, r
+        m = eng.object_moments(ids, ny, nx, wrap=not self.regional_mode)
+        props = _Props(m["id"], m["area"], m["centroid"][0], m["centroid"][1])
+        eng.sync()
+        st["objects"] = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        overlaps, merges = self._split_and_merge(eng, ids, props, nx)
+        merges_ds = self._merges_dataset(merges)
+        eng.sync()
+        st["split_and_merge"] = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        tidx = np.array([m[0] for m in merges], dtype=np.int64)
+        events_ds, N = self._cluster_rename(eng, ids, ny, nx, overlaps, merges_ds, tidx)
+        st["cluster_rename"] = time.perf_counter() - t0
+        return events_ds, merges_ds, N
+
+    # the reference's public stage methods (track.py:2554-2656, 2809-3335, 3337-3802)
+    def consolidate_object_ids(self, data_t_minus_2, data_t_minus_1, object_props, timestep: int):
+        """Rename the children at t - 1 of a parent at t - 2 that has several to the first of them (track.py:2554-2656).
+        Returns ``(data_t_minus_1, object_props)`` (a new DataArray and Dataset); runs on the device."""
+        import torch
+
+        from .xr_compat import DataArray
+
+        eng = self._engine()
+        a, _, ny, nx = self._device_ids(data_t_minus_2, eng)
+        b, _, _, _ = self._device_ids(data_t_minus_1, eng)
+        ids = torch.cat([a, b], dim=0).contiguous()
+        props = _Props.of(object_props)
+        self._consolidate(eng, ids, 1, props, nx)
+        out = DataArray(ids[1].cpu().numpy().reshape(ny, nx), dims=(self.ydim, self.xdim), name="ID_field")
+        return out, props.dataset()
+
+    def split_and_merge_objects(self, object_id_field_unique, object_props):
+        """split_and_merge_objects (track.py:3337-3802), gridded data, on the device: returns ``(object_id_field,
+        object_props, overlap_objects_list (n, 2), merge_events)``.  IDs must be unique across time."""
+        from .xr_compat import DataArray
+
+        eng = self._engine()
+        ids, T, ny, nx = self._device_ids(object_id_field_unique, eng)
+        ids = ids.clone()
+        props = _Props.of(object_props)
+        ov, merges = self._split_and_merge(eng, ids, props, nx)
+        field = DataArray(ids.cpu().numpy().reshape(T, ny, nx), dims=self._out_dims(),
+                          coords={self.timecoord: (self.timedim, self.time_values[:T])}, name="ID_field")
+        return field, props.dataset(), ov, self._merges_dataset(merges)
+
+    def cluster_rename_objects_and_props(self, object_id_field_unique, object_props, overlap_objects_list, merge_events):
+        """Events as connected components of the overlap pairs, numbered by their smallest ID, with global_ID, presence,
+        time_start / time_end, area, centroid (degrees, before _remap_coordinates) and merge_ledger
+        (track.py:2809-3335), on the device.  ``merge_events`` are the merge records of :meth:`split_and_merge_objects`; each
+        merge is placed on the time axis by its ``merge_time``."""
+        eng = self._engine()
+        ids, T, ny, nx = self._device_ids(object_id_field_unique, eng)
+        ids = ids.clone()
+        ds, _ = self._cluster_rename(eng, ids, ny, nx, overlap_objects_list, merge_events,
+                                     self._merge_time_index(merge_events))
+        return ds

@@ -39,6 +39,7 @@ class _MiniDataArray:
             raise ValueError(f"dims {self.dims} do not match data of rank {self.data.ndim}")
         self.name = name
         self.attrs: Dict[str, Any] = dict(attrs or {})
+        self.encoding: Dict[str, Any] = {}  # like xarray's: "chunks" = the store's chunk shape of a variable read from zarr
         self.coords: Dict[str, "_MiniDataArray"] = {}
         for k, v in (coords or {}).items():
             self.coords[k] = _as_coord(k, v, self.dims)

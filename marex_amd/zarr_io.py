@@ -295,6 +295,7 @@ class DeviceDataArray:
         self.coords = {k: (v if hasattr(v, "values") else _Coord(np.asarray(v))) for k, v in coords.items()}
         self.name = name
         self.attrs = dict(attrs or {})
+        self.encoding = {}  # like xarray's: "chunks" = the store's chunk shape (open_dataarray_device)
         self.shape = tuple(device_tensor.shape)
         self.dtype = np.dtype(str(device_tensor.dtype).replace("torch.", ""))
 
@@ -324,7 +325,9 @@ def open_dataarray_device(store: str, variable: str, eng, dims, time_var: str = 
     tm = decode_cf_time(read_array(tpath)[: x.shape[0]], array_attrs(tpath))
     c = {dims[0]: tm}
     c.update(coords or {})
-    return DeviceDataArray(x, dims, c, name=variable, attrs=array_attrs(os.path.join(store, variable)))
+    da = DeviceDataArray(x, dims, c, name=variable, attrs=array_attrs(os.path.join(store, variable)))
+    da.encoding["chunks"] = tuple(json.load(open(os.path.join(store, variable, ".zarray")))["chunks"])
+    return da
 
 
 # ------------------------------------------------------------------------------------------------
@@ -582,16 +585,22 @@ def read_dataset(store: str):
             v = decode_cf_time(v, at)
             at.pop("units", None)
             at.pop("calendar", None)
-        if json.load(open(os.path.join(p, ".zarray")))["dtype"] == "|b1":
+        za = json.load(open(os.path.join(p, ".zarray")))
+        if za["dtype"] == "|b1":
             v = v.astype(bool)
-        arrays[n] = (dims, v, at)
+        arrays[n] = (dims, v, at, tuple(za["chunks"]))
     aux = set()
-    for dims, v, at in arrays.values():
+    for dims, v, at, _ in arrays.values():
         aux.update(str(at.pop("coordinates", "")).split())
-    coords = {n: _MiniDataArray(v, d, None, n, at) for n, (d, v, at) in arrays.items() if d == (n,) or n in aux}
+    coords = {n: _MiniDataArray(v, d, None, n, at) for n, (d, v, at, _) in arrays.items() if d == (n,) or n in aux}
     gattrs = array_attrs(store)
     ds = _MiniDataset(None, coords, gattrs)
-    for n, (d, v, at) in arrays.items():
+    for n, (d, v, at, ch) in arrays.items():
         if n not in coords:
-            ds[n] = _MiniDataArray(v, d, {c: coords[c] for c in coords if set(coords[c].dims) <= set(d)}, n, at)
+            da = _MiniDataArray(v, d, {c: coords[c] for c in coords if set(coords[c].dims) <= set(d)}, n, at)
+            da.encoding["chunks"] = ch
+            ds[n] = da
+    for n, (_, _, _, ch) in arrays.items():
+        if n in coords:
+            coords[n].encoding["chunks"] = ch
     return ds
