@@ -2,6 +2,7 @@
 """Benchmark of the preprocess_data hot path on MI355X.
 
     python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full   (also the untimed extras and the CPU baseline, see below)
     python bench.py --gpus N --steps K --warmup W          (plain command: starts its own N ranks, one per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
@@ -16,6 +17,12 @@ scaling).  Bands are ingested with ws//2 overlap rows per interior side (marex_a
 are a broadcast of the host-built tables (calendar, bin edges / centres, detrend model) from rank 0 before the
 timed region and an all-reduce of a few int64 scalars per step.  A rank with several bands runs them round-robin
 over `--streams` engines with a HIP stream each (marex_amd.dist.EngineSet, default 3 when the workspaces fit): the product schedule.
+
+A plain run sets up, warms up, times the steps, writes `--dump-outputs` and prints the line: `kernel_ms` and `roofline` come
+from the timed steps' own HIP events.  `--full` (one GPU) adds, after the timed region, the figures that take runs of their
+own: a single-stream pass of the same step (`extra.single_stream`: undisturbed per-kernel durations, which `roofline` then
+quotes, and its `n_extreme`, which must equal the timed steps'), the seasonally drifting field (`extra.seasonal_field`), the
+NumPy oracle on the host cores (`cpu_baseline`) and the dominant kernel's HBM traffic from the committed PMC passes.
 
 Prints ONE JSON line on rank 0.
 """
@@ -302,7 +309,9 @@ def spawn_ranks(n: int, argv) -> int:
     return rc
 
 
-def main():
+def parse_args(argv=None):
+    """The command line.  A plain run (no `--full`) does only what the headline line needs -- set up, warm up, time the steps,
+    write `--dump-outputs`, print -- so it implies `--no-extra --no-cpu-baseline`."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
@@ -312,17 +321,29 @@ def main():
     ap.add_argument("--streams", type=int, default=int(os.environ.get("MAREX_BENCH_STREAMS", "0")),
                     help="engines (HIP streams) the bands of a rank alternate between; 0 = default (3 when their workspaces fit beside "
                          "the resident field, else 2; 1 for a single band / the one-GPU rehearsal)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the untimed extra measurements (single-stream pass, seasonally drifting thresholds)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run what the headline figure does not need: the single-stream pass (per-kernel "
+                         "durations, the dominant kernel's roofline, its n_extreme checked against the timed steps'), the seasonally "
+                         "drifting field and the CPU baseline, and quote the committed HBM traffic of the dominant kernel")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true",
+                    help="with --full: skip the untimed extra measurements (single-stream pass, seasonally drifting thresholds)")
     ap.add_argument("--hobday-path", default=None, choices=["tails", "bins"],
                     help="force the representation of the dayofyear histograms (default: the engine's own choice)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one returned (the last band's arrays over its owned cells -- "
                          "ocean cells only where land is NaN --, the summary counts) as DIR/<name>.npy, at most 64 MB in all; with "
                          "several ranks each writes <name>.rank<r>.npy")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if not args.full:
+        args.no_extra = args.no_cpu_baseline = True
+    return args
+
+
+def main():
+    args = parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -528,7 +549,7 @@ def main():
                             f"step ({serial['n_extreme']})")
         per_launch = serial["kernel_ms"] if serial and serial.get("kernel_ms") else None
         dom = max(per_launch, key=per_launch.get) if per_launch else max(kern, key=lambda k: kern[k][0])
-        # HBM bytes of the dominant kernel from the committed PMC passes of this same command (profiles/)
+        # --full: HBM bytes of the dominant kernel from the committed PMC passes of this same command (profiles/)
         traffic = None
         lean = (path == "tails" and detrend is None and step_kw["S"] == 21 and step_kw["W"] in (5, 15) and shard.cells_in % 4 == 0
                 and os.environ.get("MAREX_SHIFT_LEAN", "1") != "0")  # engine.shifting_baseline_tails -> k_shift_lean (csrc/marex_shifting.hip)
@@ -538,7 +559,7 @@ def main():
         kname = knames[dom]
         for rnd in ("r04", "r03", "r02"):
             tfile = os.path.join(ROOT, "profiles", f"{rnd}_{args.workload}_traffic.json")
-            if world == 1 and traffic is None and os.path.exists(tfile):
+            if args.full and world == 1 and traffic is None and os.path.exists(tfile):
                 for name, rec in json.load(open(tfile)).get("kernels", {}).items():
                     if name.startswith(kname):
                         traffic = rec["hbm_bytes"]

@@ -1,6 +1,6 @@
-"""CPU: the committed bench lines under profiles/ keep the contract of the task statement (one JSON object with the metric of
-BASELINE.json, `roofline` and `cpu_baseline` objects), their numbers are consistent with each other, and the band tiling
-`bench.py` picks per rank count divides the field in whole rows of threshold tiles."""
+"""CPU: the committed bench lines under profiles/ (full runs) keep the contract of the task statement (one JSON object with the
+metric of BASELINE.json, `roofline` and `cpu_baseline` objects), their numbers are consistent with each other, the band tiling
+`bench.py` picks per rank count divides the field in whole rows of threshold tiles, and a plain run leaves the extras to `--full`."""
 import importlib.util
 import json
 import os
@@ -128,6 +128,18 @@ def test_dump_outputs_fit_their_budget_and_repeat(tmp_path):
     s = load("a", "big")
     assert s.dtype == np.float32 and s.ndim == 1 and 0.9 * budget / 4 < s.size < budget / 4 and np.isfinite(s).all()
     assert np.array_equal(s, load("b", "big")) and np.isin(s, big[:, cells].numpy()).all()
+
+
+def test_a_plain_run_leaves_the_untimed_extras_to_full():
+    """A plain command does only what its headline line needs; `--full` adds the single-stream pass, the seasonal field and the
+    CPU baseline, of which `--no-extra` / `--no-cpu-baseline` still leave parts out."""
+    b = _bench_module()
+    plain = b.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert not plain.full and plain.no_extra and plain.no_cpu_baseline
+    full = b.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1", "--full"])
+    assert full.full and not full.no_extra and not full.no_cpu_baseline
+    part = b.parse_args(["--full", "--no-cpu-baseline"])
+    assert not part.no_extra and part.no_cpu_baseline
 
 
 def test_steps_must_be_at_least_one():
