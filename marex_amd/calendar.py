@@ -76,6 +76,11 @@ class CalendarPlan:
         return int(self.doy_rows.shape[0])
 
     @property
+    def max_bucket(self) -> int:
+        """Rows of the largest dayofyear bucket of ``doy_rows``."""
+        return int(np.diff(self.doy_start).max())
+
+    @property
     def year_idx(self) -> np.ndarray:
         return (self.year - self.min_year).astype(np.int32)
 

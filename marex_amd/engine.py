@@ -51,6 +51,20 @@ def _key_to_float(key: int) -> float:
     return float(np.array([bits], dtype=np.uint32).view(np.float32)[0])
 
 
+def _linear_percentile(values: torch.Tensor, q: float) -> float:
+    """``np.percentile(values, 100 q)`` ("linear") of a non-empty 1-D device tensor: two order statistics from a device
+    sort, then NumPy's own lerp on the host -- from the lower value below g = 0.5, from the upper one above: that is what
+    makes the result equal NumPy's to the bit."""
+    n = int(values.numel())
+    srt = torch.sort(values).values
+    virt = (n - 1) * float(np.float64(q * 100.0) / 100.0)
+    lo = int(np.floor(virt))
+    g = virt - lo
+    hi = min(lo + 1, n - 1)
+    a, b = float(srt[lo].item()), float(srt[hi].item())
+    return a + (b - a) * g if g < 0.5 else b - (b - a) * (1.0 - g)
+
+
 @dataclass
 class DeviceCalendar:
     """Calendar tables resident on the device."""
@@ -108,6 +122,23 @@ class HotPath:
     def _bind_stream(self) -> None:
         self.ctx.set_stream(torch.cuda.current_stream(self.device).cuda_stream)
 
+    def call(self, name: str, *args) -> None:
+        """The one way to a context-taking ``marex_*`` function: launches on torch's current stream of this device,
+        passes the context handle first and every tensor as its address (``None`` is NULL), and raises
+        :class:`ProcessingError` naming ``name`` when the library returns an error code.  A tensor has to be contiguous and
+        on this engine's device -- anything else would hand the kernel a valid-looking address of the wrong bytes -- and is
+        refused before the library is reached; ``argument k`` counts as in include/marex_hip.h with the context as 0."""
+        self._bind_stream()
+        argv = []
+        for k, a in enumerate(args, 1):
+            if isinstance(a, torch.Tensor):
+                if a.device != self.device or not a.is_contiguous():
+                    raise ProcessingError(f"{name}: argument {k} must be a contiguous tensor on {self.device}",
+                                          details=f"got {a.dtype} {tuple(a.shape)} with strides {a.stride()} on {a.device}")
+                a = a.data_ptr()
+            argv.append(a)
+        self.ctx.check(getattr(self.lib, name)(self.ctx.handle, *argv), name)
+
     def _dev(self, a: np.ndarray, dtype=None) -> torch.Tensor:
         t = torch.from_numpy(np.ascontiguousarray(a if dtype is None else a.astype(dtype)))
         return t.to(self.device, non_blocking=False)
@@ -154,7 +185,6 @@ class HotPath:
     # ------------------------------------------------------------------ synthetic field
     def synth_field(self, tab, cell_base: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Device evaluation of :func:`marex_amd.synth.synth_field` (bit-identical)."""
-        self._bind_stream()
         T, Cn = tab.T, tab.C
         if out is None:
             out = torch.empty((T, Cn), dtype=torch.float32, device=self.device)
@@ -162,12 +192,34 @@ class HotPath:
             self._dev(tab.mean, np.float32), self._dev(tab.amp, np.float32), self._dev(tab.hemi, np.uint8),
             self._dev(tab.land, np.uint8), self._dev(tab.seas, np.float32), self._dev(tab.trend, np.float32),
         ]
-        rc = self.lib.marex_synth_sst_f32(
-            self.ctx.handle, *[b.data_ptr() for b in bufs], tab.seed, int(cell_base), T, Cn, out.data_ptr()
-        )
-        self.ctx.check(rc, "marex_synth_sst_f32")
+        self.call("marex_synth_sst_f32", *bufs, tab.seed, int(cell_base), T, Cn, out)
         self.sync()  # the small tables above must outlive the kernel
         return out
+
+    # ------------------------------------------------------------------ what the anomaly kernels share
+    @staticmethod
+    def _check_shifting_input(x: torch.Tensor, cal: CalendarPlan) -> None:
+        assert x.dtype == torch.float32 and x.dim() == 2
+        if cal.T != x.shape[0]:
+            raise ProcessingError("calendar length does not match the time axis of x")
+        if cal.has_duplicates:
+            raise ConfigurationError(
+                "shifting_baseline needs at most one timestep per (year, dayofyear)",
+                details="sub-daily time axes are not supported by the device path",
+            )
+
+    def _anomaly_buffers(self, wsp: Optional[dict], name: str, T_out: int, Cn: int, second_stage: bool = False):
+        """``(out [T_out, Cn] float32 named name, mask [Cn] uint8, invalid [Cn] int32)`` of an anomaly kernel."""
+        out = self._buf(wsp, name, (T_out, Cn), torch.float32, self.device)
+        mask = self._buf(wsp, "mask2" if second_stage else "mask", (Cn,), torch.uint8, self.device)
+        invalid = self._buf(wsp, "invalid2" if second_stage else "invalid", (Cn,), torch.int32, self.device)
+        return out, mask, invalid
+
+    def _reference_rows(self, cal: CalendarPlan, reference_period) -> Optional[torch.Tensor]:
+        """uint8 ``[T]``: 1 for the timesteps of the years ``reference_period = (first, last)``; None without a period."""
+        if reference_period is None:
+            return None
+        return self._dev(((cal.year >= reference_period[0]) & (cal.year <= reference_period[1])).astype(np.uint8))
 
     # ------------------------------------------------------------------ stage a3+a5+a6+a7 (+a10 binning)
     def shifting_baseline(
@@ -180,37 +232,20 @@ class HotPath:
         write_clim: bool = False,
         wsp: Optional[dict] = None,
     ) -> Dict[str, torch.Tensor]:
-        self._bind_stream()
-        assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 2
-        T, Cn = x.shape
         cal = dcal.plan
-        if cal.T != T:
-            raise ProcessingError("calendar length does not match the time axis of x")
-        if cal.has_duplicates:
-            raise ConfigurationError(
-                "shifting_baseline needs at most one timestep per (year, dayofyear)",
-                details="sub-daily time axes are not supported by the device path",
-            )
+        self._check_shifting_input(x, cal)
+        T, Cn = x.shape
         T_out = cal.T_out
-        out = self._buf(wsp, "anom", (T_out, Cn), torch.float32, self.device)
+        out, mask, invalid = self._anomaly_buffers(wsp, "anom", T_out, Cn)
         if write_clim:
             out.fill_(float("nan"))
-        mask = self._buf(wsp, "mask", (Cn,), torch.uint8, self.device)
-        invalid = self._buf(wsp, "invalid", (Cn,), torch.int32, self.device)
         invalid.zero_()
+        edges = binsb = None
         if bins is not None and not write_clim:
             edges = self.bin_tables(bins)[0]
             binsb = self._buf(wsp, "bins", self.bins_shape(T_out, Cn), torch.int16, self.device)
-            e_ptr, b_ptr, nb = edges.data_ptr(), binsb.data_ptr(), bins.nb
-        else:
-            edges = binsb = None
-            e_ptr, b_ptr, nb = None, None, 0
-        rc = self.lib.marex_shifting_baseline_f32(
-            self.ctx.handle, x.data_ptr(), T, Cn, dcal.year_plan.data_ptr(), cal.n_cal_years,
-            int(W), int(S), int(write_clim),
-            e_ptr, nb, T_out, out.data_ptr(), b_ptr, mask.data_ptr(), invalid.data_ptr(),
-        )
-        self.ctx.check(rc, "marex_shifting_baseline_f32")
+        self.call("marex_shifting_baseline_f32", x, T, Cn, dcal.year_plan, cal.n_cal_years, int(W), int(S), int(write_clim),
+                  edges, bins.nb if edges is not None else 0, T_out, out, binsb, mask, invalid)
         res = {"out": out, "mask": mask, "invalid_count": invalid, "_keep": edges}
         if binsb is not None:
             res["bins"] = binsb
@@ -232,21 +267,22 @@ class HotPath:
         wsp: Optional[dict] = None,
     ) -> Dict[str, object]:
         """``rows=(row0, row1)`` restricts the output to the grid rows a latitude shard owns."""
-        self._bind_stream()
         T_out, Cn = binsb.shape[1], first_anom.shape[-1]
         row0, row1 = rows if rows is not None else (0, max(ny, 1))
+        thr, stats = self._threshold_buffers(wsp, Cn)
+        centres = self.bin_tables(bins)[1]
+        self.call("marex_hobday_thresholds_f32", binsb, T_out, Cn, int(ny), int(nx), dcal.doy_start, dcal.plan.max_bucket,
+                  first_anom, centres, bins.nb, float(q), int(wd), int(ws), float(bins.lower_bound), float(bins.upper_bound),
+                  int(row0), int(row1), thr, stats)
+        return {"thr_doy_major": thr, "stats_dev": stats, "_keep": centres}
+
+    def _threshold_buffers(self, wsp: Optional[dict], Cn: int):
+        """``(thr_doy_major [366, Cn] float32, thr_stats)`` of the dayofyear threshold kernels, the statistics reset."""
         thr = self._buf(wsp, "thr_doy_major", (N_DOY, Cn), torch.float32, self.device)
         stats = self._buf(wsp, "thr_stats", (8,), torch.int32, self.device)  # marex_thr_stats: 8 x uint32
         stats.zero_()
         stats[0:1].fill_(-1)  # min_key = 0xFFFFFFFF (a fill kernel: `stats[0] = -1` would be a blocking host-to-device copy)
-        centres = self.bin_tables(bins)[1]
-        rc = self.lib.marex_hobday_thresholds_f32(
-            self.ctx.handle, binsb.data_ptr(), T_out, Cn, int(ny), int(nx), dcal.doy_start.data_ptr(),
-            int(np.diff(dcal.plan.doy_start).max()), first_anom.data_ptr(), centres.data_ptr(), bins.nb, float(q), int(wd), int(ws),
-            float(bins.lower_bound), float(bins.upper_bound), int(row0), int(row1), thr.data_ptr(), stats.data_ptr(),
-        )
-        self.ctx.check(rc, "marex_hobday_thresholds_f32")
-        return {"thr_doy_major": thr, "stats_dev": stats, "_keep": centres}
+        return thr, stats
 
     @staticmethod
     def decode_thr_stats(stats_dev: torch.Tensor) -> Dict[str, float]:
@@ -275,7 +311,7 @@ class HotPath:
         kernels).  Results are identical on both paths (include/marex_hip.h, TAILS)."""
         if self.hobday_path == "bins":
             return None
-        nd = int(np.diff(dcal.plan.doy_start).max())
+        nd = dcal.plan.max_bucket
         if not (bins.nb <= 511 and 1 <= nd <= 128 and ws <= 7 and nd * wd * ws * ws <= 65535 and (C is None or C <= (1 << 24))):
             return None
         if self.hobday_path != "tails" and nd < 24 and ws > 1:
@@ -290,102 +326,76 @@ class HotPath:
         -- the 48-row register kernel keeps four waves per SIMD with the sorting networks in it; the 128-row one drops to two and
         measured SLOWER than kernel + extraction pass on the 100-yr field (27.9 vs 21.0 ms per band, profiles/r04_experiments.md)
         --, 2 = whenever possible, 0 = never (the extraction pass makes the lists)."""
-        nd = int(np.diff(dcal.plan.doy_start).max())
+        nd = dcal.plan.max_bucket
         mode = self.ctx_opt("FIXED_TAILS", 1)
         return bool(mode) and bool(self.ctx_opt("FIXED_REG", 1)) and 1 <= nd <= (128 if mode == 2 else 48) and bins.nb <= 511
 
-    def _tail_buffers(self, nd: int, list_rows: int, Cn: int, wsp: Optional[dict]):
+    def _tail_buffers(self, nd: int, list_rows: int, Cn: int, edges: torch.Tensor, wsp: Optional[dict]) -> Dict[str, object]:
+        """The tail-list record the threshold / mask kernels take, its lists still to be written (``edges``: the table the
+        keys are made with, kept alive with the record)."""
         nper = (nd + list_rows - 1) // list_rows
         nch = 2 if list_rows <= 16 else 4
         lists = self._buf(wsp, "tails", (N_DOY, nper, nch, Cn, 8), torch.int16, self.device)
         aux = self._buf(wsp, "tails_aux", (N_DOY, Cn), torch.int32, self.device)
-        return lists, aux
+        return {"tails": lists, "aux": aux, "max_bucket": nd, "list_rows": list_rows, "_keep": edges}
 
     def tail_extract(self, anom: torch.Tensor, dcal: DeviceCalendar, bins: BinTable, wsp: Optional[dict] = None,
                      list_rows: Optional[int] = None):
         """Sorted key lists of every (dayofyear, cell) bucket of ``anom`` (include/marex_hip.h, TAILS)."""
-        self._bind_stream()
         T_out, Cn = anom.shape
         edges = self.bin_tables(bins)[0]
-        nd = int(np.diff(dcal.plan.doy_start).max())
-        list_rows = int(list_rows or self.LIST_ROWS_EXTRACT)
-        lists, aux = self._tail_buffers(nd, list_rows, Cn, wsp)
-        rc = self.lib.marex_tail_extract_f32(
-            self.ctx.handle, anom.data_ptr(), T_out, Cn, dcal.doy_start.data_ptr(), dcal.doy_rows.data_ptr(), nd,
-            edges.data_ptr(), bins.nb, list_rows, lists.data_ptr(), aux.data_ptr(),
-        )
-        self.ctx.check(rc, "marex_tail_extract_f32")
-        return {"tails": lists, "aux": aux, "max_bucket": nd, "list_rows": list_rows, "_keep": edges}
+        nd = dcal.plan.max_bucket
+        tl = self._tail_buffers(nd, int(list_rows or self.LIST_ROWS_EXTRACT), Cn, edges, wsp)
+        self.call("marex_tail_extract_f32", anom, T_out, Cn, dcal.doy_start, dcal.doy_rows, nd, edges, bins.nb,
+                  tl["list_rows"], tl["tails"], tl["aux"])
+        return tl
 
     def shifting_tails_ok(self, dcal: DeviceCalendar) -> bool:
         """The anomaly kernel emits its own tails for buckets of at most 6 lists of 15 rows (option SHIFT_TAILS=0: never)."""
-        nd = int(np.diff(dcal.plan.doy_start).max())
-        return bool(self.ctx_opt("SHIFT_TAILS", 1)) and nd <= 6 * self.LIST_ROWS_SHIFT
+        return bool(self.ctx_opt("SHIFT_TAILS", 1)) and dcal.plan.max_bucket <= 6 * self.LIST_ROWS_SHIFT
 
     def shifting_baseline_tails(self, x: torch.Tensor, dcal: DeviceCalendar, W: int, S: int, bins: BinTable,
                                 wsp: Optional[dict] = None) -> Dict[str, object]:
         """Anomaly stage emitting the sorted key lists (TAILS) of its own output: no bin matrix, no extraction pass."""
-        self._bind_stream()
-        assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 2
-        T, Cn = x.shape
         cal = dcal.plan
-        if cal.T != T:
-            raise ProcessingError("calendar length does not match the time axis of x")
-        if cal.has_duplicates:
-            raise ConfigurationError(
-                "shifting_baseline needs at most one timestep per (year, dayofyear)",
-                details="sub-daily time axes are not supported by the device path",
-            )
+        self._check_shifting_input(x, cal)
+        T, Cn = x.shape
         T_out = cal.T_out
-        out = self._buf(wsp, "anom", (T_out, Cn), torch.float32, self.device)
-        mask = self._buf(wsp, "mask", (Cn,), torch.uint8, self.device)
-        invalid = self._buf(wsp, "invalid", (Cn,), torch.int32, self.device)
+        out, mask, invalid = self._anomaly_buffers(wsp, "anom", T_out, Cn)
         invalid.zero_()
         edges = self.bin_tables(bins)[0]
-        nd = int(np.diff(cal.doy_start).max())
-        lists, aux = self._tail_buffers(nd, self.LIST_ROWS_SHIFT, Cn, wsp)
-        rc = self.lib.marex_shifting_baseline_tails_f32(
-            self.ctx.handle, x.data_ptr(), T, Cn, dcal.year_plan.data_ptr(), cal.n_cal_years, int(W), int(S), edges.data_ptr(),
-            bins.nb, T_out, out.data_ptr(), mask.data_ptr(), invalid.data_ptr(), dcal.doy_start.data_ptr(),
-            dcal.doy_rows.data_ptr(), nd, lists.data_ptr(), aux.data_ptr(),
-        )
-        self.ctx.check(rc, "marex_shifting_baseline_tails_f32")
-        return {"out": out, "mask": mask, "invalid_count": invalid, "_keep": edges,
-                "tails": {"tails": lists, "aux": aux, "max_bucket": nd, "list_rows": self.LIST_ROWS_SHIFT, "_keep": edges}}
+        nd = cal.max_bucket
+        tl = self._tail_buffers(nd, self.LIST_ROWS_SHIFT, Cn, edges, wsp)
+        self.call("marex_shifting_baseline_tails_f32", x, T, Cn, dcal.year_plan, cal.n_cal_years, int(W), int(S), edges,
+                  bins.nb, T_out, out, mask, invalid, dcal.doy_start, dcal.doy_rows, nd, tl["tails"], tl["aux"])
+        return {"out": out, "mask": mask, "invalid_count": invalid, "_keep": edges, "tails": tl}
 
     def hobday_thresholds_tails(self, tl: dict, anom: torch.Tensor, dcal: DeviceCalendar, bins: BinTable, q: float, wd: int,
                                 ws: int, ny: int, nx: int, rows: Optional[tuple] = None, wsp: Optional[dict] = None):
-        self._bind_stream()
         T_out, Cn = anom.shape
         row0, row1 = rows if rows is not None else (0, max(ny, 1))
-        thr = self._buf(wsp, "thr_doy_major", (N_DOY, Cn), torch.float32, self.device)
-        stats = self._buf(wsp, "thr_stats", (8,), torch.int32, self.device)  # marex_thr_stats: 8 x uint32
-        stats.zero_()
-        stats[0:1].fill_(-1)
+        thr, stats = self._threshold_buffers(wsp, Cn)
         centres = self.bin_tables(bins)[1]
-        rc = self.lib.marex_hobday_thresholds_tails_f32(
-            self.ctx.handle, tl["tails"].data_ptr(), tl["aux"].data_ptr(), int(tl["list_rows"]), anom.data_ptr(), T_out, Cn,
-            int(ny), int(nx), int(tl["max_bucket"]), centres.data_ptr(), bins.nb, float(q), int(wd), int(ws),
-            float(bins.lower_bound), float(bins.upper_bound), int(row0), int(row1), thr.data_ptr(), stats.data_ptr(),
-        )
-        self.ctx.check(rc, "marex_hobday_thresholds_tails_f32")
+        self.call("marex_hobday_thresholds_tails_f32", tl["tails"], tl["aux"], int(tl["list_rows"]), anom, T_out, Cn,
+                  int(ny), int(nx), int(tl["max_bucket"]), centres, bins.nb, float(q), int(wd), int(ws),
+                  float(bins.lower_bound), float(bins.upper_bound), int(row0), int(row1), thr, stats)
         return {"thr_doy_major": thr, "stats_dev": stats, "_keep": centres}
 
-    def mask_ge_doy_tails(self, tl: dict, anom: torch.Tensor, thr_doy_major: torch.Tensor, dcal: DeviceCalendar,
-                          bins: BinTable, cells: Optional[tuple] = None, wsp: Optional[dict] = None):
-        self._bind_stream()
-        T_out, Cn = anom.shape
-        c0, c1 = cells if cells is not None else (0, Cn)
+    def _extreme_buffers(self, wsp: Optional[dict], T_out: int, Cn: int):
+        """``(extreme [T_out, Cn] uint8, n_true [1] int64 = 0)`` of the compare kernels."""
         ext = self._buf(wsp, "extreme", (T_out, Cn), torch.uint8, self.device)
         n_true = self._buf(wsp, "n_true", (1,), torch.int64, self.device)
         n_true.zero_()
+        return ext, n_true
+
+    def mask_ge_doy_tails(self, tl: dict, anom: torch.Tensor, thr_doy_major: torch.Tensor, dcal: DeviceCalendar,
+                          bins: BinTable, cells: Optional[tuple] = None, wsp: Optional[dict] = None):
+        T_out, Cn = anom.shape
+        c0, c1 = cells if cells is not None else (0, Cn)
+        ext, n_true = self._extreme_buffers(wsp, T_out, Cn)
         edges = self.bin_tables(bins)[0]
-        rc = self.lib.marex_mask_ge_doy_tails_f32(
-            self.ctx.handle, tl["tails"].data_ptr(), tl["aux"].data_ptr(), int(tl["list_rows"]), int(tl["max_bucket"]),
-            anom.data_ptr(), edges.data_ptr(), bins.nb, thr_doy_major.data_ptr(), dcal.doy_start.data_ptr(),
-            dcal.doy_rows.data_ptr(), T_out, Cn, int(c0), int(c1), ext.data_ptr(), n_true.data_ptr(),
-        )
-        self.ctx.check(rc, "marex_mask_ge_doy_tails_f32")
+        self.call("marex_mask_ge_doy_tails_f32", tl["tails"], tl["aux"], int(tl["list_rows"]), int(tl["max_bucket"]),
+                  anom, edges, bins.nb, thr_doy_major, dcal.doy_start, dcal.doy_rows, T_out, Cn, int(c0), int(c1), ext, n_true)
         return {"extreme": ext, "n_true": n_true}
 
     def hobday_approx(self, anom: torch.Tensor, dcal: DeviceCalendar, bins: BinTable, q: float, wd: int, ws: int, ny: int,
@@ -413,13 +423,10 @@ class HotPath:
                            wsp: Optional[dict] = None) -> torch.Tensor:
         """Device int64 ``[n_ocean, invalid_total, invalid_cells, max_invalid]`` over the (owned) cells: the numbers of
         ``_validate_data_values`` (detect.py:205-279) from the per-cell outputs of the anomaly kernels, one launch."""
-        self._bind_stream()
         Cn = mask.shape[-1]
         c0, c1 = cells if cells is not None else (0, Cn)
         out = self._buf(wsp, "validation_summary", (4,), torch.int64, self.device)
-        rc = self.lib.marex_validation_summary(self.ctx.handle, mask.data_ptr(), invalid_count.data_ptr(), int(c0), int(c1),
-                                               out.data_ptr())
-        self.ctx.check(rc, "marex_validation_summary")
+        self.call("marex_validation_summary", mask, invalid_count, int(c0), int(c1), out)
         return out
 
     # ------------------------------------------------------------------ stage a9 compare
@@ -429,33 +436,22 @@ class HotPath:
     ) -> Dict[str, torch.Tensor]:
         """``cells=(c0, c1)`` restricts compare / write / count to the owned cells of a shard.  ``binned=(bin matrix,
         BinTable)`` of these anomalies lets the kernel decide most samples from their 2-byte bin (same result)."""
-        self._bind_stream()
         T_out, Cn = anom.shape
         c0, c1 = cells if cells is not None else (0, Cn)
-        ext = self._buf(wsp, "extreme", (T_out, Cn), torch.uint8, self.device)
-        n_true = self._buf(wsp, "n_true", (1,), torch.int64, self.device)
-        n_true.zero_()
+        ext, n_true = self._extreme_buffers(wsp, T_out, Cn)
         if binned is not None and binned[0] is not None:
             edges = self.bin_tables(binned[1])[0]
-            rc = self.lib.marex_mask_ge_doy_bins_f32(
-                self.ctx.handle, anom.data_ptr(), binned[0].data_ptr(), edges.data_ptr(), int(binned[1].nb),
-                thr_doy_major.data_ptr(), dcal.doy_start.data_ptr(), dcal.doy_rows.data_ptr(), T_out, Cn, int(c0), int(c1),
-                ext.data_ptr(), n_true.data_ptr(),
-            )
-            self.ctx.check(rc, "marex_mask_ge_doy_bins_f32")
+            self.call("marex_mask_ge_doy_bins_f32", anom, binned[0], edges, int(binned[1].nb), thr_doy_major, dcal.doy_start,
+                      dcal.doy_rows, T_out, Cn, int(c0), int(c1), ext, n_true)
         else:
-            rc = self.lib.marex_mask_ge_doy_f32(
-                self.ctx.handle, anom.data_ptr(), thr_doy_major.data_ptr(), dcal.doy_start.data_ptr(),
-                dcal.doy_rows.data_ptr(), T_out, Cn, int(c0), int(c1), ext.data_ptr(), n_true.data_ptr(),
-            )
-            self.ctx.check(rc, "marex_mask_ge_doy_f32")
+            self.call("marex_mask_ge_doy_f32", anom, thr_doy_major, dcal.doy_start, dcal.doy_rows, T_out, Cn, int(c0), int(c1),
+                      ext, n_true)
         return {"extreme": ext, "n_true": n_true}
 
     def transpose(self, a: torch.Tensor, wsp: Optional[dict] = None, name: str = "transposed") -> torch.Tensor:
-        self._bind_stream()
         rows, cols = a.shape
         out = self._buf(wsp, name, (cols, rows), torch.float32, self.device)
-        self.ctx.check(self.lib.marex_transpose_f32(self.ctx.handle, a.data_ptr(), rows, cols, out.data_ptr()), "marex_transpose_f32")
+        self.call("marex_transpose_f32", a, rows, cols, out)
         return out
 
     # ------------------------------------------------------------------ whole path (shifting + hobday approx)
@@ -488,8 +484,7 @@ class HotPath:
                        f"'{fam}' anomaly kernel (tuned path: smooth_days_baseline=21, window_year_baseline in (5, 15), cells a "
                        "multiple of 4; same results)")
         if K is None:
-            nd = int(np.diff(dcal.plan.doy_start).max())
-            _note_path(f"hobday_extreme: dayofyear buckets of {nd} rows with window_spatial_hobday={ws}, q={q} take the bin-matrix "
+            _note_path(f"hobday_extreme: dayofyear buckets of {dcal.plan.max_bucket} rows with window_spatial_hobday={ws}, q={q} take the bin-matrix "
                        "threshold kernels (sorted key lists need >= 24 rows per bucket or no spatial pooling; same results)")
         if K is not None and self.shifting_tails_ok(dcal):
             a = self.shifting_baseline_tails(x, dcal, W, S, bins, wsp=workspace)
@@ -532,65 +527,40 @@ class HotPath:
         names of their own, so that the first stage's validation outputs (the RAW field's) survive.
         ``tails_bins``: also leave the sorted key lists of the output (``"tails"``, 32 rows per list: what
         :meth:`tail_extract` would make of it) when the register kernel takes the shape -- see :meth:`fused_tails_ok`."""
-        self._bind_stream()
         T, Cn = x.shape
         cal = dcal.plan
         assert cal.T == T and cal.T_out == T, "fixed_baseline needs an untrimmed calendar"
-        use = None
-        if reference_period is not None:
-            use = self._dev(((cal.year >= reference_period[0]) & (cal.year <= reference_period[1])).astype(np.uint8))
-        out = self._buf(wsp, "anom", (T, Cn), torch.float32, self.device)
-        mask = self._buf(wsp, "mask2" if second_stage else "mask", (Cn,), torch.uint8, self.device)
-        invalid = self._buf(wsp, "invalid2" if second_stage else "invalid", (Cn,), torch.int32, self.device)
-        invalid.zero_()
-        if tails_bins is not None and bins is None and self.fused_tails_ok(dcal, tails_bins):
-            if sub is not None:
-                assert sub.dtype == torch.float32 and sub.numel() == Cn
-            edges = self.bin_tables(tails_bins)[0]
-            nd = int(np.diff(cal.doy_start).max())
-            lists, aux = self._tail_buffers(nd, self.LIST_ROWS_EXTRACT, Cn, wsp)
-            rc = self.lib.marex_fixed_baseline_tails_f32(
-                self.ctx.handle, x.data_ptr(), sub.data_ptr() if sub is not None else None, nd, T, Cn, dcal.doy_start.data_ptr(),
-                dcal.doy_rows.data_ptr(), use.data_ptr() if use is not None else None, edges.data_ptr(), tails_bins.nb,
-                out.data_ptr(), mask.data_ptr(), invalid.data_ptr() if count_invalid else None, lists.data_ptr(), aux.data_ptr(),
-            )
-            self.ctx.check(rc, "marex_fixed_baseline_tails_f32")
-            if use is not None:
-                self.sync()
-            return {"out": out, "mask": mask, "invalid_count": invalid,
-                    "tails": {"tails": lists, "aux": aux, "max_bucket": nd, "list_rows": self.LIST_ROWS_EXTRACT, "_keep": edges}}
-        if bins is not None:
-            edges = self.bin_tables(bins)[0]
-            binsb = self._buf(wsp, "bins", self.bins_shape(T, Cn), torch.int16, self.device)
-            e_ptr, b_ptr, nb = edges.data_ptr(), binsb.data_ptr(), bins.nb
-        else:
-            binsb, e_ptr, b_ptr, nb = None, None, None, 0
-        tail = (T, Cn, dcal.doy_start.data_ptr(), dcal.doy_rows.data_ptr(), use.data_ptr() if use is not None else None, e_ptr, nb,
-                out.data_ptr(), b_ptr, mask.data_ptr(), invalid.data_ptr() if count_invalid else None)
         if sub is not None:
             assert sub.dtype == torch.float32 and sub.numel() == Cn
-        nd = int(np.diff(cal.doy_start).max())
-        rc = self.lib.marex_fixed_baseline_sub_f32(self.ctx.handle, x.data_ptr(), sub.data_ptr() if sub is not None else None, nd, *tail)
-        self.ctx.check(rc, "marex_fixed_baseline_f32")
+        use = self._reference_rows(cal, reference_period)
+        out, mask, invalid = self._anomaly_buffers(wsp, "anom", T, Cn, second_stage)
+        invalid.zero_()
+        counts = invalid if count_invalid else None
+        nd = cal.max_bucket
+        res = {"out": out, "mask": mask, "invalid_count": invalid}
+        if tails_bins is not None and bins is None and self.fused_tails_ok(dcal, tails_bins):
+            edges = self.bin_tables(tails_bins)[0]
+            tl = res["tails"] = self._tail_buffers(nd, self.LIST_ROWS_EXTRACT, Cn, edges, wsp)
+            self.call("marex_fixed_baseline_tails_f32", x, sub, nd, T, Cn, dcal.doy_start, dcal.doy_rows, use, edges,
+                      tails_bins.nb, out, mask, counts, tl["tails"], tl["aux"])
+        else:
+            edges = binsb = None
+            if bins is not None:
+                edges = self.bin_tables(bins)[0]
+                binsb = res["bins"] = self._buf(wsp, "bins", self.bins_shape(T, Cn), torch.int16, self.device)
+            self.call("marex_fixed_baseline_sub_f32", x, sub, nd, T, Cn, dcal.doy_start, dcal.doy_rows, use, edges,
+                      bins.nb if bins is not None else 0, out, binsb, mask, counts)
         if use is not None:
             self.sync()  # the small table must outlive the kernel
-        res = {"out": out, "mask": mask, "invalid_count": invalid}
-        if binsb is not None:
-            res["bins"] = binsb
         return res
 
     # ------------------------------------------------------------------ stage a10 binning on its own
     def digitize(self, anom: torch.Tensor, dcal: DeviceCalendar, bins: BinTable, wsp: Optional[dict] = None) -> torch.Tensor:
         """Dayofyear-sorted bin matrix of an anomaly field (rows with ``rowb_index < 0`` are skipped)."""
-        self._bind_stream()
         T, Cn = anom.shape
         edges = self.bin_tables(bins)[0]
         binsb = self._buf(wsp, "bins", self.bins_shape(dcal.plan.T_out, Cn), torch.int16, self.device)
-        rc = self.lib.marex_digitize_f32(
-            self.ctx.handle, anom.data_ptr(), T, Cn, dcal.rowb_index.data_ptr(), edges.data_ptr(), bins.nb,
-            dcal.plan.T_out, binsb.data_ptr(),
-        )
-        self.ctx.check(rc, "marex_digitize_f32")
+        self.call("marex_digitize_f32", anom, T, Cn, dcal.rowb_index, edges, bins.nb, dcal.plan.T_out, binsb)
         return binsb
 
     # ------------------------------------------------------------------ stage a12 (detrend)
@@ -608,27 +578,17 @@ class HotPath:
         """Residual of the least-squares fit of ``model`` (detect.py:2143-2224); optional binning of the result.
         ``defer_mean`` (with ``force_zero_mean``): ``out`` keeps its mean and ``res["mean"]`` ``[C]`` is the value still to be
         subtracted -- :meth:`fixed_baseline` takes it as ``sub`` and saves a pass over the field."""
-        self._bind_stream()
         T, Cn = x.shape
         n_coef = int(model.shape[0])
         pm = self._dev(np.ascontiguousarray(pmodel, dtype=np.float64))
         mt = self._dev(np.ascontiguousarray(model.T, dtype=np.float64))
-        out = self._buf(wsp, "detrended", (T, Cn), torch.float32, self.device)
-        mask = self._buf(wsp, "mask", (Cn,), torch.uint8, self.device)
-        invalid = self._buf(wsp, "invalid", (Cn,), torch.int32, self.device)
+        out, mask, invalid = self._anomaly_buffers(wsp, "detrended", T, Cn)
         mean = None
         if defer_mean and force_zero_mean:
             mean = self._buf(wsp, "detrend_mean", (Cn,), torch.float32, self.device)
-            rc = self.lib.marex_detrend_deferred_mean_f32(
-                self.ctx.handle, x.data_ptr(), T, Cn, pm.data_ptr(), mt.data_ptr(), n_coef, out.data_ptr(), mean.data_ptr(),
-                mask.data_ptr(), invalid.data_ptr(),
-            )
+            self.call("marex_detrend_deferred_mean_f32", x, T, Cn, pm, mt, n_coef, out, mean, mask, invalid)
         else:
-            rc = self.lib.marex_detrend_f32(
-                self.ctx.handle, x.data_ptr(), T, Cn, pm.data_ptr(), mt.data_ptr(), n_coef, int(bool(force_zero_mean)),
-                out.data_ptr(), mask.data_ptr(), invalid.data_ptr(),
-            )
-        self.ctx.check(rc, "marex_detrend_f32")
+            self.call("marex_detrend_f32", x, T, Cn, pm, mt, n_coef, int(bool(force_zero_mean)), out, mask, invalid)
         self.sync()  # pm / mt must outlive the kernel
         res = {"out": out, "mask": mask, "invalid_count": invalid}
         if mean is not None:
@@ -646,7 +606,7 @@ class HotPath:
         T, Cn = x.shape
         cal = dcal.plan
         n_coef = int(model.shape[0])
-        nd = int(np.diff(cal.doy_start).max())
+        nd = cal.max_bucket
         if n_coef > 5 or nd > 128 or not self.ctx_opt("DETREND_FUSED", 1):
             d = self.detrend(x, model, pmodel, bool(force_zero_mean), None, count_invalid=True, wsp=wsp, defer_mean=True)
             r = self.fixed_baseline(d["out"], dcal, reference_period, None, count_invalid=False, wsp=wsp, sub=d.get("mean"),
@@ -655,36 +615,22 @@ class HotPath:
             if "tails" in r:
                 res["tails"] = r["tails"]
             return res
-        self._bind_stream()
-        assert x.dtype == torch.float32 and x.is_contiguous() and cal.T == T and cal.T_out == T
+        assert x.dtype == torch.float32 and cal.T == T and cal.T_out == T
         pm = self._dev(np.ascontiguousarray(pmodel, dtype=np.float64))
         mt_host = np.ascontiguousarray(model.T, dtype=np.float64)
         mt = self._dev(mt_host)
         mts = self._dev(np.ascontiguousarray(mt_host[cal.doy_rows]))  # model rows in dayofyear-sorted row order
-        use = None
-        if reference_period is not None:
-            use = self._dev(((cal.year >= reference_period[0]) & (cal.year <= reference_period[1])).astype(np.uint8))
-        out = self._buf(wsp, "anom", (T, Cn), torch.float32, self.device)
-        mask = self._buf(wsp, "mask", (Cn,), torch.uint8, self.device)
-        invalid = self._buf(wsp, "invalid", (Cn,), torch.int32, self.device)
+        use = self._reference_rows(cal, reference_period)
+        out, mask, invalid = self._anomaly_buffers(wsp, "anom", T, Cn)
         res = {"out": out, "mask": mask, "invalid_count": invalid}
+        fit = (x, T, Cn, pm, mt, mts, n_coef, int(bool(force_zero_mean)), dcal.doy_start, dcal.doy_rows, use, nd)
         if tails_bins is not None and self.fused_tails_ok(dcal, tails_bins):
             edges = self.bin_tables(tails_bins)[0]
-            lists, aux = self._tail_buffers(nd, self.LIST_ROWS_EXTRACT, Cn, wsp)
-            rc = self.lib.marex_detrend_fixed_baseline_tails_f32(
-                self.ctx.handle, x.data_ptr(), T, Cn, pm.data_ptr(), mt.data_ptr(), mts.data_ptr(), n_coef, int(bool(force_zero_mean)),
-                dcal.doy_start.data_ptr(), dcal.doy_rows.data_ptr(), use.data_ptr() if use is not None else None, nd,
-                edges.data_ptr(), tails_bins.nb, out.data_ptr(), mask.data_ptr(), invalid.data_ptr(), lists.data_ptr(), aux.data_ptr(),
-            )
-            self.ctx.check(rc, "marex_detrend_fixed_baseline_tails_f32")
-            res["tails"] = {"tails": lists, "aux": aux, "max_bucket": nd, "list_rows": self.LIST_ROWS_EXTRACT, "_keep": edges}
+            tl = res["tails"] = self._tail_buffers(nd, self.LIST_ROWS_EXTRACT, Cn, edges, wsp)
+            self.call("marex_detrend_fixed_baseline_tails_f32", *fit, edges, tails_bins.nb, out, mask, invalid,
+                      tl["tails"], tl["aux"])
         else:
-            rc = self.lib.marex_detrend_fixed_baseline_f32(
-                self.ctx.handle, x.data_ptr(), T, Cn, pm.data_ptr(), mt.data_ptr(), mts.data_ptr(), n_coef, int(bool(force_zero_mean)),
-                dcal.doy_start.data_ptr(), dcal.doy_rows.data_ptr(), use.data_ptr() if use is not None else None, nd,
-                out.data_ptr(), mask.data_ptr(), invalid.data_ptr(),
-            )
-            self.ctx.check(rc, "marex_detrend_fixed_baseline_f32")
+            self.call("marex_detrend_fixed_baseline_f32", *fit, out, mask, invalid)
         self.sync()  # pm / mt / use must outlive the kernels
         return res
 
@@ -693,21 +639,12 @@ class HotPath:
                       wsp: Optional[dict] = None) -> Dict[str, torch.Tensor]:
         """``dat_stn`` and ``STD`` of the std_normalise branch (detect.py:2257-2278): day-of-year standard deviation,
         wrapped ``window``-day rolling RMS of it, anomaly / STD.  ``STD`` is returned dayofyear-major ``[366, C]``."""
-        self._bind_stream()
         T, Cn = anom.shape
         std_day = self._buf(wsp, "std_day", (N_DOY, Cn), torch.float32, self.device)
         std_roll = self._buf(wsp, "std_roll", (N_DOY, Cn), torch.float32, self.device)
         out = self._buf(wsp, "dat_stn", (T, Cn), torch.float32, self.device)
-        rc = self.lib.marex_std_rolling_doy_f32(
-            self.ctx.handle, anom.data_ptr(), T, Cn, dcal.doy_start.data_ptr(), dcal.doy_rows.data_ptr(), int(window),
-            std_day.data_ptr(), std_roll.data_ptr(),
-        )
-        self.ctx.check(rc, "marex_std_rolling_doy_f32")
-        rc = self.lib.marex_div_doy_f32(
-            self.ctx.handle, anom.data_ptr(), std_roll.data_ptr(), dcal.doy_start.data_ptr(), dcal.doy_rows.data_ptr(),
-            T, Cn, out.data_ptr(),
-        )
-        self.ctx.check(rc, "marex_div_doy_f32")
+        self.call("marex_std_rolling_doy_f32", anom, T, Cn, dcal.doy_start, dcal.doy_rows, int(window), std_day, std_roll)
+        self.call("marex_div_doy_f32", anom, std_roll, dcal.doy_start, dcal.doy_rows, T, Cn, out)
         return {"dat_stn": out, "STD": std_roll}
 
     # ------------------------------------------------------------------ tracker pre-processing (SURVEY 8f rank 3)
@@ -715,13 +652,17 @@ class HotPath:
                    regional_mode: bool = False, wsp: Optional[dict] = None, name: str = "filled") -> torch.Tensor:
         """Binary closing + opening with a disk of radius ``R_fill`` per timestep, land masked (track.py:1520-1676).
         ``data_bin``: uint8 ``[T, ny*nx]`` (0/1), ``mask``: uint8 ``[ny*nx]``."""
-        self._bind_stream()
         T, Cn = data_bin.shape
         assert Cn == ny * nx
         out = self._buf(wsp, name, (T, Cn), torch.uint8, self.device)
-        rc = self.lib.marex_fill_holes_u8(self.ctx.handle, data_bin.data_ptr(), mask.data_ptr(), T, int(ny), int(nx),
-                                          int(R_fill), int(bool(regional_mode)), out.data_ptr())
-        self.ctx.check(rc, "marex_fill_holes_u8")
+        self.call("marex_fill_holes_u8", data_bin, mask, T, int(ny), int(nx), int(R_fill), int(bool(regional_mode)), out)
+        return out
+
+    def time_closing(self, x: torch.Tensor, T_fill: int, wsp: Optional[dict] = None) -> torch.Tensor:
+        """Binary closing of uint8 ``[T, C]`` along time over ``T_fill + 1`` steps (first half of track.py:1678-1726), grid or mesh alike."""
+        T, Cn = x.shape
+        out = self._buf(wsp, "time_closed", (T, Cn), torch.uint8, self.device)
+        self.call("marex_time_closing_u8", x, T, Cn, int(T_fill), out)
         return out
 
     def fill_time_gaps(self, data_bin: torch.Tensor, mask: torch.Tensor, ny: int, nx: int, R_fill: int, T_fill: int,
@@ -729,24 +670,17 @@ class HotPath:
         """Temporal closing over ``T_fill + 1`` steps, then ``fill_holes(R_fill // 2)`` (track.py:1678-1726)."""
         if T_fill == 0:
             return data_bin
-        self._bind_stream()
-        T, Cn = data_bin.shape
-        tmp = self._buf(wsp, "time_closed", (T, Cn), torch.uint8, self.device)
-        rc = self.lib.marex_time_closing_u8(self.ctx.handle, data_bin.data_ptr(), T, Cn, int(T_fill), tmp.data_ptr())
-        self.ctx.check(rc, "marex_time_closing_u8")
+        tmp = self.time_closing(data_bin, T_fill, wsp=wsp)
         return self.fill_holes(tmp, mask, ny, nx, int(R_fill) // 2, regional_mode, wsp=wsp, name="gap_filled")
 
     def label_objects_2d(self, data_bin: torch.Tensor, ny: int, nx: int, wrap_x: bool = True,
                          wsp: Optional[dict] = None) -> Dict[str, torch.Tensor]:
         """Per-timestep 8-connected components (track.py:2013-2031): ``labels`` int32 ``[T, C]`` (1 + smallest linear
         index of the component, 0 = background) and ``areas`` int32 ``[T, C]`` (cell count, stored at the root cell)."""
-        self._bind_stream()
         T, Cn = data_bin.shape
         labels = self._buf(wsp, "labels", (T, Cn), torch.int32, self.device)
         areas = self._buf(wsp, "areas", (T, Cn), torch.int32, self.device)
-        rc = self.lib.marex_label2d_i32(self.ctx.handle, data_bin.data_ptr(), T, int(ny), int(nx), int(bool(wrap_x)),
-                                        labels.data_ptr(), areas.data_ptr())
-        self.ctx.check(rc, "marex_label2d_i32")
+        self.call("marex_label2d_i32", data_bin, T, int(ny), int(nx), int(bool(wrap_x)), labels, areas)
         return {"labels": labels, "areas": areas}
 
     def label_objects_3d(self, data_bin: torch.Tensor, ny: int, nx: int, wrap_x: bool = True, connect_t: bool = True,
@@ -754,24 +688,19 @@ class HotPath:
         """26-connected components in (time, y, x) (track.py:2006-2048, ``time_connectivity=True``; ``connect_t=False``:
         one labelling per timestep).  ``ids`` int32 ``[T, C]``: IDs 1..N numbered by the component's first cell in C order,
         0 = background; ``areas`` int32 (cells of ID ``k`` at ``k - 1``, the first N entries); ``n`` int32 ``[1]`` = N."""
-        self._bind_stream()
         T, Cn = data_bin.shape
         assert Cn == ny * nx
         ids = self._buf(wsp, "ids3d", (T, Cn), torch.int32, self.device)
         areas = self._buf(wsp, "areas3d", (T * Cn,), torch.int32, self.device)
         n = self._buf(wsp, "n3d", (1,), torch.int32, self.device)
-        rc = self.lib.marex_label3d_i32(self.ctx.handle, data_bin.data_ptr(), T, int(ny), int(nx), int(bool(wrap_x)),
-                                        int(bool(connect_t)), ids.data_ptr(), areas.data_ptr(), n.data_ptr())
-        self.ctx.check(rc, "marex_label3d_i32")
+        self.call("marex_label3d_i32", data_bin, T, int(ny), int(nx), int(bool(wrap_x)), int(bool(connect_t)), ids, areas, n)
         return {"ids": ids, "areas": areas, "n": n}
 
     # ------------------------------------------------------------------ object properties and overlaps (track.py:2109-2504)
     def ids_minmax(self, ids: torch.Tensor) -> tuple:
         """``(min, max)`` of an int32 ID field (synchronises)."""
-        self._bind_stream()
         mm = self._buf(None, "ids_minmax", (2,), torch.int32, self.device)
-        self.ctx.check(self.lib.marex_ids_minmax_i32(self.ctx.handle, ids.data_ptr(), ids.numel(), mm.data_ptr()),
-                       "marex_ids_minmax_i32")
+        self.call("marex_ids_minmax_i32", ids, ids.numel(), mm)
         lo, hi = (int(v) for v in mm.cpu().numpy())
         if lo < 0:
             from .exceptions import create_data_validation_error
@@ -793,13 +722,27 @@ class HotPath:
                                   details=f"got {ids.dtype} {tuple(ids.shape)} on {ids.device}")
         return tuple(int(k) for k in ids.shape)
 
+    def _object_spans(self, ids: torch.Tensor, T: int, Cn: int, hi: int, what: str, details: str):
+        """Per ID 0..hi of ``ids`` on the device: ``tmin`` / ``tmax`` int32 (first / last timestep, INT_MAX / -1 when
+        absent), ``off`` int64 (first (timestep, ID) slot of the ID when every ID gets one per step of its span) and
+        ``total`` int64 ``[1]`` (all slots).  ``what`` / ``details`` word the error when the tables do not fit."""
+        nid = hi + 1
+        ntiles = (nid + 4095) // 4096
+        self._check_fits(16 * nid + 16 * ntiles, what, details)
+        tmin = self._buf(None, "obj_tmin", (nid,), torch.int32, self.device)
+        tmax = self._buf(None, "obj_tmax", (nid,), torch.int32, self.device)
+        off = self._buf(None, "obj_off", (nid,), torch.int64, self.device)
+        work = self._buf(None, "obj_work", (2 * ntiles,), torch.int64, self.device)
+        total = self._buf(None, "obj_total", (1,), torch.int64, self.device)
+        self.call("marex_object_spans_i32", ids, T, Cn, hi, tmin, tmax, off, work, total)
+        return tmin, tmax, off, total
+
     def object_moments(self, ids: torch.Tensor, ny: int, nx: int, wrap: bool = True) -> Dict[str, np.ndarray]:
         """Area and centroid of every ID in every timestep of ``ids`` int32 ``[T, ny * nx]`` (values <= 0: background):
         ``t``, ``id`` (int64), ``area`` (float64 cells) and ``centroid`` (float64 ``[2, n]``: mean row, mean column), rows in
         (t, id) order.  With ``wrap`` the column mean of an object with cells in both the first and the last 100 columns
         is taken with the columns x > nx // 2 shifted by -nx, and nx is added when that mean is negative
         (calculate_centroid, track.py:2050-2107).  The device accumulates integer sums; the division is NumPy's float64."""
-        self._bind_stream()
         T, Cn = self._ids_check(ids)
         if Cn != ny * nx:
             raise ProcessingError(f"object_moments: {Cn} cells per slice, ny * nx = {ny * nx}")
@@ -808,32 +751,18 @@ class HotPath:
                "centroid": np.zeros((2, 0), np.float64)}
         if hi <= 0:
             return out
-        nid = hi + 1
-        ntiles = (nid + 4095) // 4096
-        self._check_fits(16 * nid + 16 * ntiles, "object properties",
-                         f"per-ID first / last timestep and slot offsets for IDs 0..{hi}; renumber sparse IDs densely")
-        tmin = self._buf(None, "obj_tmin", (nid,), torch.int32, self.device)
-        tmax = self._buf(None, "obj_tmax", (nid,), torch.int32, self.device)
-        off = self._buf(None, "obj_off", (nid,), torch.int64, self.device)
-        work = self._buf(None, "obj_work", (2 * ntiles,), torch.int64, self.device)
-        total = self._buf(None, "obj_total", (1,), torch.int64, self.device)
-        rc = self.lib.marex_object_spans_i32(self.ctx.handle, ids.data_ptr(), T, Cn, hi, tmin.data_ptr(), tmax.data_ptr(),
-                                             off.data_ptr(), work.data_ptr(), total.data_ptr())
-        self.ctx.check(rc, "marex_object_spans_i32")
+        tmin, _, off, total = self._object_spans(
+            ids, T, Cn, hi, "object properties",
+            f"per-ID first / last timestep and slot offsets for IDs 0..{hi}; renumber sparse IDs densely")
         n_slots = int(total.item())
-        del work
         self._check_fits(88 * n_slots, "object properties",
                          f"{n_slots} (timestep, ID) slots between each ID's first and last timestep, 88 bytes each")
         acc = self._buf(None, "obj_acc", (n_slots, 5), torch.int64, self.device)
-        rc = self.lib.marex_object_moments_i32(self.ctx.handle, ids.data_ptr(), T, int(ny), int(nx), tmin.data_ptr(),
-                                               off.data_ptr(), n_slots, acc.data_ptr())
-        self.ctx.check(rc, "marex_object_moments_i32")
+        self.call("marex_object_moments_i32", ids, T, int(ny), int(nx), tmin, off, n_slots, acc)
         n_out = self._buf(None, "obj_n", (1,), torch.int64, self.device)
         tid = self._buf(None, "obj_tid", (n_slots, 2), torch.int32, self.device)
         mom = self._buf(None, "obj_mom", (n_slots, 5), torch.int64, self.device)
-        rc = self.lib.marex_object_compact(self.ctx.handle, n_slots, hi, tmin.data_ptr(), off.data_ptr(), acc.data_ptr(),
-                                           n_out.data_ptr(), tid.data_ptr(), mom.data_ptr())
-        self.ctx.check(rc, "marex_object_compact")
+        self.call("marex_object_compact", n_slots, hi, tmin, off, acc, n_out, tid, mom)
         n = int(n_out.item())
         if not 0 < n <= n_slots:
             raise ProcessingError(f"object_moments: {n} non-empty slots of {n_slots} (internal sizing error)")
@@ -853,15 +782,13 @@ class HotPath:
     def overlap_pairs(self, ids: torch.Tensor) -> np.ndarray:
         """``(n, 3)`` int32 ``[id at t, id at t + 1, cells]`` over every t < T - 1 of ``ids`` int32 ``[T, C]``, summed over
         time and sorted lexicographically (check_overlap_slice / find_overlapping_objects, track.py:2396-2504)."""
-        self._bind_stream()
         T, Cn = self._ids_check(ids)
         _, hi = self.ids_minmax(ids)
         empty = np.zeros((0, 3), np.int32)
         if T < 2 or hi <= 0:
             return empty
         stats = self._buf(None, "ovl_stats", (4,), torch.int64, self.device)
-        self.ctx.check(self.lib.marex_overlap_count_i32(self.ctx.handle, ids.data_ptr(), T, Cn, stats.data_ptr()),
-                       "marex_overlap_count_i32")
+        self.call("marex_overlap_count_i32", ids, T, Cn, stats)
         runs = int(stats[1].item())
         if runs == 0:
             return empty
@@ -871,9 +798,7 @@ class HotPath:
         counts = self._buf(None, "ovl_counts", (cap,), torch.int64, self.device)
         out_k = self._buf(None, "ovl_out_keys", (runs,), torch.int64, self.device)
         out_c = self._buf(None, "ovl_out_counts", (runs,), torch.int64, self.device)
-        rc = self.lib.marex_overlap_pairs_i32(self.ctx.handle, ids.data_ptr(), T, Cn, cap, keys.data_ptr(), counts.data_ptr(),
-                                              stats.data_ptr(), runs, out_k.data_ptr(), out_c.data_ptr())
-        self.ctx.check(rc, "marex_overlap_pairs_i32")
+        self.call("marex_overlap_pairs_i32", ids, T, Cn, cap, keys, counts, stats, runs, out_k, out_c)
         s = stats.cpu().numpy()
         n = int(s[3])
         if s[2] != 0 or not 0 < n <= runs:
@@ -894,27 +819,19 @@ class HotPath:
     def relabel(self, ids: torch.Tensor, vals: np.ndarray, keys: Optional[np.ndarray] = None) -> None:
         """In place: ``ids`` (contiguous int32 on the device) -> ``vals[j]`` where ``keys[j]`` equals the ID (``keys``
         ascending; IDs without an entry stay), or with ``keys=None`` -> ``vals[id]`` for ``0 < id < len(vals)``."""
-        self._bind_stream()
         if ids.dtype != torch.int32 or not ids.is_contiguous() or ids.device != self.device:
             raise ProcessingError("relabel: ids must be a contiguous int32 tensor on the engine's device")
         if ids.numel() == 0 or len(vals) == 0:
             return
-        v = self._i32(vals)
-        k = self._i32(keys) if keys is not None else None
-        rc = self.lib.marex_relabel_i32(self.ctx.handle, ids.data_ptr(), ids.numel(), k.data_ptr() if k is not None else None,
-                                        v.data_ptr(), len(vals))
-        self.ctx.check(rc, "marex_relabel_i32")
+        self.call("marex_relabel_i32", ids, ids.numel(), self._i32(keys) if keys is not None else None, self._i32(vals),
+                  len(vals))
 
     def partition_centroid(self, cur: torch.Tensor, ny: int, nx: int, child_keys, off, pcy, pcx, lab, wrap: bool) -> None:
         """In place on the slice ``cur`` (int32 ``ny * nx``): every cell of child ``child_keys[k]`` takes ``lab[j]`` of the
         nearest parent centroid ``(pcy[j], pcx[j])``, ``off[k] <= j < off[k + 1]`` (first minimum)."""
-        self._bind_stream()
-        t = [self._i32(child_keys), self._i32(off), self._dev(np.asarray(pcy, np.float64)),
-             self._dev(np.asarray(pcx, np.float64)), self._i32(lab)]
-        rc = self.lib.marex_partition_centroid_i32(self.ctx.handle, cur.data_ptr(), int(ny), int(nx), t[0].data_ptr(),
-                                                   len(child_keys), t[1].data_ptr(), t[2].data_ptr(), t[3].data_ptr(),
-                                                   t[4].data_ptr(), int(bool(wrap)))
-        self.ctx.check(rc, "marex_partition_centroid_i32")
+        self.call("marex_partition_centroid_i32", cur, int(ny), int(nx), self._i32(child_keys), len(child_keys), self._i32(off),
+                  self._dev(np.asarray(pcy, np.float64)), self._dev(np.asarray(pcx, np.float64)), self._i32(lab),
+                  int(bool(wrap)))
 
     def partition_nn(self, cur: torch.Tensor, prev: torch.Tensor, ny: int, nx: int, child_keys, off, parents, pcy, pcx, lab,
                      maxd, wrap: bool) -> None:
@@ -922,7 +839,6 @@ class HotPath:
         ``parents[j]`` (``off[k] <= j < off[k + 1]``) with the nearest cell in ``prev`` among its cells in the 3 x 3
         buckets of size ``max(2, maxd[j] // 4)`` around the child cell's bucket and within ``maxd[j]``, else of the
         nearest parent centroid (partition_nn_grid, track.py:4972-5113)."""
-        self._bind_stream()
         parents = np.asarray(parents, np.int64)
         maxd = np.asarray(maxd, np.int64)
         gs = np.maximum(2, maxd // 4)
@@ -939,42 +855,24 @@ class HotPath:
         pcy_d, pcx_d = self._dev(np.asarray(pcy, np.float64)), self._dev(np.asarray(pcx, np.float64))
         cnt = torch.empty(n_buckets, dtype=torch.int64, device=self.device)
         bstart = torch.empty(n_buckets + 1, dtype=torch.int64, device=self.device)
-        rc = self.lib.marex_nn_bucket_count_i32(self.ctx.handle, prev.data_ptr(), int(ny), int(nx), t["par"].data_ptr(),
-                                                len(par_keys), t["poff"].data_ptr(), t["pent"].data_ptr(), t["gs"].data_ptr(),
-                                                t["ngy"].data_ptr(), t["ngx"].data_ptr(), base_d.data_ptr(), n_buckets,
-                                                cnt.data_ptr(), bstart.data_ptr())
-        self.ctx.check(rc, "marex_nn_bucket_count_i32")
+        self.call("marex_nn_bucket_count_i32", prev, int(ny), int(nx), t["par"], len(par_keys), t["poff"], t["pent"], t["gs"],
+                  t["ngy"], t["ngx"], base_d, n_buckets, cnt, bstart)
         n_cells = int(bstart[n_buckets].item())
         if n_cells <= 0:
             raise ProcessingError("partition_nn: the parents have no cells in the previous slice")
         cells = torch.empty(n_cells, dtype=torch.int32, device=self.device)
-        rc = self.lib.marex_partition_nn_i32(self.ctx.handle, cur.data_ptr(), prev.data_ptr(), int(ny), int(nx),
-                                             t["par"].data_ptr(), len(par_keys), t["poff"].data_ptr(), t["pent"].data_ptr(),
-                                             t["ck"].data_ptr(), len(child_keys), t["off"].data_ptr(), pcy_d.data_ptr(),
-                                             pcx_d.data_ptr(), t["lab"].data_ptr(), t["gs"].data_ptr(), t["ngy"].data_ptr(),
-                                             t["ngx"].data_ptr(), t["maxd"].data_ptr(), base_d.data_ptr(), n_buckets,
-                                             bstart.data_ptr(), cnt.data_ptr(), cells.data_ptr(), n_cells, int(bool(wrap)))
-        self.ctx.check(rc, "marex_partition_nn_i32")
+        self.call("marex_partition_nn_i32", cur, prev, int(ny), int(nx), t["par"], len(par_keys), t["poff"], t["pent"], t["ck"],
+                  len(child_keys), t["off"], pcy_d, pcx_d, t["lab"], t["gs"], t["ngy"], t["ngx"], t["maxd"], base_d, n_buckets,
+                  bstart, cnt, cells, n_cells, int(bool(wrap)))
 
     def id_spans(self, ids: torch.Tensor):
         """``(tmin, tmax)`` int32 host arrays over IDs 0..max of ``ids`` int32 ``[T, C]``: the first / last timestep of
         every ID (INT_MAX / -1 when absent); ``None`` when the field has no ID > 0."""
-        self._bind_stream()
         T, Cn = self._ids_check(ids)
         _, hi = self.ids_minmax(ids)
         if hi <= 0:
             return None
-        nid = hi + 1
-        ntiles = (nid + 4095) // 4096
-        self._check_fits(16 * nid + 16 * ntiles, "ID spans", f"per-ID first / last timestep for IDs 0..{hi}")
-        tmin = torch.empty(nid, dtype=torch.int32, device=self.device)
-        tmax = torch.empty(nid, dtype=torch.int32, device=self.device)
-        off = torch.empty(nid, dtype=torch.int64, device=self.device)
-        work = torch.empty(2 * ntiles, dtype=torch.int64, device=self.device)
-        total = torch.empty(1, dtype=torch.int64, device=self.device)
-        rc = self.lib.marex_object_spans_i32(self.ctx.handle, ids.data_ptr(), T, Cn, hi, tmin.data_ptr(), tmax.data_ptr(),
-                                             off.data_ptr(), work.data_ptr(), total.data_ptr())
-        self.ctx.check(rc, "marex_object_spans_i32")
+        tmin, tmax, _, _ = self._object_spans(ids, T, Cn, hi, "ID spans", f"per-ID first / last timestep for IDs 0..{hi}")
         return tmin.cpu().numpy(), tmax.cpu().numpy()
 
     def event_moments(self, ev: torch.Tensor, orig: torch.Tensor, ny: int, nx: int, n_ev: int,
@@ -983,7 +881,6 @@ class HotPath:
         ``[T, n_ev, 5]`` (cells, sum y, sum x, sum of x shifted by -nx right of nx / 2, near-edge flags), ``gid`` int32
         ``[T, n_ev]`` (largest ID of ``orig`` under the slot) and, with float32 ``weights`` of a slice, ``wmom`` float64
         ``[T, n_ev, 4]`` (sums of w, w y, w x, w x_shifted)."""
-        self._bind_stream()
         T, Cn = self._ids_check(ev)
         self._ids_check(orig)
         slots = T * int(n_ev)
@@ -992,10 +889,7 @@ class HotPath:
         acc = torch.empty((slots, 5), dtype=torch.int64, device=self.device)
         gid = torch.empty(slots, dtype=torch.int32, device=self.device)
         wacc = torch.empty((slots, 4), dtype=torch.float64, device=self.device) if weights is not None else None
-        rc = self.lib.marex_event_moments_i32(self.ctx.handle, ev.data_ptr(), orig.data_ptr(), T, int(ny), int(nx), int(n_ev),
-                                              weights.data_ptr() if weights is not None else None, acc.data_ptr(),
-                                              wacc.data_ptr() if wacc is not None else None, gid.data_ptr())
-        self.ctx.check(rc, "marex_event_moments_i32")
+        self.call("marex_event_moments_i32", ev, orig, T, int(ny), int(nx), int(n_ev), weights, acc, wacc, gid)
         out = {"mom": acc.cpu().numpy().reshape(T, n_ev, 5), "gid": gid.cpu().numpy().reshape(T, n_ev)}
         if wacc is not None:
             out["wmom"] = wacc.cpu().numpy().reshape(T, n_ev, 4)
@@ -1020,14 +914,8 @@ class HotPath:
             raise ProcessingError("No objects found for area-based filtering")
         if area_filter_absolute is not None:
             thr = float(area_filter_absolute)
-        else:  # np.percentile(areas, 100 q), "linear": two order statistics from a device sort, NumPy's lerp on the host
-            srt = torch.sort(obj_areas).values
-            virt = (n_before - 1) * float(np.float64(area_filter_quartile * 100.0) / 100.0)
-            lo = int(np.floor(virt))
-            g = virt - lo
-            hi = min(lo + 1, n_before - 1)
-            a, b = float(srt[lo].item()), float(srt[hi].item())
-            thr = a + (b - a) * g if g < 0.5 else b - (b - a) * (1.0 - g)
+        else:
+            thr = _linear_percentile(obj_areas, area_filter_quartile)
         out = self._buf(wsp, "filtered", tuple(data_bin.shape), torch.uint8, self.device)
         dropped = False  # the reference's `object_ids_keep[0] = -1`: the first object of the whole list is never kept
         n_after = int((obj_areas.to(torch.float64) >= thr).sum().item())
@@ -1040,21 +928,16 @@ class HotPath:
                 if float(flat[root].item()) >= thr:
                     n_after -= 1
                 dropped = True
-            rc = self.lib.marex_filter_by_area_u8(self.ctx.handle, labels.data_ptr(), areas.data_ptr(), labels.numel(), thr,
-                                                  first, out[t0:t0 + labels.shape[0]].data_ptr())
-            self.ctx.check(rc, "marex_filter_by_area_u8")
+            self.call("marex_filter_by_area_u8", labels, areas, labels.numel(), thr, first, out[t0:t0 + labels.shape[0]])
         return {"filtered": out, "area_threshold": thr, "object_areas": obj_areas, "n_before": n_before, "n_after": n_after,
                 "labels": blocks[0][1] if len(blocks) == 1 else [b[1] for b in blocks]}
 
     def fill_holes_mesh(self, data_bin: torch.Tensor, mask: torch.Tensor, nbr: torch.Tensor, R_fill: int,
                         wsp: Optional[dict] = None) -> torch.Tensor:
         """``fill_holes`` on an unstructured mesh (track.py:1543-1606): ``nbr`` int32 ``[3, C]``, 0-based, -1 = none."""
-        self._bind_stream()
         T, Cn = data_bin.shape
         out = self._buf(wsp, "filled_mesh", (T, Cn), torch.uint8, self.device)
-        rc = self.lib.marex_fill_holes_mesh_u8(self.ctx.handle, data_bin.data_ptr(), mask.data_ptr(), nbr.data_ptr(), T, Cn,
-                                               int(R_fill), out.data_ptr())
-        self.ctx.check(rc, "marex_fill_holes_mesh_u8")
+        self.call("marex_fill_holes_mesh_u8", data_bin, mask, nbr, T, Cn, int(R_fill), out)
         return out
 
     def filter_small_objects_mesh(self, data_bin: torch.Tensor, mask: torch.Tensor, nbr: torch.Tensor,
@@ -1062,13 +945,10 @@ class HotPath:
                                   wsp: Optional[dict] = None) -> Dict[str, object]:
         """``filter_small_objects`` on an unstructured mesh (track.py:1776-1857): sizes in cells, percentile over the
         clusters larger than 50 (5) cells, keep STRICTLY larger than the threshold."""
-        self._bind_stream()
         T, Cn = data_bin.shape
         labels = self._buf(wsp, "labels_mesh", (T, Cn), torch.int32, self.device)
         areas = self._buf(wsp, "areas_mesh", (T, Cn), torch.int32, self.device)
-        rc = self.lib.marex_label_mesh_i32(self.ctx.handle, data_bin.data_ptr(), mask.data_ptr(), nbr.data_ptr(), T, Cn,
-                                           labels.data_ptr(), areas.data_ptr())
-        self.ctx.check(rc, "marex_label_mesh_i32")
+        self.call("marex_label_mesh_i32", data_bin, mask, nbr, T, Cn, labels, areas)
         flat = areas.reshape(-1)
         big = flat[flat > (5 if area_filter_absolute is not None else 50)]
         n_before = int(big.numel())
@@ -1077,25 +957,16 @@ class HotPath:
         if area_filter_absolute is not None:
             thr = float(area_filter_absolute)
         else:
-            srt = torch.sort(big).values
-            virt = (n_before - 1) * float(np.float64(area_filter_quartile * 100) / 100.0)
-            lo = int(np.floor(virt))
-            g = virt - lo
-            hi = min(lo + 1, n_before - 1)
-            a, b = float(srt[lo].item()), float(srt[hi].item())
-            thr = a + (b - a) * g if g < 0.5 else b - (b - a) * (1.0 - g)
+            thr = _linear_percentile(big, area_filter_quartile)
         out = self._buf(wsp, "filtered_mesh", (T, Cn), torch.uint8, self.device)
         # strict ">" : areas are integers, so "> thr" == ">= floor(thr) + 1"
-        rc = self.lib.marex_filter_by_area_u8(self.ctx.handle, labels.data_ptr(), areas.data_ptr(), labels.numel(),
-                                              float(np.floor(thr) + 1.0), 0, out.data_ptr())
-        self.ctx.check(rc, "marex_filter_by_area_u8")
+        self.call("marex_filter_by_area_u8", labels, areas, labels.numel(), float(np.floor(thr) + 1.0), 0, out)
         return {"filtered": out, "area_threshold": thr, "object_areas": big, "n_before": n_before,
                 "n_after": int((big.to(torch.float64) > thr).sum().item()), "labels": labels}
 
     def hobday_thresholds_exact(self, anom: torch.Tensor, dcal: DeviceCalendar, percentile: float, wd: int,
                                 wsp: Optional[dict] = None) -> torch.Tensor:
         """``np.nanpercentile`` per (dayofyear window, cell), float32, layout ``[366, C]`` (detect.py:1921-1956)."""
-        self._bind_stream()
         T_out, Cn = anom.shape
         nd = np.diff(dcal.plan.doy_start).astype(np.int64)
         half = int(wd) // 2
@@ -1104,11 +975,8 @@ class HotPath:
         q32 = np.float32(percentile) / np.float32(100)  # NumPy's own float32 quantile
         thr = self._buf(wsp, "thr_doy_major", (N_DOY, Cn), torch.float32, self.device)
         overflow = torch.zeros((1,), dtype=torch.int32, device=self.device)
-        rc = self.lib.marex_hobday_exact_f32(
-            self.ctx.handle, anom.data_ptr(), T_out, Cn, dcal.doy_start.data_ptr(), dcal.doy_rows.data_ptr(),
-            max(max_rows, 1), float(q32), float(q32), int(wd), thr.data_ptr(), overflow.data_ptr(),
-        )
-        self.ctx.check(rc, "marex_hobday_exact_f32")
+        self.call("marex_hobday_exact_f32", anom, T_out, Cn, dcal.doy_start, dcal.doy_rows, max(max_rows, 1), float(q32),
+                  float(q32), int(wd), thr, overflow)
         if int(overflow.item()) != 0:
             raise ProcessingError("exact Hobday percentile: selection buffer overflow (internal sizing error)")
         return thr
@@ -1118,26 +986,19 @@ class HotPath:
         """Per-cell constant threshold, float64 ``[C]`` (detect.py:2873-2912) + warning statistics."""
         from .binning import global_bins
 
-        self._bind_stream()
         T_out, Cn = anom.shape
         thr = torch.empty((Cn,), dtype=torch.float64, device=self.device)
         q = float(percentile) / 100.0
         if method_percentile == "exact":
-            rc = self.lib.marex_global_threshold_f32(
-                self.ctx.handle, anom.data_ptr(), T_out, Cn, q, 1, None, None, 0, 0.0, 0.0, thr.data_ptr(), None, None
-            )
-            self.ctx.check(rc, "marex_global_threshold_f32")
+            self.call("marex_global_threshold_f32", anom, T_out, Cn, q, 1, None, None, 0, 0.0, 0.0, thr, None, None)
             return {"thr_f64": thr, "stats": {"n_too_low": 0, "n_too_high": 0, "min": float("nan"), "max": float("nan")}}
         gb = global_bins(bins.precision, bins.max_anomaly)
         edges = self._dev(gb.edges.astype(np.float64))
         centres = self._dev(gb.centres.astype(np.float64))
         stats = torch.zeros((8,), dtype=torch.int32, device=self.device)
         minmax = torch.tensor([float("inf"), float("-inf")], dtype=torch.float64, device=self.device)
-        rc = self.lib.marex_global_threshold_f32(
-            self.ctx.handle, anom.data_ptr(), T_out, Cn, q, 0, edges.data_ptr(), centres.data_ptr(), gb.nb,
-            float(gb.lower_bound), float(gb.upper_bound), thr.data_ptr(), stats.data_ptr(), minmax.data_ptr(),
-        )
-        self.ctx.check(rc, "marex_global_threshold_f32")
+        self.call("marex_global_threshold_f32", anom, T_out, Cn, q, 0, edges, centres, gb.nb, float(gb.lower_bound),
+                  float(gb.upper_bound), thr, stats, minmax)
         self.sync()
         s = stats.cpu().numpy().view(np.uint32)
         mm = minmax.cpu().numpy()
@@ -1151,15 +1012,9 @@ class HotPath:
         }
 
     def mask_ge_const(self, anom: torch.Tensor, thr_f64: torch.Tensor, wsp: Optional[dict] = None) -> Dict[str, torch.Tensor]:
-        self._bind_stream()
         T_out, Cn = anom.shape
-        ext = self._buf(wsp, "extreme", (T_out, Cn), torch.uint8, self.device)
-        n_true = self._buf(wsp, "n_true", (1,), torch.int64, self.device)
-        n_true.zero_()
-        rc = self.lib.marex_mask_ge_const_f32(
-            self.ctx.handle, anom.data_ptr(), thr_f64.data_ptr(), T_out, Cn, ext.data_ptr(), n_true.data_ptr()
-        )
-        self.ctx.check(rc, "marex_mask_ge_const_f32")
+        ext, n_true = self._extreme_buffers(wsp, T_out, Cn)
+        self.call("marex_mask_ge_const_f32", anom, thr_f64, T_out, Cn, ext, n_true)
         return {"extreme": ext, "n_true": n_true}
 
     # ------------------------------------------------------------------ Blosc / LZ4 chunk compression (zarr_io.write_array)
@@ -1179,7 +1034,6 @@ class HotPath:
         byte-identical to ``marex_blosc_compress_h`` with ``dstcap = nbytes + 16``.  Returns ``(frames, lengths)``:
         frames uint8 ``[B, nbytes + 16]`` on the device (row i holds frame i in its first ``lengths[i]`` bytes) and
         lengths int64 NumPy ``[B]`` (synchronises).  ``variant`` 0: one wave per LZ4 stream, 1: one lane per stream."""
-        self._bind_stream()
         if chunks.dtype != torch.uint8 or chunks.dim() != 2 or not chunks.is_contiguous() or chunks.device != self.device:
             raise ProcessingError("blosc_compress: chunks must be a contiguous uint8 [B, nbytes] tensor on the engine's device",
                                   details=f"got {chunks.dtype} {tuple(chunks.shape)} on {chunks.device}")
@@ -1191,9 +1045,8 @@ class HotPath:
         work = self._buf(wsp, "blosc_work", (max(wb, 1),), torch.uint8, self.device)
         frames = self._buf(wsp, "blosc_frames", (B, nb + 16), torch.uint8, self.device)
         lens = self._buf(wsp, "blosc_lens", (B,), torch.int64, self.device)
-        rc = self.lib.marex_blosc_compress_d(self.ctx.handle, chunks.data_ptr(), nb, B, int(typesize), int(shuffle), int(blocksize),
-                                             int(variant), work.data_ptr(), wb, frames.data_ptr(), lens.data_ptr())
-        self.ctx.check(rc, "marex_blosc_compress_d")
+        self.call("marex_blosc_compress_d", chunks, nb, B, int(typesize), int(shuffle), int(blocksize), int(variant), work, wb,
+                  frames, lens)
         lengths[:] = lens.cpu().numpy()
         if (lengths < 16).any() or (lengths > nb + 16).any():
             raise ProcessingError("blosc_compress: frame length out of range (internal error)", details=str(lengths[:8]))

@@ -434,24 +434,17 @@ class tracker:  # noqa: N801 -- the reference's public name (marEx.tracker)
         area_threshold, accepted_area_fraction, preprocessed_area_fraction)``, areas in cells."""
         import torch
 
+        from .track_pre import _preprocess_device
+
         if checkpoint in ("save", "load"):
             raise ConfigurationError(f"checkpoint={checkpoint!r} is not supported by the device tracker")
         eng = self._engine()
         x, T, ny, nx = self._device_u8(self.data_bin, eng)
         mk = torch.from_numpy(self._mask_host.reshape(-1).astype(np.uint8)).to(eng.device)
-        R = self.R_fill
-        raw_area = float(x.sum(dtype=torch.int64).item())
-        a = eng.fill_holes(x, mk, ny, nx, R, self.regional_mode)
-        g = eng.fill_time_gaps(a, mk, ny, nx, R, int(self.T_fill), self.regional_mode)
         absolute = float(self.area_filter_absolute) if self._use_absolute_filtering else None
-        r = eng.filter_small_objects(g, ny, nx, self.area_filter_quartile, absolute, self.regional_mode)
-        areas = r["object_areas"].to(torch.float64)
-        total = float(areas.sum().item())
-        accepted = float(areas[areas > r["area_threshold"]].sum().item())  # strictly above, as track.py:1337
-        processed = float(r["filtered"].sum(dtype=torch.int64).item())
-        stats = (total, r["n_before"], r["n_after"], r["area_threshold"], accepted / total,
-                 raw_area / processed if processed else float("nan"))
-        return self._wrap_device(r["filtered"], T, ny, nx, "data_bin_preproc"), stats
+        filtered, stats = _preprocess_device(eng, x, mk, ny, nx, self.R_fill, self.T_fill, self.area_filter_quartile, absolute,
+                                             self.regional_mode)
+        return self._wrap_device(filtered, T, ny, nx, "data_bin_preproc"), stats
 
     def identify_objects(self, data_bin, time_connectivity: bool):
         """Connected regions of ``data_bin`` (track.py:1912-2048, structured grid): 26-connected in (time, y, x) with
@@ -514,6 +507,11 @@ class tracker:  # noqa: N801 -- the reference's public name (marEx.tracker)
         at.update(self.data_attrs)
         return self._remap_coordinates(events_ds)
 
+    def _latlon_coords(self) -> dict:
+        """The input's lat / lon as coordinate entries ``name -> (dims, host values)``."""
+        return {self.ycoord: (_coord_dims(self.lat_init, (self.ydim,)), _host(self.lat_init)),
+                self.xcoord: (_coord_dims(self.lon_init, (self.xdim,)), _host(self.lon_init))}
+
     def _remap_coordinates(self, events_ds):
         """Re-assign the input's lat / lon coordinates (track.py:978-983)."""
         from .xr_compat import DataArray, Dataset
@@ -521,9 +519,7 @@ class tracker:  # noqa: N801 -- the reference's public name (marEx.tracker)
         if "centroid" in events_ds.data_vars:
             return self._remap_merge_coordinates(events_ds)
         v = events_ds["ID_field"]
-        coords = {self.timecoord: (self.timedim, self.time_values),
-                  self.ycoord: (_coord_dims(self.lat_init, (self.ydim,)), _host(self.lat_init)),
-                  self.xcoord: (_coord_dims(self.lon_init, (self.xdim,)), _host(self.lon_init))}
+        coords = {self.timecoord: (self.timedim, self.time_values), **self._latlon_coords()}
         out = Dataset({"ID_field": DataArray(v.values, dims=tuple(v.dims), coords=coords, name="ID_field")})
         out.attrs.update(events_ds.attrs)
         return out
@@ -727,8 +723,15 @@ class tracker:  # noqa: N801 -- the reference's public name (marEx.tracker)
             found = (sid[pos] == col) if sid.size else np.zeros(col.shape, dtype=bool)
             return found, (sarea[pos] if sid.size else np.zeros(col.shape))
 
-        f0, a0 = lookup(ov[:, 0])
-        f1, a1 = lookup(ov[:, 1])
+        return self._keep_overlaps(ov, lookup)
+
+    def _keep_overlaps(self, ov: np.ndarray, lookup) -> np.ndarray:
+        """The overlap-threshold rule (track.py:2506-2552) on ``(n, 3)`` pairs; ``lookup(ids) -> (found, area)`` says per
+        column which IDs are known and their areas (any value where not found)."""
+        empty = np.empty((0, 3), dtype=np.int32)
+        if len(ov) == 0:
+            return empty
+        (f0, a0), (f1, a1) = lookup(ov[:, 0]), lookup(ov[:, 1])
         valid = f0 & f1
         if not np.any(valid):
             return empty
@@ -792,18 +795,11 @@ class tracker:  # noqa: N801 -- the reference's public name (marEx.tracker)
 
     def _enforce(self, ov: np.ndarray, props: _Props) -> np.ndarray:
         """enforce_overlap_threshold (track.py:2506-2552) against the live props."""
-        ov = np.asarray(ov)
-        if len(ov) == 0:
-            return np.empty((0, 3), dtype=np.int32)
-        ok = props.has(ov[:, 0]) & props.has(ov[:, 1])
-        if not ok.any():
-            return np.empty((0, 3), dtype=np.int32)
-        v = ov[ok]
-        frac = v[:, 2].astype(float) / np.minimum(props.area[v[:, 0]], props.area[v[:, 1]])
-        if np.any(frac > 1.0):
-            logger.warning(f"Found {np.sum(frac > 1.0)} overlap fractions > 1.0")
-            logger.warning(f"Max overlap fraction: {frac.max()}")
-        return v[frac >= self.overlap_threshold]
+        def lookup(col):
+            found = props.has(col)
+            return found, props.area[np.where(found, col, 0)]
+
+        return self._keep_overlaps(np.asarray(ov), lookup)
 
     def _slice_props(self, eng, ids, t, nx):
         r = eng.object_moments(ids[t:t + 1], ids.shape[1] // nx, nx, wrap=not self.regional_mode)
@@ -1063,8 +1059,7 @@ class tracker:  # noqa: N801 -- the reference's public name (marEx.tracker)
         elif lo >= 0 and hi > 180:
             clon = np.where(clon < 0, clon + 360, clon)
         cen = np.stack([clat, clon]).astype(np.float32)
-        extra = {self.ycoord: (_coord_dims(self.lat_init, (self.ydim,)), _host(self.lat_init)),
-                 self.xcoord: (_coord_dims(self.lon_init, (self.xdim,)), lon0)}
+        extra = self._latlon_coords()
         data = {}
         for k, v in events_ds.data_vars.items():
             c = {n: (tuple(cv.dims), np.asarray(cv.values)) for n, cv in v.coords.items()}

@@ -272,13 +272,8 @@ def read_array_to_device(path: str, eng, lead: int | None = None):
     tab = lambda a, dt: torch.from_numpy(np.asarray(a, dtype=dt)).to(dev)  # noqa: E731
     t_src, t_cs, t_dst, t_raw = tab(s_src, np.int64), tab(s_cs, np.int32), tab(s_dst, np.int64), tab(s_raw, np.int32)
     t_off, t_e0, t_ne, t_valid = tab(b_off, np.int64), tab(b_e0, np.int64), tab(b_ne, np.int32), tab(b_valid, np.int32)
-    eng._bind_stream()
-    rc = eng.lib.marex_lz4_decode_streams(eng.ctx.handle, comp_d.data_ptr(), t_src.data_ptr(), t_cs.data_ptr(), t_dst.data_ptr(),
-                                          t_raw.data_ptr(), len(s_src), int(max(s_raw)), planes.data_ptr(), status.data_ptr())
-    eng.ctx.check(rc, "marex_lz4_decode_streams")
-    rc = eng.lib.marex_unshuffle_place(eng.ctx.handle, planes.data_ptr(), t_off.data_ptr(), t_e0.data_ptr(), t_ne.data_ptr(),
-                                       t_valid.data_ptr(), len(b_off), int(max(b_ne)), ts, int(bool(shuffled)), out.data_ptr())
-    eng.ctx.check(rc, "marex_unshuffle_place")
+    eng.call("marex_lz4_decode_streams", comp_d, t_src, t_cs, t_dst, t_raw, len(s_src), int(max(s_raw)), planes, status)
+    eng.call("marex_unshuffle_place", planes, t_off, t_e0, t_ne, t_valid, len(b_off), int(max(b_ne)), ts, int(bool(shuffled)), out)
     eng.sync()
     if int(status.item()) != 0:
         raise DataValidationError("malformed LZ4 stream in a chunk", details=f"{int(status.item())} streams failed")

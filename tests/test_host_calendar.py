@@ -26,6 +26,8 @@ def test_year_doy_tables_and_trim():
     # rowb_index inverts doy_rows on the kept rows
     assert np.array_equal(cal.doy_rows[cal.rowb_index[cal.kept]], cal.out_index[cal.kept])
     assert not cal.has_duplicates
+    # largest bucket: 1 January of the kept years 2002..2008 (the axis ends on 2008-06-19)
+    assert cal.max_bucket == np.diff(cal.doy_start).max() == 7 and isinstance(cal.max_bucket, int)
 
 
 def test_leap_day_labels():
@@ -34,6 +36,7 @@ def test_leap_day_labels():
     assert cal.doy[59] == 60 and cal.doy[365] == 366  # 29 Feb 2000 and 31 Dec 2000
     assert cal.tindex[1, 365] == -1  # 2001 has no dayofyear 366
     assert cal.T_out == cal.T
+    assert cal.max_bucket == np.diff(cal.doy_start).max() == 2  # two years; dayofyear 366 alone has one row
 
 
 def test_duplicates_are_flagged():
