@@ -288,12 +288,12 @@ extern "C" int marex_blosc_decompress_h(const void* src_v, int64_t srclen, void*
 // stored (incompressible) splits: plain copies, spread over many threads
 __global__ void __launch_bounds__(256)
 k_stored_streams(const unsigned char* __restrict__ comp, const long* __restrict__ src_off, const int* __restrict__ csize,
-                 const long* __restrict__ dst_off, const int* __restrict__ rawsz, unsigned char* __restrict__ out) {
-    const int s = blockIdx.y;
-    const int raw = rawsz[s];
-    if (csize[s] != raw) return;
+                 const long* __restrict__ dst_off, const int* __restrict__ rawsz, int n_streams, unsigned char* __restrict__ out) {
     const int i = (int)blockIdx.x * 256 + threadIdx.x;
-    if (i < raw) out[dst_off[s] + i] = comp[src_off[s] + i];
+    for (int s = blockIdx.y; s < n_streams; s += gridDim.y) {  // a grid's y extent ends at 65 535: more streams are strided over
+        const int raw = rawsz[s];
+        if (csize[s] == raw && i < raw) out[dst_off[s] + i] = comp[src_off[s] + i];
+    }
 }
 
 __global__ void __launch_bounds__(64)
@@ -385,18 +385,19 @@ k_lz4_streams(const unsigned char* __restrict__ comp, const long* __restrict__ s
 // byte planes of a shuffled block -> elements at their place in the destination (typesize bytes each)
 __global__ void __launch_bounds__(256)
 k_unshuffle_place(const unsigned char* __restrict__ planes, const long* __restrict__ blk_off, const long* __restrict__ blk_elem0,
-                  const int* __restrict__ blk_ne, const int* __restrict__ blk_valid, int typesize, int shuffled,
+                  const int* __restrict__ blk_ne, const int* __restrict__ blk_valid, int n_blocks, int typesize, int shuffled,
                   unsigned char* __restrict__ out) {
-    const int b = blockIdx.y;
     const int e = (int)blockIdx.x * 256 + threadIdx.x;
-    if (e >= blk_valid[b]) return;
-    const int ne = blk_ne[b];
-    const unsigned char* p = planes + blk_off[b];
-    unsigned char* o = out + (size_t)(blk_elem0[b] + e) * typesize;
-    if (shuffled) {
-        for (int k = 0; k < typesize; ++k) o[k] = p[(size_t)k * ne + e];
-    } else {
-        for (int k = 0; k < typesize; ++k) o[k] = p[(size_t)e * typesize + k];
+    for (int b = blockIdx.y; b < n_blocks; b += gridDim.y) {  // as k_stored_streams: more than 65 535 blocks are strided over
+        if (e >= blk_valid[b]) continue;
+        const int ne = blk_ne[b];
+        const unsigned char* p = planes + blk_off[b];
+        unsigned char* o = out + (size_t)(blk_elem0[b] + e) * typesize;
+        if (shuffled) {
+            for (int k = 0; k < typesize; ++k) o[k] = p[(size_t)k * ne + e];
+        } else {
+            for (int k = 0; k < typesize; ++k) o[k] = p[(size_t)e * typesize + k];
+        }
     }
 }
 
@@ -411,8 +412,9 @@ extern "C" int marex_lz4_decode_streams(marex_ctx* ctx, const uint8_t* comp, con
     while (ring < max_raw && ring < 65536) ring <<= 1;  // power of two: ring positions are masked
     if (ring > 48 * 1024)
         HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_lz4_streams, hipFuncAttributeMaxDynamicSharedMemorySize, ring));
-    hipLaunchKernelGGL(k_stored_streams, dim3((unsigned)((max_raw + 255) / 256), (unsigned)n_streams), dim3(256), 0, ctx->stream, comp,
-                       reinterpret_cast<const long*>(src_off), csize, reinterpret_cast<const long*>(dst_off), rawsz, planes);
+    hipLaunchKernelGGL(k_stored_streams, dim3((unsigned)((max_raw + 255) / 256), (unsigned)std::min(n_streams, 65535)), dim3(256), 0,
+                       ctx->stream, comp, reinterpret_cast<const long*>(src_off), csize, reinterpret_cast<const long*>(dst_off), rawsz,
+                       n_streams, planes);
     hipLaunchKernelGGL(k_lz4_streams, dim3((unsigned)n_streams), dim3(64), (size_t)ring, ctx->stream, comp,
                        reinterpret_cast<const long*>(src_off), csize, reinterpret_cast<const long*>(dst_off), rawsz, ring - 1, planes,
                        status);
@@ -427,9 +429,9 @@ extern "C" int marex_unshuffle_place(marex_ctx* ctx, const uint8_t* planes, cons
     if (!planes || !blk_off || !blk_elem0 || !blk_ne || !blk_valid || !out || n_blocks <= 0 || max_ne <= 0 || typesize < 1)
         return fail(ctx, -1, "marex_unshuffle_place: null pointer or empty table");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(k_unshuffle_place, dim3((unsigned)((max_ne + 255) / 256), (unsigned)n_blocks), dim3(256), 0, ctx->stream, planes,
-                       reinterpret_cast<const long*>(blk_off), reinterpret_cast<const long*>(blk_elem0), blk_ne, blk_valid, typesize,
-                       shuffled, out);
+    hipLaunchKernelGGL(k_unshuffle_place, dim3((unsigned)((max_ne + 255) / 256), (unsigned)std::min(n_blocks, 65535)), dim3(256), 0,
+                       ctx->stream, planes, reinterpret_cast<const long*>(blk_off), reinterpret_cast<const long*>(blk_elem0), blk_ne,
+                       blk_valid, n_blocks, typesize, shuffled, out);
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }

@@ -154,7 +154,14 @@ def plan_blosc_frame(raw: bytes, typesize: int, expected_nbytes: int, where: str
 
     Returns ``(shuffled, streams, blocks)``: ``streams`` = ``(offset of the compressed bytes in the frame, compressed size,
     destination offset in the chunk's byte planes, raw size)``, ``blocks`` = ``(plane offset, first element relative to the
-    chunk, elements, bytes)``."""
+    chunk, elements, bytes)``.  A memcpyed frame (flag 0x2: what ``marex_blosc_compress_h`` and c-blosc write for a chunk
+    LZ4 cannot shrink) has no streams to decode: it is planned as ``(None, [], [])``, and its ``expected_nbytes`` payload
+    bytes follow the 16-byte header as they are.
+
+    A frame whose blocks or whose whole do not hold whole elements (``blocksize % typesize != 0``, ``nbytes % typesize !=
+    0``) raises ``DataValidationError``: no encoder we know writes one, the placement kernel counts in elements, and such a
+    frame would come out with every block after the first misplaced -- it is refused like any other frame whose numbers do
+    not fit together, not decoded wrongly."""
     import struct
 
     def bad(msg):
@@ -163,14 +170,21 @@ def plan_blosc_frame(raw: bytes, typesize: int, expected_nbytes: int, where: str
     if len(raw) < 16:
         raise bad(f"{len(raw)} bytes, shorter than the 16-byte header")
     _, _, flags, ts, nbytes, blocksize, cbytes = struct.unpack("<BBBBIII", raw[:16])
-    if flags & 0x2 or flags & 0x4 or (flags >> 5) != 1 or ts != typesize:
+    memcpyed = bool(flags & 0x2)  # the payload is the chunk itself: codec and shuffle bits say nothing about it
+    if ts != typesize or (not memcpyed and (flags & 0x4 or (flags >> 5) != 1)):
         raise DependencyError("device read: LZ4 Blosc frames with byte shuffle only", details=f"{where}: flags {flags:#x}, typesize {ts}")
     if cbytes != len(raw):
         raise bad(f"header says {cbytes} compressed bytes, the file holds {len(raw)}")
     if nbytes != expected_nbytes:
         raise bad(f"header says {nbytes} decoded bytes, the chunk shape needs {expected_nbytes}")
+    if memcpyed:
+        if 16 + nbytes > len(raw):
+            raise bad(f"memcpyed frame of {nbytes} bytes in a file of {len(raw)}")
+        return None, [], []
     if blocksize <= 0 or nbytes <= 0:
         raise bad(f"blocksize {blocksize}, nbytes {nbytes}")
+    if blocksize % ts or nbytes % ts:
+        raise bad(f"blocksize {blocksize} / nbytes {nbytes} do not hold whole elements of {ts} bytes")
     nblocks = (nbytes + blocksize - 1) // blocksize
     table_end = 16 + 4 * nblocks
     if table_end > len(raw):
@@ -203,7 +217,9 @@ def read_array_to_device(path: str, eng, lead: int | None = None):
     """Read a Zarr v2 array whose chunks span every dimension but the first (``chunks = (ct, *shape[1:])``, the layout of
     the reference's time-chunked stores) straight into HBM: the COMPRESSED chunk bytes are uploaded, the LZ4 streams are
     decoded one wave each (``marex_lz4_decode_streams``) and the byte shuffle is undone while the elements are placed in
-    the destination (``marex_unshuffle_place``).  ``lead`` limits the read to the first ``lead`` steps of dimension 0.
+    the destination (``marex_unshuffle_place``); a memcpyed frame (an incompressible chunk) is uploaded and copied to its
+    place as it is.  ``lead`` limits the read to the first ``lead`` steps of dimension 0.  Byte orders and dtypes torch has
+    no tensor for raise ``DependencyError`` before a chunk file is opened.
     Returns a torch tensor of the array's dtype and shape ``(lead, *shape[1:])`` on ``eng.device``."""
     import struct
 
@@ -214,6 +230,11 @@ def read_array_to_device(path: str, eng, lead: int | None = None):
     if meta.get("zarr_format") != 2 or meta.get("order", "C") != "C" or meta.get("filters") or comp.get("id") != "blosc":
         raise DependencyError("device read: Zarr v2, C order, Blosc chunks, no filters")
     shape, chunks, dtype = tuple(meta["shape"]), tuple(meta["chunks"]), np.dtype(meta["dtype"])
+    tdt = {"float32": torch.float32, "float64": torch.float64, "int32": torch.int32, "int64": torch.int64, "int8": torch.int8,
+           "uint8": torch.uint8, "int16": torch.int16, "bool": torch.bool}.get(dtype.name)
+    if tdt is None or not dtype.isnative:  # before any chunk is opened; ">f4" is also named float32
+        raise DependencyError("device read: native-endian float32/64, int8/16/32/64, uint8 and bool arrays",
+                              details=f"dtype {meta['dtype']!r}")
     if chunks[1:] != shape[1:]:
         raise DependencyError("device read: chunks must span every dimension but the first", details=f"shape {shape}, chunks {chunks}")
     sep = meta.get("dimension_separator", ".")
@@ -226,6 +247,7 @@ def read_array_to_device(path: str, eng, lead: int | None = None):
     planes_size, shuffled = 0, None
     chunk_bytes = int(np.prod(chunks)) * ts
     missing = []  # (first element, one-past-last element) of chunks without a file: left at the fill value, as read_array does
+    copied = []   # (first byte in out, payload) of memcpyed frames: uploaded as they are, clipped by ``lead``
     for ci in range((T + chunks[0] - 1) // chunks[0]):
         f = os.path.join(path, sep.join([str(ci)] + ["0"] * (len(shape) - 1)))
         elem_first = ci * chunks[0] * per_step
@@ -235,6 +257,9 @@ def read_array_to_device(path: str, eng, lead: int | None = None):
             continue
         raw = open(f, "rb").read()
         sh, streams, blocks = plan_blosc_frame(raw, ts, chunk_bytes, f)
+        if sh is None:
+            copied.append((elem_first * ts, raw[16: 16 + min(chunk_bytes, (elem_valid_end - elem_first) * ts)]))
+            continue
         if shuffled is None:
             shuffled = sh
         elif shuffled != sh:
@@ -257,8 +282,6 @@ def read_array_to_device(path: str, eng, lead: int | None = None):
     planes = torch.empty(max(planes_size, 1), dtype=torch.uint8, device=dev)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
     out = torch.empty(T * per_step * ts, dtype=torch.uint8, device=dev)
-    tdt = {"float32": torch.float32, "float64": torch.float64, "int32": torch.int32, "int64": torch.int64, "int8": torch.int8,
-           "uint8": torch.uint8, "int16": torch.int16, "bool": torch.bool}[dtype.name]
     if missing:
         fv = decode_fill_value(meta.get("fill_value"), dtype)  # the host reader's decoding; no fill value: NaN for floats, else 0
         if fv is None:
@@ -266,6 +289,8 @@ def read_array_to_device(path: str, eng, lead: int | None = None):
         typed = out.view(tdt)
         for e0, e1 in missing:
             typed[e0:e1] = fv
+    for b0, payload in copied:
+        out[b0: b0 + len(payload)] = torch.frombuffer(bytearray(payload), dtype=torch.uint8).to(dev)
     if not s_src:
         return out.view(tdt).reshape((T,) + shape[1:])
     comp_d = torch.frombuffer(bytearray(b"".join(blobs)), dtype=torch.uint8).to(dev)
