@@ -373,6 +373,29 @@ int marex_label2d_i32(marex_ctx* ctx, const uint8_t* data, int64_t T, int ny, in
 int marex_label3d_i32(marex_ctx* ctx, const uint8_t* data, int64_t T, int ny, int nx, int wrap_x, int connect_t, int32_t* ids,
                       int32_t* areas, int32_t* n_out);
 
+/* Labelling in time blocks, for fields of 2^31 - 1 cells and more (marex_label3d_i32 takes fewer): the caller labels
+ * contiguous blocks of timesteps with marex_label3d_i32 into the slices of one ids[T][ny * nx], block k giving local IDs
+ * 1..n_k; its provisional global IDs are off_k + local, off_k = n_0 + ... + n_{k-1}, N_prov = the sum (at most 2^31 - 2).
+ * table: int32 [table_len = N_prov + 1], table[g] = g on entry (entry 0 = background) -- a parent array over the
+ * provisional IDs.
+ *
+ * marex_label_seam_union_i32: one seam.  prev_ids = the last slice of block k, next_ids = the first slice of block k+1
+ *   (int32 [ny * nx] each, still local IDs); every cell of next_ids unions its ID with those of its up to nine
+ *   neighbours in prev_ids (3 x 3 in (y, x), x periodic when wrap_x), the larger root hooked under the smaller.
+ *   Not called with connect_t = 0.  IDs outside 1..n_prev / 1..n_next are ignored.
+ * marex_label_table_resolve_i32: after all seams.  table[g] becomes the final ID of provisional ID g: 1 + the number of
+ *   roots (smallest provisional ID of an event) below g's root, table[0] = 0 -- the numbering of one labelling call over
+ *   the whole field.  prov_areas: int32 [n_prov], cells of provisional ID g at g - 1 (the blocks' areas, concatenated);
+ *   areas: int64 [n_prov], areas[id - 1] = cells of final ID id, the first *n_out entries meaningful; *n_out = N.
+ * marex_label_apply_table_i32: ids[i] = ids[i] > 0 ? table[off + ids[i]] : 0 in place over the n cells of one block
+ *   (off = off_k; n < 2^31 - 1).
+ * All three are asynchronous on the context's stream. */
+int marex_label_seam_union_i32(marex_ctx* ctx, const int32_t* prev_ids, const int32_t* next_ids, int ny, int nx, int wrap_x,
+                               int off_prev, int n_prev, int off_next, int n_next, int32_t* table, int64_t table_len);
+int marex_label_table_resolve_i32(marex_ctx* ctx, int32_t* table, int64_t n_prov, const int32_t* prov_areas, int64_t* areas,
+                                  int32_t* n_out);
+int marex_label_apply_table_i32(marex_ctx* ctx, int32_t* ids, int64_t n, const int32_t* table, int64_t table_len, int off);
+
 /* out[i] = labels[i] > 0 && labels[i] != drop_label && areas[labels[i] - 1] >= area_threshold (track.py:1891-1903;
  * drop_label = the reference's `object_ids_keep[0] = -1`, which removes the first object of the list) */
 int marex_filter_by_area_u8(marex_ctx* ctx, const int32_t* labels, const int32_t* areas, int64_t n,

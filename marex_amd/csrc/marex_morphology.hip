@@ -587,6 +587,171 @@ extern "C" int marex_label3d_i32(marex_ctx* ctx, const uint8_t* data, int64_t T,
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Labelling in time blocks (fields of 2^31 - 1 cells and more): every block of timesteps is labelled on its own by
+// marex_label3d_i32 (local IDs 1..n_k by first cell inside the block), block k's provisional global IDs are
+// off_k + local with off_k = n_0 + ... + n_{k-1} -- already the global first-cell order, because every cell of block k
+// precedes every cell of block k+1 -- and the seams are stitched at OBJECT level: a parent table over the provisional
+// IDs (entry 0 = background, a root of its own), the same hook-to-the-smaller-root union-find as the cells', so that a
+// root is the smallest provisional ID of its event = the one whose first cell comes first.  Ranking the roots of the
+// table then is the single call's numbering (dask_image.ndmeasure.label does the same on the host: block labels offset
+// in time order, joined through connected components of the seam pairs).
+// ------------------------------------------------------------------------------------------------
+// One thread per cell of the later slice (`next`, first step of block k+1): it looks at its up to nine neighbours in the
+// earlier slice (`prev`, last step of block k), 3 x 3 in (y, x), x periodic with wrap_x.  Shared addresses: a lane
+// skips a neighbour that repeats its previous one, and the lanes of a wave that hold the same (earlier, later) pair
+// send ONE union (ballot, as in k_ccl_relabel); a pair that is already joined costs two finds and no atomic.  IDs
+// outside 1..n_prev / 1..n_next count as background, so no table access can leave [0, off_next + n_next].
+__global__ void __launch_bounds__(256)
+k_seam_union(const int* __restrict__ prev, const int* __restrict__ next, int ny, int nx, int wrap_x, int off_prev,
+             int n_prev, int off_next, int n_next, int* __restrict__ table) {
+    const long C = (long)ny * nx;
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const bool wrap = wrap_x && nx > 1;
+    int b = 0, x = 0, y = 0;
+    if (i < C) {
+        const int v = next[i];
+        if (v > 0 && v <= n_next) b = off_next + v;
+        x = (int)(i % nx);
+        y = (int)(i / nx);
+    }
+    int last = 0;
+    for (int d = 0; d < 9; ++d) {  // uniform trip count: every lane takes part in the ballots
+        int a = 0;
+        if (b) {
+            const int yy = y + d / 3 - 1;
+            int xx = x + d % 3 - 1;
+            bool ok = yy >= 0 && yy < ny;
+            if (xx < 0) {
+                ok = ok && wrap;
+                xx += nx;
+            } else if (xx >= nx) {
+                ok = ok && wrap;
+                xx -= nx;
+            }
+            if (ok) {
+                const int p = prev[(long)yy * nx + xx];
+                if (p > 0 && p <= n_prev) a = off_prev + p;
+            }
+            if (a == last) a = 0;
+            else if (a) last = a;
+        }
+        unsigned long long todo = __ballot(a != 0);
+        while (todo) {
+            const int lead = __ffsll((long long)todo) - 1;
+            const int al = __shfl(a, lead, 64), bl = __shfl(b, lead, 64);
+            const unsigned long long same = __ballot(a == al && b == bl) & todo;
+            if (lane == lead) uf_union(table, al, bl);
+            todo &= ~same;
+        }
+    }
+}
+
+// table[g] = final ID of provisional ID g (rank[] holds, at the roots, the number of roots before them -- entry 0
+// included, so that it IS the 1-based final ID and final[0] = 0); each thread rewrites only its own entry.  The block
+// areas fold into the events' areas in int64: one event of such a field may exceed 2^31 cells.
+__global__ void __launch_bounds__(256)
+k_table_final(long len, const int* __restrict__ rank, const int* __restrict__ n_roots, int* __restrict__ table,
+              const int* __restrict__ prov_areas, unsigned long long* __restrict__ areas, int* __restrict__ n_out) {
+    const long g = (long)blockIdx.x * 256 + threadIdx.x;
+    if (g >= len) return;
+    if (g == 0) *n_out = *n_roots - 1;  // the background entry is a root too
+    const int f = rank[table[g]];
+    table[g] = f;
+    if (g > 0 && f > 0) atomicAdd(&areas[f - 1], (unsigned long long)prov_areas[g - 1]);
+}
+
+// ids[i] = ids[i] > 0 ? table[off + ids[i]] : 0 in place: 16 bytes per thread where the slice allows it, the `head`
+// elements before the first 16-byte boundary and the rest behind the last full vector one by one
+__device__ __forceinline__ int table_map(const int* __restrict__ table, long table_len, int off, int v) {
+    const long g = (long)off + v;
+    return (v > 0 && g < table_len) ? table[g] : 0;
+}
+
+__global__ void __launch_bounds__(256)
+k_label_apply(int* __restrict__ ids, long n, int head, const int* __restrict__ table, long table_len, int off) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    const long nvec = (n - head) / 4;
+    if (idx < nvec) {
+        int4* p = reinterpret_cast<int4*>(ids + head) + idx;
+        int4 v = *p;
+        v.x = table_map(table, table_len, off, v.x);
+        v.y = table_map(table, table_len, off, v.y);
+        v.z = table_map(table, table_len, off, v.z);
+        v.w = table_map(table, table_len, off, v.w);
+        *p = v;
+        return;
+    }
+    const long j = idx - nvec;
+    const long e = j < head ? j : head + 4 * nvec + (j - head);
+    if (e < n) ids[e] = table_map(table, table_len, off, ids[e]);
+}
+
+extern "C" int marex_label_seam_union_i32(marex_ctx* ctx, const int32_t* prev_ids, const int32_t* next_ids, int ny, int nx,
+                                          int wrap_x, int off_prev, int n_prev, int off_next, int n_next, int32_t* table,
+                                          int64_t table_len) {
+    if (!ctx) return -1;
+    if (!prev_ids || !next_ids || !table || ny <= 0 || nx <= 0) return fail(ctx, -1, "marex_label_seam_union_i32: null pointer or empty shape");
+    if ((long)ny * nx >= 2147483647L) return fail(ctx, -4, "marex_label_seam_union_i32: a slice of 2^31 - 1 cells or more");
+    if (off_prev < 0 || n_prev < 0 || off_next < 0 || n_next < 0 || (long)off_prev + n_prev >= table_len ||
+        (long)off_next + n_next >= table_len || table_len > 2147483647L)
+        return fail(ctx, -4, "marex_label_seam_union_i32: ID ranges outside the table (off + n must stay below table_len <= 2^31 - 1)");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    LaunchTimer lt(ctx, MAREX_K_MORPH);
+    const long C = (long)ny * nx;
+    hipLaunchKernelGGL(k_seam_union, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, ctx->stream, prev_ids, next_ids, ny, nx,
+                       wrap_x, off_prev, n_prev, off_next, n_next, table);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
+extern "C" int marex_label_table_resolve_i32(marex_ctx* ctx, int32_t* table, int64_t n_prov, const int32_t* prov_areas,
+                                             int64_t* areas, int32_t* n_out) {
+    if (!ctx) return -1;
+    if (!table || !prov_areas || !areas || !n_out || n_prov <= 0) return fail(ctx, -1, "marex_label_table_resolve_i32: null pointer or empty table");
+    if (n_prov > 2147483646L) return fail(ctx, -4, "marex_label_table_resolve_i32: more than 2^31 - 2 provisional objects");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    LaunchTimer lt(ctx, MAREX_K_MORPH);
+    const long len = (long)n_prov + 1;  // entry 0 = background
+    const unsigned g = (unsigned)((len + 255) / 256);
+    const long ntiles = (len + CCL_TILE - 1) / CCL_TILE;
+    // scratch: rank [len] (written at the roots only), tile counts and offsets [ntiles] each, the number of roots
+    if (int rc = ensure_scratch(ctx, (size_t)(len + 2 * ntiles + 1) * sizeof(int))) return rc;
+    int* rank = reinterpret_cast<int*>(ctx->morph_scratch);
+    int* tile_cnt = rank + len;
+    int* tile_off = tile_cnt + ntiles;
+    int* n_roots = tile_off + ntiles;
+    HIP_TRY(ctx, hipMemsetAsync(areas, 0, (size_t)n_prov * sizeof(int64_t), ctx->stream));
+    hipLaunchKernelGGL(k_ccl_compress, dim3(g), dim3(256), 0, ctx->stream, len, table);
+    hipLaunchKernelGGL(k_ccl_roots<false>, dim3((unsigned)ntiles), dim3(256), 0, ctx->stream, table, len, tile_off, tile_cnt, rank);
+    hipLaunchKernelGGL(k_ccl_scan_tiles, dim3(1), dim3(1024), 0, ctx->stream, tile_cnt, ntiles, tile_off, n_roots);
+    hipLaunchKernelGGL(k_ccl_roots<true>, dim3((unsigned)ntiles), dim3(256), 0, ctx->stream, table, len, tile_off, tile_cnt, rank);
+    hipLaunchKernelGGL(k_table_final, dim3(g), dim3(256), 0, ctx->stream, len, rank, n_roots, table, prov_areas,
+                       reinterpret_cast<unsigned long long*>(areas), n_out);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
+extern "C" int marex_label_apply_table_i32(marex_ctx* ctx, int32_t* ids, int64_t n, const int32_t* table, int64_t table_len,
+                                           int off) {
+    if (!ctx) return -1;
+    if (!ids || !table || n <= 0 || table_len <= 0) return fail(ctx, -1, "marex_label_apply_table_i32: null pointer or empty shape");
+    if (n >= 2147483647L) return fail(ctx, -4, "marex_label_apply_table_i32: a block of 2^31 - 1 cells or more");
+    if (off < 0 || off >= table_len || table_len > 2147483647L) return fail(ctx, -4, "marex_label_apply_table_i32: offset outside the table");
+    if ((uintptr_t)ids & 3) return fail(ctx, -4, "marex_label_apply_table_i32: ids must be 4-byte aligned");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    LaunchTimer lt(ctx, MAREX_K_MORPH);
+    long head = (long)(((16 - ((uintptr_t)ids & 15)) & 15) / 4);  // elements before the first 16-byte boundary
+    if (head > n) head = n;
+    const long nvec = (n - head) / 4;
+    const long threads = nvec + head + (n - head - 4 * nvec);
+    hipLaunchKernelGGL(k_label_apply, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream, ids, (long)n, (int)head,
+                       table, (long)table_len, off);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
 extern "C" int marex_filter_by_area_u8(marex_ctx* ctx, const int32_t* labels, const int32_t* areas, int64_t n,
                                        double area_threshold, int drop_label, uint8_t* out) {
     if (!ctx) return -1;

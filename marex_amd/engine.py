@@ -10,7 +10,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
-from typing import Dict, Optional
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -18,7 +18,7 @@ import torch
 from . import _lib
 from .binning import BinTable
 from .calendar import N_DOY, CalendarPlan
-from .exceptions import ConfigurationError, ProcessingError
+from .exceptions import ConfigurationError, ProcessingError, TrackingError
 
 
 import logging
@@ -43,6 +43,27 @@ def shifting_kernel_family(W: int, S: int, C: int, lists: bool) -> str:
     if S == 21 and W in (5, 15) and C >= 4 and C % 4 == 0:
         return "lean"
     return "fast" if fast else "general"
+
+
+#: cells one marex_label3d_i32 call takes (int32 parents, 2^31 - 1 refused): the default and the largest labelling block
+LABEL_BLOCK_CELLS = 2**31 - 2
+
+
+def plan_time_blocks(T: int, C: int, max_block_cells: Optional[int] = None) -> List[Tuple[int, int]]:
+    """Contiguous time blocks ``[(t0, t1), ...]`` covering ``[0, T)`` for the blocked labelling of a ``[T, C]`` field:
+    every block holds as many whole timesteps as fit ``max_block_cells`` cells (default and upper limit 2^31 - 2), the
+    last one what remains.  :class:`TrackingError` when a single timestep does not fit.  Needs no GPU."""
+    T, C = int(T), int(C)
+    if T <= 0 or C <= 0:
+        raise TrackingError(f"cannot plan labelling blocks for an empty field ({T} steps of {C} cells)")
+    if max_block_cells is not None and int(max_block_cells) <= 0:
+        raise TrackingError(f"max_block_cells must be positive, got {max_block_cells}")
+    limit = LABEL_BLOCK_CELLS if max_block_cells is None else min(int(max_block_cells), LABEL_BLOCK_CELLS)
+    if C > limit:
+        raise TrackingError(f"one timestep of {C} cells exceeds the labelling block of {limit} cells",
+                            details="a block is at least one timestep; a single slice must stay below 2^31 - 1 cells")
+    steps = limit // C
+    return [(t0, min(T, t0 + steps)) for t0 in range(0, T, steps)]
 
 
 def _key_to_float(key: int) -> float:
@@ -684,17 +705,65 @@ class HotPath:
         return {"labels": labels, "areas": areas}
 
     def label_objects_3d(self, data_bin: torch.Tensor, ny: int, nx: int, wrap_x: bool = True, connect_t: bool = True,
-                         wsp: Optional[dict] = None) -> Dict[str, torch.Tensor]:
+                         wsp: Optional[dict] = None, max_block_cells: Optional[int] = None) -> Dict[str, torch.Tensor]:
         """26-connected components in (time, y, x) (track.py:2006-2048, ``time_connectivity=True``; ``connect_t=False``:
         one labelling per timestep).  ``ids`` int32 ``[T, C]``: IDs 1..N numbered by the component's first cell in C order,
-        0 = background; ``areas`` int32 (cells of ID ``k`` at ``k - 1``, the first N entries); ``n`` int32 ``[1]`` = N."""
+        0 = background; ``areas`` int32 (cells of ID ``k`` at ``k - 1``, the first N entries); ``n`` int32 ``[1]`` = N.
+
+        A field of more than 2^31 - 2 cells, or any field when ``max_block_cells`` is given, is labelled in time blocks
+        of at most that many cells (:func:`plan_time_blocks`) and stitched across the seams: the same ``ids`` and ``n``
+        as one call would give, ``areas`` int64 ``[N]`` (one event may exceed 2^31 cells there).  Refused with
+        :class:`TrackingError`: a single slice of 2^31 - 1 cells or more, more than 2^31 - 2 objects before stitching."""
         T, Cn = data_bin.shape
         assert Cn == ny * nx
+        if max_block_cells is not None or T * Cn > LABEL_BLOCK_CELLS:
+            return self._label_objects_3d_blocked(data_bin, ny, nx, wrap_x, connect_t, wsp, max_block_cells)
         ids = self._buf(wsp, "ids3d", (T, Cn), torch.int32, self.device)
         areas = self._buf(wsp, "areas3d", (T * Cn,), torch.int32, self.device)
         n = self._buf(wsp, "n3d", (1,), torch.int32, self.device)
         self.call("marex_label3d_i32", data_bin, T, int(ny), int(nx), int(bool(wrap_x)), int(bool(connect_t)), ids, areas, n)
         return {"ids": ids, "areas": areas, "n": n}
+
+    def _label_objects_3d_blocked(self, data_bin: torch.Tensor, ny: int, nx: int, wrap_x: bool, connect_t: bool,
+                                  wsp: Optional[dict], max_block_cells: Optional[int]) -> Dict[str, torch.Tensor]:
+        """:meth:`label_objects_3d` in time blocks: label every block into its slice of ``ids``,
+        stitch the seams in a parent table over the provisional IDs, rank its roots, map every block through the table.
+        The scratch (the blocks' int32 areas here, the rank array inside the library) has the size of the largest
+        block; one host read of ``n_k`` per block sizes the table."""
+        T, Cn = data_bin.shape
+        blocks = plan_time_blocks(T, Cn, max_block_cells)
+        ids = self._buf(wsp, "ids3d", (T, Cn), torch.int32, self.device)
+        areas_blk = self._buf(wsp, "areas3d_block", (max(b - a for a, b in blocks) * Cn,), torch.int32, self.device)
+        n = self._buf(wsp, "n3d", (1,), torch.int32, self.device)
+        wrap, ct = int(bool(wrap_x)), int(bool(connect_t))
+        offs, counts, parts = [], [], []
+        n_prov = 0
+        for t0, t1 in blocks:
+            self.call("marex_label3d_i32", data_bin[t0:t1], t1 - t0, int(ny), int(nx), wrap, ct, ids[t0:t1], areas_blk, n)
+            nk = int(n.item())
+            offs.append(n_prov)
+            counts.append(nk)
+            parts.append(areas_blk[:nk].clone())  # the next block overwrites areas_blk
+            n_prov += nk
+            if n_prov > LABEL_BLOCK_CELLS:
+                raise TrackingError(f"more than 2^31 - 2 provisional objects ({n_prov} after the block of steps {t0}..{t1 - 1})",
+                                    details="block labels are int32; smaller blocks do not help, the field has too many objects")
+        if n_prov == 0:  # nothing set anywhere: ids is all background already
+            return {"ids": ids, "areas": torch.zeros((0,), dtype=torch.int64, device=self.device), "n": n}
+        table = torch.arange(n_prov + 1, dtype=torch.int32, device=self.device)
+        if ct:
+            for k in range(len(blocks) - 1):
+                if counts[k] and counts[k + 1]:  # an empty block has no ID to join
+                    seam = blocks[k][1]
+                    self.call("marex_label_seam_union_i32", ids[seam - 1], ids[seam], int(ny), int(nx), wrap, offs[k], counts[k],
+                              offs[k + 1], counts[k + 1], table, n_prov + 1)
+        areas = self._buf(wsp, "areas3d_i64", (n_prov,), torch.int64, self.device)
+        self.call("marex_label_table_resolve_i32", table, n_prov, torch.cat(parts), areas, n)
+        # block 0 goes through the table too: two of its events joined only through block 1 collapse into the smaller ID
+        for (t0, t1), off, nk in zip(blocks, offs, counts):
+            if nk:
+                self.call("marex_label_apply_table_i32", ids[t0:t1], (t1 - t0) * Cn, table, n_prov + 1, off)
+        return {"ids": ids, "areas": areas[:int(n.item())], "n": n}
 
     # ------------------------------------------------------------------ object properties and overlaps (track.py:2109-2504)
     def ids_minmax(self, ids: torch.Tensor) -> tuple:

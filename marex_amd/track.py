@@ -19,13 +19,55 @@ from .exceptions import ConfigurationError, ProcessingError, TrackingError, crea
 
 logger = logging.getLogger("marex_amd")
 
-#: cells of one labelling (int32 parents; the limit of the 2-D labeller too)
+#: cells of one labelling call (int32 parents; the limit of the 2-D labeller too) and of a field under merge tracking
 MAX_CELLS = 2**31 - 1
 
 #: regionprops names calculate_object_properties computes on the device
 SUPPORTED_PROPERTIES = ("label", "area", "centroid")
 
 _I32_MAX = 2**31 - 1
+
+#: ID fields of at least this many bytes come to the host through pinned staging buffers
+PINNED_ID_FIELD_BYTES = 256 << 20
+
+#: cells of one labelling block (engine.LABEL_BLOCK_CELLS; repeated here so that this module imports without torch)
+_BLOCK_CELLS = 2**31 - 2
+
+
+def labelling_memory_need(T: int, C: int, max_block_cells: Optional[int] = None, resident: bool = False) -> Dict[str, int]:
+    """Bytes of the device buffers ``HotPath.label_objects_3d`` holds for a ``[T, C]`` field, by name: the uint8 mask
+    (unless it is ``resident`` already), the int32 ID field, the int32 areas of one call (of the largest block on the
+    blocked path) and the library's rank scratch of the same size.  The object-level tables of the blocked path
+    (12 bytes per provisional object) are not known before labelling and are left out."""
+    n = int(T) * int(C)
+    blocked = max_block_cells is not None or n > _BLOCK_CELLS
+    limit = _BLOCK_CELLS if max_block_cells is None else min(int(max_block_cells), _BLOCK_CELLS)
+    blk = min(n, max(1, limit // int(C)) * int(C)) if blocked else n
+    need = {} if resident else {"mask uint8": n}
+    need.update({"ID field int32": 4 * n, "areas int32 (one block)": 4 * blk, "rank scratch int32 (one block)": 4 * blk})
+    return need
+
+
+def tracking_memory_need(T: int, ny: int, nx: int, R_fill: int, T_fill: int, resident: bool = False) -> Dict[str, int]:
+    """Bytes of the ``[T, C]`` device buffers alive at the peak of ``tracker(allow_merging=False).run()``, by name.  The
+    peak is inside ``filter_small_objects`` at the end of ``run_preprocess``: the input mask, the hole-filled mask, the
+    gap-filled mask (``T_fill > 0``), the int32 labels and areas of the per-timestep labelling (8 bytes per cell) and the
+    filtered mask, torch's temporaries while it selects the non-zero areas of one labelling block (4 bytes per cell of the
+    block, as measured: DESIGN.md section 4), plus the library's scratch at its largest -- the bit-packed padded images of
+    ``fill_holes`` or the int32 copy of one labelling block.  The labelling that follows holds less (:func:`labelling_memory_need`, with the
+    ID field reusing what the pre-processing released: mask + 4 n + 8 bytes per cell of a block against at least 11 n + 4 per
+    cell of a block here), so a run that passes this check fits."""
+    n = int(T) * int(ny) * int(nx)
+    R = int(R_fill)
+    packed = 16 * int(T) * (ny + 4 * R) * ((nx + 4 * R + 63) // 64) if R > 0 else 0
+    need = {} if resident else {"mask uint8": n}
+    need["hole-filled mask uint8"] = n
+    if int(T_fill) > 0:
+        need["gap-filled mask uint8"] = n
+    need.update({"2-D labels int32": 4 * n, "2-D areas int32": 4 * n, "filtered mask uint8": n,
+                 "area selection temporaries": 4 * min(n, _BLOCK_CELLS),
+                 "library scratch": max(packed, 4 * min(n, _BLOCK_CELLS))})
+    return need
 
 
 def _tensor_of(da):
@@ -181,6 +223,15 @@ class tracker:  # noqa: N801 -- the reference's public name (marEx.tracker)
     :meth:`find_overlapping_objects`, :meth:`enforce_overlap_threshold`, :meth:`consolidate_object_ids`,
     :meth:`split_and_merge_objects`, :meth:`cluster_rename_objects_and_props` and :meth:`track_objects`, on the device.
 
+    Size limits.  One labelling call takes fewer than 2^31 - 1 cells; a longer record is labelled in blocks of timesteps
+    of at most 2^31 - 2 cells each, and the objects are joined across the seams on the device, so that ``ID_field`` is what
+    one labelling of the whole field would give.  ``label_block_steps`` forces the block length in timesteps (for tests,
+    and for less scratch memory: the labelling's work buffers have the size of one block).  This holds for
+    ``allow_merging=False`` and :meth:`identify_objects`.  :class:`TrackingError` is raised for a single timestep of
+    2^31 - 1 cells or more, for more than 2^31 - 2 objects before the seams are joined, when the buffers of the run
+    (:func:`tracking_memory_need`, about 12 bytes per cell) exceed the free device memory -- before anything is allocated,
+    with both numbers -- and by merge tracking (``allow_merging=True``) for fields of 2^31 - 1 cells and more.
+
     ``data_bin`` may be device resident -- a DataArray whose data is a torch tensor (bool or uint8) on the GPU, e.g. from
     ``zarr_io.open_dataarray_device`` -- and is then consumed without a host round trip.  ``device`` picks the GPU.
     """
@@ -212,8 +263,14 @@ class tracker:  # noqa: N801 -- the reference's public name (marEx.tracker)
         coordinate_units: Optional[Literal["degrees", "radians"]] = None,
         device: int = 0,
         timechunks: Optional[int] = None,
+        label_block_steps: Optional[int] = None,
     ) -> None:
         supported = "gridded data without checkpointing"
+        if label_block_steps is not None and (isinstance(label_block_steps, bool) or not isinstance(label_block_steps, (int, np.integer))
+                                              or label_block_steps <= 0):
+            raise ConfigurationError("label_block_steps must be a positive number of timesteps",
+                                     details=f"label_block_steps={label_block_steps!r}")
+        self.label_block_steps = None if label_block_steps is None else int(label_block_steps)
         self._time_chunks = None
         if allow_merging and not unstructured_grid:
             # merge results depend on the time chunks the per-timestep loop walks (track.py:3379-3382, 3602-3615)
@@ -375,9 +432,48 @@ class tracker:  # noqa: N801 -- the reference's public name (marEx.tracker)
     def _check_size(shape) -> None:
         n = int(np.prod([int(k) for k in shape]))
         if n >= MAX_CELLS:
-            raise TrackingError("more than 2^31 - 1 cells; label the series in time blocks",
-                                details=f"{n} cells: the device labelling holds one int32 parent per cell; time-blocked "
-                                        "labelling with seam stitching is not built")
+            raise TrackingError("more than 2^31 - 1 cells: merge tracking (allow_merging=True) is not built for such fields",
+                                details=f"{n} cells: its dense (timestep, object) tables and slice tables are int32-indexed; "
+                                        "allow_merging=False and identify_objects label such a field in time blocks")
+
+    def _perm_of(self, da):
+        """Axis order that brings ``da`` to (time, y, x), as :meth:`_device_u8` applies it."""
+        dims = tuple(getattr(da, "dims", self._out_dims()))
+        return tuple(dims.index(k) for k in self._out_dims()) if set(dims) == set(self._out_dims()) else (0, 1, 2)
+
+    @staticmethod
+    def _check_fits(eng, need: Dict[str, int], what: str) -> None:
+        """:class:`TrackingError` with both numbers when the ``[T, C]`` buffers of ``need`` (name -> bytes) exceed the free
+        device memory -- what the driver reports free plus what torch's allocator holds cached -- instead of a torch
+        out-of-memory error half way through."""
+        import torch
+
+        free, _ = torch.cuda.mem_get_info(eng.device)
+        free += torch.cuda.memory_reserved(eng.device) - torch.cuda.memory_allocated(eng.device)
+        total = sum(need.values())
+        if total > free:
+            raise TrackingError(f"{what}: needs {total / 1e9:.3f} GB of device memory, {free / 1e9:.3f} GB are free",
+                                details="; ".join(f"{k} {v / 1e9:.3f} GB" for k, v in need.items()),
+                                suggestions=["Track a shorter record", "Free device memory held by other arrays"])
+
+    def _check_memory(self, shape) -> None:
+        """The basic tracker's buffers at their peak against the free device memory."""
+        T, ny, nx = (int(shape[k]) for k in self._perm)
+        need = tracking_memory_need(T, ny, nx, self.R_fill, self.T_fill, resident=_tensor_of(self.data_bin) is not None)
+        self._check_fits(self._engine(), need, "tracker.run")
+
+    @staticmethod
+    def _ids_to_host(eng, ids) -> np.ndarray:
+        """The int32 ``[T, C]`` ID field as a NumPy array; a large one goes through the engine's pinned staging buffers
+        (marex_amd/transfer.py) instead of one pageable copy."""
+        if ids.numel() * 4 < PINNED_ID_FIELD_BYTES:
+            return ids.cpu().numpy()
+        from .detect import _pipe
+
+        out = np.empty(tuple(ids.shape), dtype=np.int32)
+        eng.sync()
+        _pipe(eng).download(ids, out)
+        return out
 
     # ------------------------------------------------------------------ device plumbing
     def _engine(self):
@@ -420,7 +516,10 @@ class tracker:  # noqa: N801 -- the reference's public name (marEx.tracker)
     def run(self, return_merges: bool = False, checkpoint: Optional[str] = None):
         """``run_preprocess`` -> ``run_tracking`` -> ``run_stats_attributes``; returns the events Dataset, and with
         ``return_merges`` and merging also the merge events: ``(events_ds, merges_ds)`` (track.py:1162-1232)."""
-        self._check_size(self.data_bin.shape)
+        if self.allow_merging:
+            self._check_size(self.data_bin.shape)
+        else:
+            self._check_memory(self.data_bin.shape)
         data_bin_preprocessed, object_stats = self.run_preprocess(checkpoint=checkpoint)
         events_ds, merges_ds, N_events_final = self.run_tracking(data_bin_preprocessed)
         events_ds = self.run_stats_attributes(events_ds, merges_ds, object_stats, N_events_final)
@@ -452,11 +551,15 @@ class tracker:  # noqa: N801 -- the reference's public name (marEx.tracker)
         ``(ID_field int32, None, N_objects)``; IDs 1..N by first cell in C order, unique across time either way."""
         from .xr_compat import DataArray
 
-        self._check_size(data_bin.shape)
         eng = self._engine()
+        T, ny, nx = (int(data_bin.shape[k]) for k in self._perm_of(data_bin))
+        block = None if self.label_block_steps is None else self.label_block_steps * ny * nx
+        need = labelling_memory_need(T, ny * nx, block, resident=_tensor_of(data_bin) is not None)
+        self._check_fits(eng, need, "identify_objects")
         x, T, ny, nx = self._device_u8(data_bin, eng)
-        r = eng.label_objects_3d(x, ny, nx, wrap_x=not self.regional_mode, connect_t=bool(time_connectivity))
-        ids = r["ids"].cpu().numpy().reshape(T, ny, nx)
+        r = eng.label_objects_3d(x, ny, nx, wrap_x=not self.regional_mode, connect_t=bool(time_connectivity),
+                                 max_block_cells=block)
+        ids = self._ids_to_host(eng, r["ids"]).reshape(T, ny, nx)
         N = int(r["n"].item())
         da = DataArray(ids, dims=self._out_dims(), coords={self.timedim: (self.timedim, self.time_values)}, name="ID_field")
         return da, None, N
@@ -1076,6 +1179,7 @@ class tracker:  # noqa: N801 -- the reference's public name (marEx.tracker)
         N_events)``."""
         import time
 
+        self._check_size(data_bin.shape)  # merge tracking keeps refusing fields of 2^31 - 1 cells and more
         eng = self._engine()
         st = self._stage_times = {}
         t0 = time.perf_counter()
