@@ -482,6 +482,42 @@ int marex_overlap_count_i32(marex_ctx* ctx, const int32_t* ids, int64_t T, int64
 int marex_overlap_pairs_i32(marex_ctx* ctx, const int32_t* ids, int64_t T, int64_t C, int64_t cap, uint64_t* keys,
                             uint64_t* counts, uint64_t* stats, int64_t out_cap, uint64_t* out_keys, uint64_t* out_counts);
 
+/* The same object stages on an unstructured mesh (marEx/track.py:1947-2005, 2135-2323, 2431-2439, 1513-1514, 2762-2764),
+ * area weighted in fixed point.  q: int64 [4][C], row-major: q[0][c] = rint(area * 2^e), q[1..3][c] = rint(area * x, y, z
+ * * 2^e) with (x, y, z) the unit vector of cell c; the host picks e so that |sum over c of any row| < 2^62
+ * (marex_amd.track.mesh_weight_tables).  The device adds these integers with 64-bit integer atomics only: results are
+ * bitwise reproducible and independent of the launch shape.  ids: int32 [T][C], values <= 0 are background; C and T
+ * below 2^31 - 1.
+ *
+ * marex_label_mesh_rank_i32: labels [T][C] of marex_label_mesh_i32 (1 + smallest linear index of the component in this
+ *   [T][C] block, T * C < 2^31 - 1) -> ids[t][c] = the rank of the cell's component among the components of timestep t
+ *   by smallest cell index, 1 .. n_t[t] (scipy.sparse.csgraph.connected_components order, track.py:1979-1982), 0 for
+ *   background; n_t: int32 [T].  rank: int32 [T * C] work (only root cells are written and read; the areas array of
+ *   marex_label_mesh_i32 may be given).  ids may be labels (in place).
+ * marex_ids_row_max_i32: rowmax[t] = max(0, max over c of ids[t][c]), int32 [T].
+ * marex_ids_add_row_offset_i32: out[t][c] = ids[t][c] > 0 ? ids[t][c] + off[t] : 0 (off: int32 [T]; the caller makes sure
+ *   the sums fit int32); out may be ids.  Together: the IDs made unique in time of track.py:2762-2764.
+ * marex_mesh_object_moments_i64: slots as in marex_object_spans_i32; acc[slot][0] = cells, acc[slot][1..4] = sums of
+ *   q[0..3][c] over the cells of the slot (two's complement); acc [n_slots][5] is zeroed first; marex_object_compact
+ *   lists the non-empty slots.
+ * marex_mesh_overlap_pairs_i64: marex_overlap_pairs_i32 with the sum of q0[c] (= q[0]) over the cells of the pair in
+ *   place of their number; marex_overlap_count_i32 sizes the table (stats as there).  A pair met in many timesteps can
+ *   exceed 64 bits, so a sum is two words: sums [cap][2] and out_sums [out_cap][2], the pair's sum = word 1 * 2^32 + word 0
+ *   (word 0 collects the low 32 bits of the partial sums and may itself exceed 2^32).
+ * marex_mesh_area_i64: out[t] = sum over c of data[t][c] != 0 ? q0[c] : 0, data uint8 [T][C]; out uint64 [T], zeroed
+ *   first.
+ * All are asynchronous on the context's stream. */
+int marex_label_mesh_rank_i32(marex_ctx* ctx, const int32_t* labels, int64_t T, int64_t C, int32_t* rank, int32_t* ids,
+                              int32_t* n_t);
+int marex_ids_row_max_i32(marex_ctx* ctx, const int32_t* ids, int64_t T, int64_t C, int32_t* rowmax);
+int marex_ids_add_row_offset_i32(marex_ctx* ctx, const int32_t* ids, int64_t T, int64_t C, const int32_t* off, int32_t* out);
+int marex_mesh_object_moments_i64(marex_ctx* ctx, const int32_t* ids, int64_t T, int64_t C, const int64_t* q,
+                                  const int32_t* tmin, const int64_t* off, int64_t n_slots, uint64_t* acc);
+int marex_mesh_overlap_pairs_i64(marex_ctx* ctx, const int32_t* ids, int64_t T, int64_t C, const int64_t* q0, int64_t cap,
+                                 uint64_t* keys, uint64_t* sums, uint64_t* stats, int64_t out_cap, uint64_t* out_keys,
+                                 uint64_t* out_sums);
+int marex_mesh_area_i64(marex_ctx* ctx, const uint8_t* data, int64_t T, int64_t C, const int64_t* q0, uint64_t* out);
+
 /* Stages of the merge tracker on grids (tracker.split_and_merge_objects / consolidate_object_ids /
  * cluster_rename_objects_and_props, marEx/track.py:2554-3802).  Slices are int32 [ny][nx], fields int32 [T][ny][nx];
  * values <= 0 are background.  Distances are float64 sqrt(dy * dy + dx * dx), dx wrapped by +-nx when |dx| > nx / 2 and

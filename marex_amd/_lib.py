@@ -97,6 +97,12 @@ PROTOTYPES = {
     "marex_object_compact": (_i32, [_p, _i64, _i32, _p, _p, _p, _p, _p, _p]),
     "marex_overlap_count_i32": (_i32, [_p, _p, _i64, _i64, _p]),
     "marex_overlap_pairs_i32": (_i32, [_p, _p, _i64, _i64, _i64, _p, _p, _p, _i64, _p, _p]),
+    "marex_label_mesh_rank_i32": (_i32, [_p, _p, _i64, _i64, _p, _p, _p]),
+    "marex_ids_row_max_i32": (_i32, [_p, _p, _i64, _i64, _p]),
+    "marex_ids_add_row_offset_i32": (_i32, [_p, _p, _i64, _i64, _p, _p]),
+    "marex_mesh_object_moments_i64": (_i32, [_p, _p, _i64, _i64, _p, _p, _p, _i64, _p]),
+    "marex_mesh_overlap_pairs_i64": (_i32, [_p, _p, _i64, _i64, _p, _i64, _p, _p, _p, _i64, _p, _p]),
+    "marex_mesh_area_i64": (_i32, [_p, _p, _i64, _i64, _p, _p]),
     "marex_relabel_i32": (_i32, [_p, _p, _i64, _p, _p, _i32]),
     "marex_partition_centroid_i32": (_i32, [_p, _p, _i32, _i32, _p, _i32, _p, _p, _p, _p, _i32]),
     "marex_nn_bucket_count_i32": (_i32, [_p, _p, _i32, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _i64, _p, _p]),

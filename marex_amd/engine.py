@@ -881,6 +881,150 @@ class HotPath:
                                   details=f"largest overlap {int(c.max())} cells")
         return np.stack([k >> 32, k & 0xFFFFFFFF, c], axis=1).astype(np.int32)
 
+    # ------------------------------------------------------------------ the same stages on a mesh (track.py:1947-2005, 2135-2323, 2431-2439)
+    def _mesh_weights_check(self, q: torch.Tensor, Cn: int, what: str) -> None:
+        if q.dtype != torch.int64 or tuple(q.shape) != (4, Cn) or not q.is_contiguous() or q.device != self.device:
+            raise ProcessingError(f"{what}: the weight table must be a contiguous int64 [4, {Cn}] tensor on the engine's device",
+                                  details=f"got {q.dtype} {tuple(q.shape)} on {q.device}")
+
+    def label_objects_mesh(self, x: torch.Tensor, mask: torch.Tensor, nbr: torch.Tensor,
+                           max_block_cells: Optional[int] = None) -> Dict[str, torch.Tensor]:
+        """Connected components per timestep over the mesh edges, land excluded (track.py:1947-2005): ``ids`` int32
+        ``[T, C]`` restarting at 1 in every timestep, numbered by each component's smallest cell index (scipy's
+        ``connected_components`` order), 0 = background, and ``n_t`` int32 ``[T]``, the objects of every timestep.
+        ``x`` uint8 ``[T, C]``, ``mask`` uint8 ``[C]``, ``nbr`` int32 ``[3, C]`` 0-based, -1 = none.  Timesteps are
+        independent, so a field of 2^31 - 1 cells and more (or any field when ``max_block_cells`` is given) is labelled in
+        time blocks (:func:`plan_time_blocks`) with no seam work."""
+        T, Cn = (int(k) for k in x.shape)
+        blocks = plan_time_blocks(T, Cn, max_block_cells)
+        blk = max(b - a for a, b in blocks) * Cn
+        self._check_fits(4 * T * Cn + 4 * T + 8 * blk, "mesh labelling",
+                         f"int32 IDs of {T} x {Cn} cells, the int32 sizes and the union-find scratch of a block of {blk} cells")
+        ids = self._buf(None, "ids_mesh", (T, Cn), torch.int32, self.device)
+        n_t = self._buf(None, "n_t_mesh", (T,), torch.int32, self.device)
+        work = self._buf(None, "areas_mesh_block", (blk,), torch.int32, self.device)
+        for t0, t1 in blocks:
+            self.call("marex_label_mesh_i32", x[t0:t1], mask, nbr, t1 - t0, Cn, ids[t0:t1], work)
+            self.call("marex_label_mesh_rank_i32", ids[t0:t1], t1 - t0, Cn, work, ids[t0:t1], n_t[t0:t1])
+        return {"ids": ids, "n_t": n_t}
+
+    def unique_ids_in_time(self, ids: torch.Tensor) -> torch.Tensor:
+        """``ids + (exclusive cumulative sum over time of the per-timestep maximum)`` where ``ids > 0`` (track.py:2762-2764):
+        a new int32 ``[T, C]`` tensor.  :class:`TrackingError` when the largest new ID would exceed 2^31 - 2."""
+        T, Cn = self._ids_check(ids)
+        self._check_fits(4 * T * Cn + 8 * T, "unique IDs in time", f"an int32 copy of {T} x {Cn} IDs")
+        rowmax = self._buf(None, "ids_rowmax", (T,), torch.int32, self.device)
+        self.call("marex_ids_row_max_i32", ids, T, Cn, rowmax)
+        csum = torch.cumsum(rowmax.to(torch.int64), 0)
+        total = int(csum[-1].item())
+        if total > LABEL_BLOCK_CELLS:
+            raise TrackingError(f"more than 2^31 - 2 objects ({total}): unique IDs do not fit int32")
+        off = (csum - rowmax).to(torch.int32)
+        out = self._buf(None, "ids_unique", (T, Cn), torch.int32, self.device)
+        self.call("marex_ids_add_row_offset_i32", ids, T, Cn, off, out)
+        return out
+
+    def mesh_object_moments(self, ids: torch.Tensor, q: torch.Tensor, e: int) -> Dict[str, np.ndarray]:
+        """Area and centroid on the sphere of every ID in every timestep of ``ids`` int32 ``[T, C]`` (values <= 0:
+        background), weighted by the fixed-point table ``q`` int64 ``[4, C]`` with exponent ``e``
+        (:func:`marex_amd.track.mesh_weight_tables`): ``t``, ``id``, ``cells`` (int64), ``area`` (float32) and ``centroid``
+        (float32 ``[2, n]``: latitude, longitude in degrees), rows in (t, id) order.  The device adds integers; the host
+        divides in float64: ``area = float32(S0 / 2^e)``, the centroid is the direction of ``(S1, S2, S3)``."""
+        T, Cn = self._ids_check(ids)
+        self._mesh_weights_check(q, Cn, "mesh_object_moments")
+        _, hi = self.ids_minmax(ids)
+        out = {"t": np.zeros(0, np.int64), "id": np.zeros(0, np.int64), "cells": np.zeros(0, np.int64),
+               "area": np.zeros(0, np.float32), "centroid": np.zeros((2, 0), np.float32)}
+        if hi <= 0:
+            return out
+        tmin, _, off, total = self._object_spans(
+            ids, T, Cn, hi, "mesh object properties",
+            f"per-ID first / last timestep and slot offsets for IDs 0..{hi}; renumber sparse IDs densely")
+        n_slots = int(total.item())
+        self._check_fits(88 * n_slots, "mesh object properties",
+                         f"{n_slots} (timestep, ID) slots between each ID's first and last timestep, 88 bytes each")
+        acc = self._buf(None, "mobj_acc", (n_slots, 5), torch.int64, self.device)
+        self.call("marex_mesh_object_moments_i64", ids, T, Cn, q, tmin, off, n_slots, acc)
+        n_out = self._buf(None, "mobj_n", (1,), torch.int64, self.device)
+        tid = self._buf(None, "mobj_tid", (n_slots, 2), torch.int32, self.device)
+        mom = self._buf(None, "mobj_mom", (n_slots, 5), torch.int64, self.device)
+        self.call("marex_object_compact", n_slots, hi, tmin, off, acc, n_out, tid, mom)
+        n = int(n_out.item())
+        if not 0 < n <= n_slots:
+            raise ProcessingError(f"mesh_object_moments: {n} non-empty slots of {n_slots} (internal sizing error)")
+        tid_h = tid[:n].cpu().numpy().astype(np.int64)
+        mom_h = mom[:n].cpu().numpy()
+        order = np.argsort((tid_h[:, 0] << 32) | tid_h[:, 1])  # (t, id) order: the device compacts in no particular order
+        tid_h, mom_h = tid_h[order], mom_h[order]
+        s0, s1, s2, s3 = (mom_h[:, k].astype(np.float64) for k in range(1, 5))
+        norm = np.sqrt(s1 * s1 + s2 * s2 + s3 * s3)
+        norm = np.where(norm > 0, norm, 1.0)
+        lat = np.degrees(np.arcsin(np.clip(s3 / norm, -1.0, 1.0)))
+        lon = np.degrees(np.arctan2(s2 / norm, s1 / norm))
+        lon = np.where(lon > 180.0, lon - 360.0, np.where(lon < -180.0, lon + 360.0, lon))  # track.py:2226-2230
+        out.update(t=tid_h[:, 0], id=tid_h[:, 1], cells=mom_h[:, 0].copy(), area=np.ldexp(s0, -int(e)).astype(np.float32),
+                   centroid=np.stack([lat, lon]).astype(np.float32))
+        return out
+
+    def mesh_overlap_pairs(self, ids: torch.Tensor, q: torch.Tensor, e: int) -> np.ndarray:
+        """``(n, 3)`` float32 ``[id at t, id at t + 1, overlap area]`` over every t < T - 1 of ``ids`` int32 ``[T, C]``: the area
+        of the cells a pair shares, summed over time as an integer of ``q[0]`` and returned as ``float32(S / 2^e)``, rows
+        sorted lexicographically (check_overlap_slice / find_overlapping_objects on a mesh, track.py:2396-2504); ``S`` is exact
+        even where a pair met in many timesteps adds up to more than 64 bits.  The IDs
+        travel in float32 columns as the reference's do: :class:`TrackingError` for an ID of 2^24 or above."""
+        T, Cn = self._ids_check(ids)
+        self._mesh_weights_check(q, Cn, "mesh_overlap_pairs")
+        _, hi = self.ids_minmax(ids)
+        if hi >= 1 << 24:
+            raise TrackingError(f"object IDs of 2^24 and above ({hi}) do not survive the float32 columns of the overlap list",
+                                details="the reference stores [id, id, area] in one float32 array (track.py:2450)",
+                                suggestions=["Renumber the IDs densely"])
+        empty = np.zeros((0, 3), np.float32)
+        if T < 2 or hi <= 0:
+            return empty
+        stats = self._buf(None, "ovl_stats", (4,), torch.int64, self.device)
+        self.call("marex_overlap_count_i32", ids, T, Cn, stats)
+        runs = int(stats[1].item())
+        if runs == 0:
+            return empty
+        cap = max(64, 1 << (2 * runs - 1).bit_length())  # load factor <= 1/2 even if every run were a distinct pair
+        self._check_fits(24 * cap + 24 * runs, "mesh overlap pairs", f"a hash table of {cap} entries for {runs} runs of equal pairs")
+        keys = self._buf(None, "movl_keys", (cap,), torch.int64, self.device)
+        sums = self._buf(None, "movl_sums", (cap, 2), torch.int64, self.device)
+        out_k = self._buf(None, "movl_out_keys", (runs,), torch.int64, self.device)
+        out_s = self._buf(None, "movl_out_sums", (runs, 2), torch.int64, self.device)
+        self.call("marex_mesh_overlap_pairs_i64", ids, T, Cn, q[0], cap, keys, sums, stats, runs, out_k, out_s)
+        s = stats.cpu().numpy()
+        n = int(s[3])
+        if s[2] != 0 or not 0 < n <= runs:
+            raise ProcessingError(f"mesh overlap pairs: hash table overflow ({n} pairs, {runs} runs, {cap} entries)")
+        k = out_k[:n].cpu().numpy()
+        a = out_s[:n].cpu().numpy().view(np.uint64)
+        order = np.argsort(k, kind="stable")
+        k, a = k[order], a[order]
+        # the pair's sum S = a[:, 1] * 2^32 + a[:, 0] as a correctly rounded float64: through int64 below 2^63, else exactly
+        # in Python integers (a pair that persists over many timesteps; few rows)
+        hi, lo = a[:, 1] + (a[:, 0] >> np.uint64(32)), a[:, 0] & np.uint64(0xFFFFFFFF)
+        small = hi < np.uint64(1 << 31)
+        S = np.empty(n, np.float64)
+        S[small] = ((hi[small] << np.uint64(32)) | lo[small]).astype(np.int64).astype(np.float64)
+        for j in np.nonzero(~small)[0]:
+            S[j] = float((int(hi[j]) << 32) + int(lo[j]))
+        return np.stack([(k >> 32).astype(np.float32), (k & 0xFFFFFFFF).astype(np.float32),
+                         np.ldexp(S, -int(e)).astype(np.float32)], axis=1)
+
+    def mesh_area(self, x: torch.Tensor, q: torch.Tensor, e: int) -> np.ndarray:
+        """float64 ``[T]``: the area of the cells set in every timestep of ``x`` uint8 ``[T, C]``, ``S / 2^e`` of the integer
+        sum ``S`` of ``q[0]`` over them (compute_area on a mesh, track.py:1513-1514)."""
+        if x.dtype != torch.uint8 or x.dim() != 2:
+            raise ProcessingError("mesh_area: the field must be a uint8 [T, C] tensor", details=f"got {x.dtype} {tuple(x.shape)}")
+        T, Cn = (int(k) for k in x.shape)
+        self._mesh_weights_check(q, Cn, "mesh_area")
+        self._check_fits(8 * T, "mesh area", f"one int64 sum per timestep, {T} timesteps")
+        out = self._buf(None, "mesh_area", (T,), torch.int64, self.device)
+        self.call("marex_mesh_area_i64", x, T, Cn, q[0], out)
+        return np.ldexp(out.cpu().numpy().astype(np.float64), -int(e))
+
     # ------------------------------------------------------------------ merge tracker stages (track.py:2554-3802)
     def _i32(self, a) -> torch.Tensor:
         return self._dev(np.asarray(a, dtype=np.int32))

@@ -16,6 +16,7 @@ from typing import Dict, List, Literal, Optional, Tuple, Union
 import numpy as np
 
 from .exceptions import ConfigurationError, ProcessingError, TrackingError, create_data_validation_error
+from .track_mesh import _MeshStages, _not_built, mesh_weight_tables  # noqa: F401 -- mesh_weight_tables is public here
 
 logger = logging.getLogger("marex_amd")
 
@@ -203,15 +204,31 @@ class _Props:
         return cls(ids, np.asarray(object_props["area"].values, dtype=np.float64), c[0], c[1])
 
 
-class tracker:  # noqa: N801 -- the reference's public name (marEx.tracker)
-    """Identify extreme events as connected regions in (time, y, x) of a binary field on a grid.
+class tracker(_MeshStages):  # noqa: N801 -- the reference's public name (marEx.tracker)
+    """Identify extreme events as connected regions in (time, y, x) of a binary field on a grid; on an unstructured mesh,
+    the stages of the merge tracker up to the overlap threshold.
 
     The constructor takes the reference's arguments (track.py:323-348).  Supported here: gridded data, with
     ``allow_merging=False`` (the reference's "basic" tracker) and with ``allow_merging=True`` (the default: merging and
     splitting, centroid or ``nn_partitioning``).  Merge results depend on the time chunks the per-timestep loop walks: they
     are taken from ``data_bin.chunks`` (Dask), from ``data_bin.encoding["chunks"]`` (a store's chunks) or from the
     ``timechunks`` keyword (regular chunks from t = 0); with none of them ``allow_merging=True`` raises
-    :class:`ConfigurationError`.  ``unstructured_grid=True`` and ``checkpoint="save"`` / ``"load"`` raise too.
+    :class:`ConfigurationError`.  ``checkpoint="save"`` / ``"load"`` raise too.
+
+    Unstructured meshes (``unstructured_grid=True``, marex_amd/track_mesh.py).  ``data_bin`` is ``(time, x)`` (transposed if
+    given the other way), ``mask`` ``(x,)``, lat / lon coordinates over ``x``, ``neighbours`` ``("nv", x)`` with 3 rows of
+    1-based cell numbers (0: none) and ``cell_areas`` over ``x``; without the last two the constructor raises
+    :class:`ConfigurationError`, ``regional_mode=True`` raises ``NotImplementedError`` and ``grid_resolution`` is refused, as
+    in the reference.  Built on a mesh, on the device: :meth:`run_preprocess`, :meth:`compute_area`,
+    :meth:`identify_objects` (IDs restart at 1 in every timestep, in scipy's ``connected_components`` order),
+    :meth:`unique_ids_in_time`, :meth:`calculate_object_properties` (float32 area in the units of ``cell_areas``, float32
+    centroid (lat, lon) in degrees on the sphere), :meth:`check_overlap_slice` / :meth:`find_overlapping_objects`
+    (``(n, 3)`` float32 ``[id, id, overlap area]``) and :meth:`enforce_overlap_threshold`.  Areas are integer sums of the
+    fixed-point weights of :func:`mesh_weight_tables`: bitwise reproducible, and within the rounding bound of the
+    reference's float32 sums.  The split-and-merge stage is not built: :meth:`run`, :meth:`run_tracking`,
+    :meth:`track_objects`, :meth:`split_and_merge_objects`, :meth:`consolidate_object_ids` and
+    :meth:`cluster_rename_objects_and_props` raise :class:`ConfigurationError` on a mesh.  ``allow_merging=True`` needs no
+    time chunking there; ``temp_dir`` is not required (nothing is written to disk) and ``max_iteration`` is ignored.
 
     ``grid_resolution`` and ``cell_areas`` weight the final area and centroid of merge tracking (object properties count
     cells, as the reference's do, track.py:1499-1518, 2337).  Accepted and ignored: ``temp_dir``,
@@ -282,8 +299,10 @@ class tracker:  # noqa: N801 -- the reference's public name (marEx.tracker)
                                          suggestions=["Pass timechunks=<steps per chunk>", "Chunk data_bin in time",
                                                       "Pass allow_merging=False"])
         if unstructured_grid:
-            raise ConfigurationError("unstructured_grid=True is not supported by the device tracker",
-                                     details=f"supported: {supported}; the reference tracks meshes with the merge tracker only")
+            self._init_mesh(data_bin, mask, R_fill, area_filter_quartile, area_filter_absolute, T_fill, allow_merging,
+                            nn_partitioning, overlap_threshold, dimensions, coordinates, neighbours, cell_areas, grid_resolution,
+                            max_iteration, checkpoint, regional_mode, coordinate_units, device)
+            return
         if checkpoint in ("save", "load"):
             raise ConfigurationError(f"checkpoint={checkpoint!r} is not supported by the device tracker",
                                      details=f"supported: {supported}; the pipeline stays in device memory",
@@ -516,6 +535,8 @@ class tracker:  # noqa: N801 -- the reference's public name (marEx.tracker)
     def run(self, return_merges: bool = False, checkpoint: Optional[str] = None):
         """``run_preprocess`` -> ``run_tracking`` -> ``run_stats_attributes``; returns the events Dataset, and with
         ``return_merges`` and merging also the merge events: ``(events_ds, merges_ds)`` (track.py:1162-1232)."""
+        if self.unstructured_grid:
+            raise _not_built("tracker.run")
         if self.allow_merging:
             self._check_size(self.data_bin.shape)
         else:
@@ -530,13 +551,16 @@ class tracker:  # noqa: N801 -- the reference's public name (marEx.tracker)
     def run_preprocess(self, checkpoint: Optional[str] = None) -> Tuple[object, Tuple[float, int, int, float, float, float]]:
         """Fill holes, fill time gaps and remove small objects (track.py:1234-1368), on the device.  Returns the filtered
         mask as a device-resident DataArray and ``(total_area_IDed, N_objects_prefiltered, N_objects_filtered,
-        area_threshold, accepted_area_fraction, preprocessed_area_fraction)``, areas in cells."""
+        area_threshold, accepted_area_fraction, preprocessed_area_fraction)``, areas in cells.  On a mesh: the mesh forms of
+        the same stages, sizes in cells, ``preprocessed_area_fraction`` from the area-weighted :meth:`compute_area`."""
         import torch
 
         from .track_pre import _preprocess_device
 
         if checkpoint in ("save", "load"):
             raise ConfigurationError(f"checkpoint={checkpoint!r} is not supported by the device tracker")
+        if self.unstructured_grid:
+            return self._mesh_run_preprocess()
         eng = self._engine()
         x, T, ny, nx = self._device_u8(self.data_bin, eng)
         mk = torch.from_numpy(self._mask_host.reshape(-1).astype(np.uint8)).to(eng.device)
@@ -548,9 +572,14 @@ class tracker:  # noqa: N801 -- the reference's public name (marEx.tracker)
     def identify_objects(self, data_bin, time_connectivity: bool):
         """Connected regions of ``data_bin`` (track.py:1912-2048, structured grid): 26-connected in (time, y, x) with
         ``time_connectivity``, else 8-connected per timestep; periodic in x unless ``regional_mode``.  Returns
-        ``(ID_field int32, None, N_objects)``; IDs 1..N by first cell in C order, unique across time either way."""
+        ``(ID_field int32, None, N_objects)``; IDs 1..N by first cell in C order, unique across time either way.  On a mesh
+        (track.py:1932-2005): components over the listed edges per timestep, land excluded, ``time_connectivity=True``
+        refused; IDs restart at 1 in every timestep, ranked by each component's smallest cell, and the third value is the
+        reference's placeholder 1 (see :meth:`unique_ids_in_time`)."""
         from .xr_compat import DataArray
 
+        if self.unstructured_grid:
+            return self._mesh_identify_objects(data_bin, time_connectivity)
         eng = self._engine()
         T, ny, nx = (int(data_bin.shape[k]) for k in self._perm_of(data_bin))
         block = None if self.label_block_steps is None else self.label_block_steps * ny * nx
@@ -569,6 +598,8 @@ class tracker:  # noqa: N801 -- the reference's public name (marEx.tracker)
         coordinate gets its own name back when it differs from the time dimension."""
         from .xr_compat import DataArray, Dataset
 
+        if self.unstructured_grid:
+            raise _not_built("tracker.run_tracking")
         if self.allow_merging:  # track.py:1388-1390
             return self.track_objects(data_bin_preprocessed)
         ids, _, N_events_final = self.identify_objects(data_bin_preprocessed, time_connectivity=True)
@@ -630,11 +661,14 @@ class tracker:  # noqa: N801 -- the reference's public name (marEx.tracker)
     # ------------------------------------------------------------------ object properties and overlaps (track.py:1499-1518, 2050-2552)
     def compute_area(self, data_bin):
         """Cells of ``data_bin`` per timestep (track.py:1499-1518, gridded: ``data_bin.sum(dim=[y, x])``), an int64
-        DataArray over time.  ``data_bin`` may be device resident."""
+        DataArray over time.  ``data_bin`` may be device resident.  On a mesh: the area of the cells set per timestep
+        (``(data_bin * cell_area).sum(x)``), float64, from integer sums of the fixed-point cell areas on the device."""
         import torch
 
         from .xr_compat import DataArray
 
+        if self.unstructured_grid:
+            return self._mesh_compute_area(data_bin)
         dims = tuple(getattr(data_bin, "dims", ()) or ())
         if not dims:
             dims = self._out_dims() if len(data_bin.shape) == 3 else (self.ydim, self.xdim)
@@ -749,9 +783,13 @@ class tracker:  # noqa: N801 -- the reference's public name (marEx.tracker)
         reference's concatenation of per-slice ``regionprops_table`` results does.  ``area`` is float64 cells;
         ``centroid`` is float64 ``(component, ID)``: the mean row index and the mean column index, the latter with the
         seam rule of :meth:`calculate_centroid` unless ``regional_mode``.  Values <= 0 are background; a negative ID or
-        one beyond int32 raises :class:`DataValidationError`."""
+        one beyond int32 raises :class:`DataValidationError`.  On a mesh (track.py:2135-2323): ``area`` is float32 in the
+        units of ``cell_areas`` and ``centroid`` float32 (lat, lon) in degrees, the direction of the area-weighted mean unit
+        vector; one row per (timestep, ID) in (t, ID) order."""
         from .xr_compat import DataArray, Dataset
 
+        if self.unstructured_grid:
+            return self._mesh_object_properties(object_id_field, properties)
         properties = ["label", "area"] if properties is None else list(properties)
         if "label" not in properties:
             properties = ["label"] + properties
@@ -776,9 +814,13 @@ class tracker:  # noqa: N801 -- the reference's public name (marEx.tracker)
 
     def check_overlap_slice(self, ids_t0, ids_next) -> np.ndarray:
         """Overlaps of two ID slices (track.py:2396-2452): ``(n, 3)`` int32 ``[id_t0, id_next, cells]`` over the cells
-        where both are > 0, sorted lexicographically; ``(0, 3)`` when there are none.  Computed on the device."""
+        where both are > 0, sorted lexicographically; ``(0, 3)`` when there are none.  Computed on the device.  On a mesh:
+        ``(n, 3)`` float32 ``[id_t0, id_next, overlap area]``; IDs of 2^24 and above, which the float32 columns would round,
+        raise :class:`TrackingError`."""
         import torch
 
+        if self.unstructured_grid:
+            return self._mesh_check_overlap_slice(ids_t0, ids_next)
         eng = self._engine()
         a, Ta, nya, nxa = self._device_ids(ids_t0, eng)
         b, Tb, nyb, nxb = self._device_ids(ids_next, eng)
@@ -792,7 +834,10 @@ class tracker:  # noqa: N801 -- the reference's public name (marEx.tracker)
     def find_overlapping_objects(self, object_id_field) -> np.ndarray:
         """Overlaps of every slice t with slice t + 1, t < T - 1 (track.py:2454-2504), computed on the device: ``(n, 3)``
         int32 ``[id at t, id at t + 1, cells]``, counts of equal pairs summed over time, sorted lexicographically.  A sum
-        that int32 cannot hold raises :class:`ProcessingError` instead of wrapping."""
+        that int32 cannot hold raises :class:`ProcessingError` instead of wrapping.  On a mesh: float32 rows with the shared
+        area in the third column, as :meth:`check_overlap_slice`."""
+        if self.unstructured_grid:
+            return self._mesh_find_overlapping_objects(object_id_field)
         eng = self._engine()
         ids, T, ny, nx = self._device_ids(object_id_field, eng)
         if ids.numel() == 0:
@@ -808,6 +853,8 @@ class tracker:  # noqa: N801 -- the reference's public name (marEx.tracker)
         Defined for unique IDs only -- object properties of per-timestep objects, e.g. of
         ``identify_objects(..., time_connectivity=False)``: ``object_props`` with repeated IDs (those of multi-day events)
         raises :class:`DataValidationError`."""
+        if self.unstructured_grid:
+            return self._mesh_enforce_overlap_threshold(overlap_objects_list, object_props)
         ov = np.asarray(overlap_objects_list)
         empty = np.empty((0, 3), dtype=np.int32)
         if len(ov) == 0:
@@ -1179,6 +1226,8 @@ class tracker:  # noqa: N801 -- the reference's public name (marEx.tracker)
         N_events)``."""
         import time
 
+        if self.unstructured_grid:
+            raise _not_built("tracker.track_objects")
         self._check_size(data_bin.shape)  # merge tracking keeps refusing fields of 2^31 - 1 cells and more
         eng = self._engine()
         st = self._stage_times = {}
@@ -1210,6 +1259,8 @@ class tracker:  # noqa: N801 -- the reference's public name (marEx.tracker)
 
         from .xr_compat import DataArray
 
+        if self.unstructured_grid:
+            raise _not_built("tracker.consolidate_object_ids")
         eng = self._engine()
         a, _, ny, nx = self._device_ids(data_t_minus_2, eng)
         b, _, _, _ = self._device_ids(data_t_minus_1, eng)
@@ -1224,6 +1275,8 @@ class tracker:  # noqa: N801 -- the reference's public name (marEx.tracker)
         object_props, overlap_objects_list (n, 2), merge_events)``.  IDs must be unique across time."""
         from .xr_compat import DataArray
 
+        if self.unstructured_grid:
+            raise _not_built("tracker.split_and_merge_objects")
         eng = self._engine()
         ids, T, ny, nx = self._device_ids(object_id_field_unique, eng)
         ids = ids.clone()
@@ -1238,6 +1291,8 @@ class tracker:  # noqa: N801 -- the reference's public name (marEx.tracker)
         time_start / time_end, area, centroid (degrees, before _remap_coordinates) and merge_ledger
         (track.py:2809-3335), on the device.  ``merge_events`` are the merge records of :meth:`split_and_merge_objects`; each
         merge is placed on the time axis by its ``merge_time``."""
+        if self.unstructured_grid:
+            raise _not_built("tracker.cluster_rename_objects_and_props")
         eng = self._engine()
         ids, T, ny, nx = self._device_ids(object_id_field_unique, eng)
         ids = ids.clone()
