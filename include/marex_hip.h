@@ -556,6 +556,34 @@ int marex_partition_nn_i32(marex_ctx* ctx, int32_t* ids, const int32_t* prev, in
 int marex_event_moments_i32(marex_ctx* ctx, const int32_t* ev, const int32_t* orig, int64_t T, int ny, int nx, int n_ev,
                             const float* w, uint64_t* acc, double* wacc, int32_t* gid);
 
+/* The partition kernels of the split-and-merge stage on an unstructured mesh (tracker.split_and_merge_objects_parallel,
+ * marEx/track.py:3804-4814, 5246-5419).  A slice is int32 [C], values <= 0 are background, C below 2^31 - 1.  u: float64
+ * [3][C], the unit vectors of the cells; pv: float64 [3][n], the unit vectors of the parents' centroids.  "Nearest" is the
+ * smallest ((dx dx + dy dy) + dz dz) in float64 without fused multiply-add, first minimum.
+ *
+ * marex_mesh_partition_centroid_i32: every cell of child child_keys[k] (ascending, distinct) takes lab[j] of the nearest
+ *   of the parent entries j in off[k] .. off[k + 1] (of n_ent).  In place, all merging children of one timestep at once.
+ * marex_mesh_nn_seed_i32 / marex_mesh_nn_hops_i32 / marex_mesh_nn_finish_i32 (partition_nn_unstructured_optimised) for one
+ *   child of the slice cur, with parents[j] (n_par <= 10) the parent IDs in the slice prev.  word: uint32 [C] work, one
+ *   (substep stamp << 8 | owner) per cell, owner 255 = unclaimed.  ctl: int32 [8]: [0] child cells without an owner,
+ *   [1] a child cell was claimed in the running hop, [2] stopped, [3] hops run, [4] child cells resolved by the nearest
+ *   centroid, [5] why it stopped (1: no child cell left, 2: a hop claimed no child cell, 3: max_hops).  seed zeroes ctl,
+ *   gives the cells of parent j the owner j and counts ctl[0].  hops queues hops first_hop .. first_hop + n_hops (at most
+ *   max_hops in all; nbr: int32 [3][C], 0-based, negative = none): before each hop one thread applies the stopping
+ *   rule; a hop is one launch per (parent ascending, direction 0 .. 2), in which every unclaimed cell that is the
+ *   listed neighbour of a cell the parent owned when the launch began becomes the parent's; launches after ctl[2] was
+ *   set do nothing, so the caller may read ctl as rarely as it likes.  finish applies the stopping rule once more and
+ *   writes cur[c] = lab[owner] on the child's cells, unclaimed ones by the nearest of pv [3][n_par].
+ * All are asynchronous on the context's stream. */
+int marex_mesh_partition_centroid_i32(marex_ctx* ctx, int32_t* ids, int64_t C, const int32_t* child_keys, int n_child,
+                                      const int32_t* off, const double* u, const double* pv, int n_ent, const int32_t* lab);
+int marex_mesh_nn_seed_i32(marex_ctx* ctx, const int32_t* cur, const int32_t* prev, int64_t C, int child,
+                           const int32_t* parents, int n_par, uint32_t* word, int32_t* ctl);
+int marex_mesh_nn_hops_i32(marex_ctx* ctx, const int32_t* cur, const int32_t* nbr, int64_t C, int child, int n_par,
+                           int first_hop, int n_hops, int max_hops, uint32_t* word, int32_t* ctl);
+int marex_mesh_nn_finish_i32(marex_ctx* ctx, int32_t* cur, int64_t C, int child, const double* u, const double* pv, int n_par,
+                             const int32_t* lab, const uint32_t* word, int32_t* ctl, int max_hops);
+
 /* out[c, r] = in[r, c]  (thresholds [366, C] -> the reference's (cells, dayofyear) order) */
 int marex_transpose_f32(marex_ctx* ctx, const float* in, int64_t rows, int64_t cols, float* out);
 

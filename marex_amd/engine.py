@@ -1078,6 +1078,83 @@ class HotPath:
                   len(child_keys), t["off"], pcy_d, pcx_d, t["lab"], t["gs"], t["ngy"], t["ngx"], t["maxd"], base_d, n_buckets,
                   bstart, cnt, cells, n_cells, int(bool(wrap)))
 
+    # ------------------------------------------------------------------ the partitions of the merge stage on a mesh (track.py:5246-5419)
+    def _mesh_partition_check(self, what: str, cur: torch.Tensor, u: torch.Tensor) -> int:
+        if cur.dtype != torch.int32 or cur.dim() != 1 or not cur.is_contiguous() or cur.device != self.device:
+            raise ProcessingError(f"{what}: the slice must be a contiguous int32 [C] tensor on the engine's device",
+                                  details=f"got {cur.dtype} {tuple(cur.shape)} on {cur.device}")
+        Cn = int(cur.numel())
+        if u.dtype != torch.float64 or tuple(u.shape) != (3, Cn) or not u.is_contiguous() or u.device != self.device:
+            raise ProcessingError(f"{what}: the cells' unit vectors must be a contiguous float64 [3, {Cn}] tensor on the engine's "
+                                  f"device", details=f"got {u.dtype} {tuple(u.shape)} on {u.device}")
+        return Cn
+
+    def mesh_partition_centroid(self, cur: torch.Tensor, child_keys, off, parent_vectors, labels, u: torch.Tensor) -> None:
+        """In place on the slice ``cur`` (int32 ``[C]``): every cell of child ``child_keys[k]`` (ascending) takes
+        ``labels[j]`` of the parent entry ``off[k] <= j < off[k + 1]`` whose float64 unit vector ``parent_vectors[:, j]`` is
+        nearest to the cell's, ``u[:, c]``: smallest ``((dx dx + dy dy) + dz dz)``, first minimum.  All children of a
+        timestep go in one launch (their cells are disjoint, the new labels fresh)."""
+        Cn = self._mesh_partition_check("mesh_partition_centroid", cur, u)
+        keys, off = np.asarray(child_keys, np.int64), np.asarray(off, np.int64)
+        pv = np.ascontiguousarray(np.asarray(parent_vectors, np.float64))
+        n_ent = len(labels)
+        if (keys.size == 0 or off.size != keys.size + 1 or np.any(np.diff(keys) <= 0) or off[0] != 0 or off[-1] != n_ent
+                or np.any(np.diff(off) <= 0) or pv.shape != (3, n_ent)):
+            raise ProcessingError("mesh_partition_centroid: child_keys must ascend, off must run from 0 to len(labels) with at "
+                                  "least one entry per child, parent_vectors must be [3, len(labels)]",
+                                  details=f"{keys.size} children, off {off.tolist()}, {n_ent} labels, vectors {pv.shape}")
+        self._check_fits(4 * (2 * keys.size + 1 + n_ent) + 24 * n_ent, "mesh centroid partition",
+                         f"the tables of {keys.size} children and {n_ent} parent entries")
+        self.call("marex_mesh_partition_centroid_i32", cur, Cn, self._i32(keys), int(keys.size), self._i32(off), u, self._dev(pv),
+                  n_ent, self._i32(labels))
+
+    #: hops of the nearest-neighbour partition queued between two reads of its control block (the result does not depend on it)
+    MESH_NN_HOPS_PER_READ = 8
+
+    def mesh_partition_nn(self, cur: torch.Tensor, prev: torch.Tensor, nbr: torch.Tensor, child: int, parents, parent_vectors,
+                          labels, max_hops: int, u: torch.Tensor, hops_per_read: Optional[int] = None) -> Dict[str, int]:
+        """In place on the slice ``cur``: the cells of ``child`` are divided among ``parents`` (IDs in the slice ``prev``, at
+        most 10) as partition_nn_unstructured_optimised does (track.py:5246-5353): the parents' cells seed frontiers that
+        grow over the listed neighbours ``nbr`` (int32 ``[3, C]``, 0-based, negative = none) hop by hop -- per hop, parent
+        ascending, direction 0, 1, 2, one launch each -- until no child cell is unclaimed, a hop claims no child cell or
+        ``max_hops`` hops have run; child cells still unclaimed take the nearest of ``parent_vectors`` (float64 ``[3, k]``) as
+        in :meth:`mesh_partition_centroid`.  A cell owned by parent ``j`` gets ``labels[j]``.  The stopping rule lives in a
+        control block on the device; the host reads it every ``hops_per_read`` hops.  Returns ``hops`` (run), ``leftover``
+        (cells resolved by the centroid rule), ``reason`` (1: no child cell left, 2: a hop claimed no child cell, 3: the
+        cap), ``launches`` and ``reads``."""
+        Cn = self._mesh_partition_check("mesh_partition_nn", cur, u)
+        k = len(parents)
+        pv = np.ascontiguousarray(np.asarray(parent_vectors, np.float64))
+        max_hops = int(max_hops)
+        per = int(self.MESH_NN_HOPS_PER_READ if hops_per_read is None else hops_per_read)
+        if (prev.dtype != torch.int32 or tuple(prev.shape) != (Cn,) or nbr.dtype != torch.int32 or tuple(nbr.shape) != (3, Cn)
+                or not prev.is_contiguous() or not nbr.is_contiguous() or prev.device != self.device or nbr.device != self.device):
+            raise ProcessingError("mesh_partition_nn: prev must be a contiguous int32 [C] tensor and nbr a contiguous int32 "
+                                  "[3, C] tensor on the engine's device",
+                                  details=f"got {prev.dtype} {tuple(prev.shape)} on {prev.device} and {nbr.dtype} "
+                                          f"{tuple(nbr.shape)} on {nbr.device}")
+        if not 1 <= k <= 10 or len(labels) != k or pv.shape != (3, k) or int(child) <= 0 or max_hops < 0 or per < 1:
+            raise ProcessingError("mesh_partition_nn: 1 to 10 parents with one label and one vector each, a positive child ID, "
+                                  "max_hops >= 0", details=f"{k} parents, {len(labels)} labels, vectors {pv.shape}, child {child}")
+        if max_hops * 3 * k >= 1 << 24:
+            raise ProcessingError(f"mesh_partition_nn: {max_hops} hops of {3 * k} substeps do not fit the 24-bit substep stamp")
+        self._check_fits(4 * Cn + 32 + 32 * k, "mesh nearest-neighbour partition", f"one 32-bit owner word per cell, {Cn} cells")
+        word = self._buf(None, "mnn_word", (Cn,), torch.int32, self.device)
+        ctl = self._buf(None, "mnn_ctl", (8,), torch.int32, self.device)
+        lab_d, pv_d = self._i32(labels), self._dev(pv)
+        self.call("marex_mesh_nn_seed_i32", cur, prev, Cn, int(child), self._i32(parents), k, word, ctl)
+        done = reads = 0
+        while done < max_hops:
+            n = min(per, max_hops - done)
+            self.call("marex_mesh_nn_hops_i32", cur, nbr, Cn, int(child), k, done, n, max_hops, word, ctl)
+            done += n
+            reads += 1
+            if int(ctl[2].item()):
+                break
+        self.call("marex_mesh_nn_finish_i32", cur, Cn, int(child), u, pv_d, k, lab_d, word, ctl, max_hops)
+        c = ctl.cpu().numpy()
+        return {"hops": int(c[3]), "leftover": int(c[4]), "reason": int(c[5]), "launches": 3 + done * (3 * k + 1), "reads": reads}
+
     def id_spans(self, ids: torch.Tensor):
         """``(tmin, tmax)`` int32 host arrays over IDs 0..max of ``ids`` int32 ``[T, C]``: the first / last timestep of
         every ID (INT_MAX / -1 when absent); ``None`` when the field has no ID > 0."""

@@ -206,7 +206,7 @@ class _Props:
 
 class tracker(_MeshStages):  # noqa: N801 -- the reference's public name (marEx.tracker)
     """Identify extreme events as connected regions in (time, y, x) of a binary field on a grid; on an unstructured mesh,
-    the stages of the merge tracker up to the overlap threshold.
+    the stages of the merge tracker up to and including split-and-merge.
 
     The constructor takes the reference's arguments (track.py:323-348).  Supported here: gridded data, with
     ``allow_merging=False`` (the reference's "basic" tracker) and with ``allow_merging=True`` (the default: merging and
@@ -223,17 +223,21 @@ class tracker(_MeshStages):  # noqa: N801 -- the reference's public name (marEx.
     :meth:`identify_objects` (IDs restart at 1 in every timestep, in scipy's ``connected_components`` order),
     :meth:`unique_ids_in_time`, :meth:`calculate_object_properties` (float32 area in the units of ``cell_areas``, float32
     centroid (lat, lon) in degrees on the sphere), :meth:`check_overlap_slice` / :meth:`find_overlapping_objects`
-    (``(n, 3)`` float32 ``[id, id, overlap area]``) and :meth:`enforce_overlap_threshold`.  Areas are integer sums of the
-    fixed-point weights of :func:`mesh_weight_tables`: bitwise reproducible, and within the rounding bound of the
-    reference's float32 sums.  The split-and-merge stage is not built: :meth:`run`, :meth:`run_tracking`,
-    :meth:`track_objects`, :meth:`split_and_merge_objects`, :meth:`consolidate_object_ids` and
-    :meth:`cluster_rename_objects_and_props` raise :class:`ConfigurationError` on a mesh.  ``allow_merging=True`` needs no
-    time chunking there; ``temp_dir`` is not required (nothing is written to disk) and ``max_iteration`` is ignored.
+    (``(n, 3)`` float32 ``[id, id, overlap area]``), :meth:`enforce_overlap_threshold` and
+    :meth:`split_and_merge_objects_parallel` (the reference's merge algorithm for meshes: it walks the time chunks of
+    ``data_bin`` or of ``timechunks=``, no chunk of one step, and raises :class:`TrackingError` after ``max_iteration``
+    iterations).  Areas are integer sums of the fixed-point weights of :func:`mesh_weight_tables`: bitwise reproducible,
+    and within the rounding bound of the reference's float32 sums.  Cluster renaming and the end-to-end run are not built
+    on a mesh: :meth:`run`, :meth:`run_tracking`, :meth:`track_objects`, :meth:`split_and_merge_objects` (the gridded
+    algorithm), :meth:`consolidate_object_ids` and :meth:`cluster_rename_objects_and_props` raise
+    :class:`ConfigurationError` there.  The constructor needs no time chunking on a mesh (only
+    :meth:`split_and_merge_objects_parallel` does); ``temp_dir`` is not required (nothing is written to disk).
 
     ``grid_resolution`` and ``cell_areas`` weight the final area and centroid of merge tracking (object properties count
     cells, as the reference's do, track.py:1499-1518, 2337).  Accepted and ignored: ``temp_dir``,
-    ``max_iteration`` (meshes only), ``debug``, ``verbose`` and ``quiet`` (logging).  ``coordinate_units`` is resolved as
-    the reference does (track.py:919-976) when merging; the basic tracker carries the input's lat / lon unchanged.
+    ``max_iteration`` on grids (the gridded algorithm walks the timesteps once), ``debug``, ``verbose`` and ``quiet``
+    (logging).  ``coordinate_units`` is resolved as the reference does (track.py:919-976) when merging; the basic tracker
+    carries the input's lat / lon unchanged.
 
     The stages of the reference's merge tracker are public methods here too (track.py:1499-1518, 2050-3802):
     :meth:`compute_area`, :meth:`calculate_centroid`, :meth:`calculate_object_properties`, :meth:`check_overlap_slice`,
@@ -299,6 +303,8 @@ class tracker(_MeshStages):  # noqa: N801 -- the reference's public name (marEx.
                                          suggestions=["Pass timechunks=<steps per chunk>", "Chunk data_bin in time",
                                                       "Pass allow_merging=False"])
         if unstructured_grid:
+            # split_and_merge_objects_parallel walks these chunks; a mesh tracker without a known chunking still constructs
+            self._time_chunks = _time_chunk_layout(data_bin, dimensions, timechunks)
             self._init_mesh(data_bin, mask, R_fill, area_filter_quartile, area_filter_absolute, T_fill, allow_merging,
                             nn_partitioning, overlap_threshold, dimensions, coordinates, neighbours, cell_areas, grid_resolution,
                             max_iteration, checkpoint, regional_mode, coordinate_units, device)

@@ -1,13 +1,17 @@
 """The tracker on unstructured meshes (``marEx.tracker(unstructured_grid=True)``): the stages of ``track_objects``
-(track.py:2734-2807) up to and including the overlap threshold -- per-timestep objects, IDs unique in time, area-weighted
-object properties with centroids on the sphere, area-weighted time overlaps -- on the device.  The parallel
-split-and-merge and the cluster renaming that follow (track.py:2809-3335, 3804-4826) are not built.
+(track.py:2734-2807) up to and including split-and-merge -- per-timestep objects, IDs unique in time, area-weighted
+object properties with centroids on the sphere, area-weighted time overlaps, the overlap threshold, and the reference's
+parallel split-and-merge for meshes (``split_and_merge_objects_parallel``, track.py:3804-4814) -- on the device.  The cluster
+renaming that follows (track.py:2809-3335) and the end-to-end ``run()`` over it are not built.
 
 Arithmetic.  The reference sums cell areas and area-weighted unit vectors in float32 with ``np.add.at`` in cell order
 (track.py:2190-2208, 2436-2439); a parallel float sum cannot reproduce that bit for bit, and float atomics differ from
 run to run.  Here the weights are fixed point (:func:`mesh_weight_tables`), the device adds integers only, and the host
 turns the sums into float32 values: every result is exact in the sense of that contract and bitwise reproducible, and
-lies inside the rounding bound of the reference's own float32 sums (tests/test_mesh_tracker_host.py).
+lies inside the rounding bound of the reference's own float32 sums (tests/test_mesh_tracker_host.py).  The
+split-and-merge stage decides every overlap fraction on those areas and every "nearest centroid" on float64 unit vectors
+(:func:`mesh_unit_vectors`); its host side -- :func:`plan_merge_step`, :func:`queue_after_step`,
+:func:`check_temporary_id_ranges` -- works on the small tables the device hands back and needs no GPU.
 """
 from __future__ import annotations
 
@@ -15,7 +19,7 @@ from typing import List, Optional, Tuple
 
 import numpy as np
 
-from .exceptions import ConfigurationError, create_data_validation_error
+from .exceptions import ConfigurationError, TrackingError, create_data_validation_error
 
 
 def mesh_weight_tables(cell_areas, lat_deg, lon_deg) -> Tuple[int, np.ndarray]:
@@ -56,14 +60,119 @@ def mesh_weight_tables(cell_areas, lat_deg, lon_deg) -> Tuple[int, np.ndarray]:
     return e, q
 
 
+MESH_MAX_MERGES = 20    # merges per timestep and iteration (track.py:3828)
+MESH_MAX_PARENTS = 10   # parents per merge (track.py:3829)
+MESH_MAX_NEW_IDS = 255  # new IDs per timestep and iteration (the reference's updates_ids, track.py:3925)
+_I32_MAX = 2 ** 31 - 1
+
+
+def mesh_unit_vectors(lat_deg, lon_deg) -> np.ndarray:
+    """float64 ``[3, n]`` unit vectors of points given in degrees, with the expressions of :func:`mesh_weight_tables`: the
+    vectors the nearest-centroid rule of the split-and-merge stage compares."""
+    lat_r = np.radians(np.asarray(lat_deg, dtype=np.float64).reshape(-1))
+    lon_r = np.radians(np.asarray(lon_deg, dtype=np.float64).reshape(-1))
+    cl = np.cos(lat_r)
+    return np.stack([cl * np.cos(lon_r), cl * np.sin(lon_r), np.sin(lat_r)])
+
+
+def _overlap_fraction(ov, a, b) -> float:
+    """``float64(overlap) / float64(min(area, area))`` of float32 values, as ``_mesh_enforce_overlap_threshold`` divides."""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return float(np.float64(np.float32(ov)) / np.float64(min(np.float32(a), np.float32(b))))
+
+
+def mesh_nn_hop_cap(parent_areas, mean_cell_area: float) -> int:
+    """The hop cap of the nearest-neighbour partition (track.py:4061-4072)."""
+    biggest = np.float64(np.max(np.asarray(parent_areas, dtype=np.float32)))
+    return max(int(np.sqrt(float(biggest / mean_cell_area)) * 2.0), 20) * 2
+
+
+def plan_merge_step(t: int, children, ov_prev: np.ndarray, area_prev: dict, area_cur: dict, threshold: float, next_id: int):
+    """The merges of one timestep of one chunk, decided on the host from the step's tables (process_chunk,
+    track.py:3949-4056): ``children`` in processing order, ``ov_prev`` the ``[parent at t - 1, child at t, overlap area]``
+    rows of the two slices sorted lexicographically, ``area_prev`` / ``area_cur`` the float32 areas of the IDs of the two
+    slices, ``next_id`` the first temporary ID of the timestep.  Returns ``(merges, next_id)``; a merge is a dict with
+    ``child``, ``child_ids``, ``parents``, ``areas`` (overlaps) and ``parent_areas``.  The children's masks are disjoint and
+    their parents live in the previous slice, so the decisions do not depend on the partitions made in the same step.
+    :class:`TrackingError` where the reference's fixed-size tables would overflow."""
+    merges, n_new = [], 0
+    ov_prev = np.asarray(ov_prev)
+    for child in children:
+        rows = ov_prev[ov_prev[:, 1] == np.float32(child)] if len(ov_prev) else ov_prev
+        parents, areas, parent_areas = [], [], []
+        for par, _, ova in rows:  # candidate parents, ascending
+            if len(parents) >= MESH_MAX_PARENTS:
+                raise TrackingError("Too many parent objects for tracking",
+                                    details=f"Child {child} at timestep {t} has {len(parents)} parents (limit: {MESH_MAX_PARENTS})",
+                                    suggestions=["Increase overlap_threshold to reduce fragmentation",
+                                                 "Apply stronger area filtering"],
+                                    context={"child_id": int(child), "timestep": int(t), "limit": MESH_MAX_PARENTS})
+            if _overlap_fraction(ova, area_prev[int(par)], area_cur[int(child)]) < threshold:
+                continue
+            parents.append(int(par))
+            areas.append(np.float32(ova))
+            parent_areas.append(np.float32(area_prev[int(par)]))
+        if len(parents) < 2:
+            continue
+        k = len(parents)
+        if len(merges) >= MESH_MAX_MERGES:
+            raise TrackingError("Too many merge operations",
+                                details=f"Timestep {t} requires more than {MESH_MAX_MERGES} merges in one iteration",
+                                suggestions=["Increase area_filter_quartile to reduce small objects",
+                                             "Consider adjusting tracking parameters"],
+                                context={"timestep": int(t), "limit": MESH_MAX_MERGES})
+        if n_new + k - 1 > MESH_MAX_NEW_IDS:
+            raise TrackingError("Too many new objects in one timestep",
+                                details=f"Timestep {t} needs more than {MESH_MAX_NEW_IDS} new IDs in one iteration",
+                                context={"timestep": int(t), "limit": MESH_MAX_NEW_IDS})
+        if next_id + k - 2 > _I32_MAX:
+            raise TrackingError("Temporary object IDs do not fit int32", details=f"timestep {t}, next ID {next_id}")
+        n_new += k - 1
+        merges.append({"child": int(child), "child_ids": [int(child)] + list(range(next_id, next_id + k - 1)), "parents": parents,
+                       "areas": areas, "parent_areas": parent_areas})
+        next_id += k - 1
+    return merges, next_id
+
+
+def queue_after_step(merges, ov_next: np.ndarray, area_cur: dict, area_next: dict, threshold: float) -> List[int]:
+    """The IDs of the next slice that the new pieces of ``merges`` overlap by more than ``threshold`` (strictly,
+    track.py:4102-4117), in order of discovery, repeats included.  ``ov_next``: the ``[piece at t, ID at t + 1, overlap
+    area]`` rows after the partition; ``area_cur`` holds the non-empty pieces only."""
+    found = []
+    ov_next = np.asarray(ov_next)
+    if not len(ov_next):
+        return found
+    for m in merges:
+        for piece in m["child_ids"]:
+            if piece not in area_cur:
+                continue
+            for _, nxt, ova in ov_next[ov_next[:, 0] == np.float32(piece)]:
+                if _overlap_fraction(ova, area_cur[piece], area_next[int(nxt)]) > threshold:
+                    found.append(int(nxt))
+    return found
+
+
+def check_temporary_id_ranges(drawn: dict) -> None:
+    """``drawn``: timestep -> ``(first, end)`` of the temporary IDs it drew in one iteration.  The reference spaces the
+    timesteps' bases by ``max_merges * timechunks`` and silently aliases the IDs of two timesteps when one of them draws
+    past the next one's base (track.py:4440-4444); here that is a :class:`TrackingError`."""
+    ranges = sorted((v[0], v[1], t) for t, v in drawn.items() if v[1] > v[0])
+    for (b0, n0, t0), (b1, _, t1) in zip(ranges[:-1], ranges[1:]):
+        if n0 > b1:
+            raise TrackingError("Temporary object IDs of two timesteps collide",
+                                details=f"timestep {t0} drew IDs {b0}..{n0 - 1}, timestep {t1} starts at {b1}",
+                                suggestions=["Use longer time chunks", "Increase overlap_threshold to reduce fragmentation"],
+                                context={"timesteps": [int(t0), int(t1)]})
+
+
 def _not_built(what: str) -> ConfigurationError:
     return ConfigurationError(
         f"{what} is not built for unstructured grids: the split-and-merge stage is missing",
         details="built on a mesh: run_preprocess, compute_area, identify_objects, unique_ids_in_time, "
-                "calculate_object_properties, check_overlap_slice, find_overlapping_objects, enforce_overlap_threshold; the "
-                "reference's split_and_merge_objects_parallel and cluster_rename_objects_and_props (track.py:2809-3335, "
-                "3804-4826) are not",
-        suggestions=["Use the stage methods up to enforce_overlap_threshold", "Track gridded data"])
+                "calculate_object_properties, check_overlap_slice, find_overlapping_objects, enforce_overlap_threshold, "
+                "split_and_merge_objects_parallel; the reference's cluster_rename_objects_and_props on meshes "
+                "(track.py:2809-3335) and the end-to-end run over it are not",
+        suggestions=["Use the stage methods up to split_and_merge_objects_parallel", "Track gridded data"])
 
 
 class _MeshStages:
@@ -202,6 +311,7 @@ class _MeshStages:
         self.cell_area = ca.astype(np.float32)  # the reference's own copy (track.py:477)
         self._mesh_e, self._mesh_q = mesh_weight_tables(ca, self.lat, self.lon)
         self._mesh_dev_tables = None
+        self._mesh_u_dev = None
 
     # ------------------------------------------------------------------ device plumbing
     def _mesh_tables(self, eng):
@@ -456,6 +566,218 @@ class _MeshStages:
             logger.warning(f"Found {np.sum(fractions > 1.0)} overlap fractions > 1.0")
             logger.warning(f"Max overlap fraction: {fractions.max()}")
         return kept[fractions >= self.overlap_threshold]
+
+
+    # ------------------------------------------------------------------ split and merge (track.py:3804-4814)
+    def _mesh_unit_vectors_dev(self, eng):
+        """float64 ``[3, C]`` unit vectors of the cells on the engine's device, uploaded once."""
+        import torch
+
+        if getattr(self, "_mesh_u_dev", None) is None or self._mesh_u_dev.device != eng.device:
+            self._mesh_u_dev = torch.from_numpy(np.ascontiguousarray(mesh_unit_vectors(self.lat, self.lon))).to(eng.device)
+        return self._mesh_u_dev
+
+    def _mesh_merge_chunks(self) -> List[Tuple[int, int]]:
+        """The ``[start, end)`` ranges of the time chunks the merge stage walks; :class:`ConfigurationError` when no
+        chunking is known or a chunk has one step (the reference's ``squeeze()[1]`` breaks there, track.py:3885-3886)."""
+        chunks = self._time_chunks
+        if chunks is None:
+            raise ConfigurationError("split_and_merge_objects_parallel is not supported without a time chunking of data_bin",
+                                     details="the merges depend on the time chunks the stage walks (track.py:4452-4459)",
+                                     suggestions=["Pass timechunks=<steps per chunk>", "Chunk data_bin in time"])
+        if any(int(c) == 1 for c in chunks):
+            raise ConfigurationError("split_and_merge_objects_parallel is not supported with a time chunk of one step",
+                                     details=f"time chunks {tuple(chunks)}: every chunk needs its own previous and next step",
+                                     suggestions=["Choose timechunks so that no chunk, the last one included, has one step"])
+        out, s = [], 0
+        for c in chunks:
+            out.append((s, s + int(c)))
+            s += int(c)
+        return out
+
+    def split_and_merge_objects_parallel(self, object_id_field_unique, object_props):
+        """split_and_merge_objects_parallel (track.py:3804-4814), the reference's algorithm for unstructured grids, on the
+        device: objects with several parents are split among them -- by the nearest parent cell over the mesh edges
+        (``nn_partitioning=True``) or by the nearest parent centroid -- iterating over the time chunks of ``data_bin`` until no
+        new merging object turns up.  ``object_id_field_unique``: int32 IDs ``(time, x)`` unique in time
+        (:meth:`unique_ids_in_time`); ``object_props``: their ``ID`` and ``area``.  Returns ``(object_id_field, object_props,
+        overlap_objects_list (n, 2) int32, merge_events)``.  The ID field stays on the device; per timestep with pending
+        children only the overlap and property tables of two slices reach the host.  Areas and fractions follow the
+        fixed-point contract of this module, the nearest centroid is decided on float64 unit vectors."""
+        import torch
+
+        from .xr_compat import DataArray, Dataset
+
+        if not self.unstructured_grid:
+            raise ConfigurationError("split_and_merge_objects_parallel is the merge stage of unstructured grids",
+                                     details="gridded data is tracked by the sequential algorithm (track.py:3337-3802)",
+                                     suggestions=["Call split_and_merge_objects on gridded data"])
+        ranges = self._mesh_merge_chunks()
+        timechunks = ranges[0][1] - ranges[0][0]
+        thr = self.overlap_threshold
+        eng = self._engine()
+        ids = self._mesh_device_ids(object_id_field_unique, eng)
+        T, Cn = (int(k) for k in ids.shape)
+        if ranges[-1][1] != T:
+            raise create_data_validation_error("The ID field does not cover the time axis of data_bin",
+                                               details=f"{T} timesteps, time chunks of data_bin {tuple(self._time_chunks)}")
+        self._check_fits(eng, {"ID field int32": 4 * T * Cn, "iteration snapshot int32": 4 * T * Cn,
+                               "two-slice views int32": 8 * Cn, "unit vectors float64": 24 * Cn,
+                               "owner words uint32": 4 * Cn}, "tracker.split_and_merge_objects_parallel")
+        ids = ids.clone()
+        q, nbr, _ = self._mesh_tables(eng)
+        u = self._mesh_unit_vectors_dev(eng)
+        e = self._mesh_e
+        mean_cell_area = float(self.cell_area.mean())
+        zeros = torch.zeros(Cn, dtype=torch.int32, device=eng.device)
+        stats = self._merge_stats = {"iterations": 0, "partitions": 0, "hops": 0, "launches": 0, "reads": 0, "steps": 0,
+                                     "partition_s": 0.0, "tables_s": 0.0}
+
+        def tables(a, b):
+            """Overlap rows and per-slice areas (and centroids of the first slice) of the slices a, b."""
+            import time
+
+            t0 = time.perf_counter()
+            pair = torch.stack([a, b])
+            ov = eng.mesh_overlap_pairs(pair, q, e)
+            m = eng.mesh_object_moments(pair, q, e)
+            first = m["t"] == 0
+            area_a = dict(zip(m["id"][first].tolist(), m["area"][first]))
+            area_b = dict(zip(m["id"][~first].tolist(), m["area"][~first]))
+            cen_a = dict(zip(m["id"][first].tolist(), m["centroid"][:, first].T))
+            stats["tables_s"] += time.perf_counter() - t0
+            return ov, area_a, area_b, cen_a
+
+        ov = self._mesh_enforce_overlap_threshold(eng.mesh_overlap_pairs(ids, q, e) if T > 1 else np.zeros((0, 3), np.float32),
+                                                  object_props)
+        uc, cc = np.unique(ov[:, 1], return_counts=True) if len(ov) else (np.zeros(0), np.zeros(0, np.int64))
+        merging = set(int(v) for v in uc[cc > 1])
+        prop_ids = np.asarray(object_props["ID"].values)
+        counter = int(prop_ids.max()) + 1 if prop_ids.size else 1
+        processed = set()
+        merges = []
+        iteration = 0
+        while merging and iteration < self.max_iteration:
+            spans = eng.id_spans(ids)
+            per_t = {}
+            for cid in sorted(merging):  # ascending ID: the reference iterates a Python set (DESIGN.md, READING)
+                if spans is not None and cid < len(spans[0]) and spans[1][cid] >= 0:
+                    per_t.setdefault(int(spans[0][cid]), []).append(cid)
+            max_merges = max((len(v) for v in per_t.values()), default=0)
+            bases = np.arange(T, dtype=np.int64) * max_merges * timechunks + counter
+            if int(bases.max()) > _I32_MAX - MESH_MAX_NEW_IDS:
+                raise TrackingError("Temporary object IDs do not fit int32",
+                                    details=f"{T} timesteps x {max_merges} merging objects x chunks of {timechunks} above ID {counter}",
+                                    suggestions=["Use shorter time chunks", "Track a shorter record"])
+            snap = ids.clone()
+            it_merges, final, drawn = [], [], {}
+            for s, end in ranges:
+                queue = {t: list(per_t.get(t, [])) for t in range(s, end)}
+                chunk_final = []
+                for t in range(s, end):
+                    if not queue[t]:
+                        continue
+                    stats["steps"] += 1
+                    m1 = (snap[s - 1] if s > 0 else zeros) if t == s else ids[t - 1]
+                    p1 = (snap[end] if end < T else zeros) if t == end - 1 else ids[t + 1]
+                    cur = ids[t]
+                    ov_prev, area_prev, area_cur, cen_prev = tables(m1, cur)
+                    plan, nxt = plan_merge_step(t, queue[t], ov_prev, area_prev, area_cur, thr, int(bases[t]))
+                    if not plan:
+                        continue
+                    drawn[t] = (int(bases[t]), nxt)
+                    self._mesh_partition_step(eng, cur, m1, nbr, u, plan, cen_prev, mean_cell_area, stats)
+                    ov_next, area_now, area_next, _ = tables(cur, p1)
+                    found = queue_after_step(plan, ov_next, area_now, area_next, thr)
+                    it_merges.extend((t, m["child_ids"], m["parents"], m["areas"]) for m in plan)
+                    if t < end - 1:
+                        for c in found:
+                            if c not in queue[t + 1]:
+                                queue[t + 1].append(c)
+                    else:
+                        for c in found:
+                            if c not in chunk_final:
+                                if len(chunk_final) >= MESH_MAX_MERGES:
+                                    raise TrackingError("Excessive merge operations detected",
+                                                        details=f"more than {MESH_MAX_MERGES} merging objects leave the chunk that "
+                                                                f"ends at timestep {t}",
+                                                        context={"timestep": int(t), "limit": MESH_MAX_MERGES})
+                                chunk_final.append(c)
+                final.extend(chunk_final)
+            check_temporary_id_ranges(drawn)
+            temp = sorted({c for _, ch, _, _ in it_merges for c in ch if c >= counter})
+            lookup = {tid: counter + k for k, tid in enumerate(temp)}
+            if temp:
+                eng.relabel(ids, np.array([lookup[k] for k in temp], np.int32), np.array(temp, np.int32))
+            counter += len(temp)
+            for t, ch, pa, ar in it_merges:
+                merges.append((t, [lookup.get(c, c) for c in ch], [lookup.get(p, p) for p in pa], ar))
+            final_mapped = set(lookup.get(c, c) for c in final)
+            merging = final_mapped - processed
+            processed |= final_mapped
+            iteration += 1
+            del snap
+        stats["iterations"] = iteration
+        if iteration == self.max_iteration:
+            raise TrackingError("Maximum iterations reached in tracking algorithm",
+                                details=f"Algorithm failed to converge after {self.max_iteration} iterations",
+                                suggestions=["Increase max_iteration parameter",
+                                             "Increase area_filter_quartile to reduce small objects",
+                                             "Consider adjusting tracking parameters"],
+                                context={"max_iteration": self.max_iteration, "reached_iteration": iteration})
+
+        props = self._mesh_object_properties(self._mesh_wrap(ids, "ID_field"), ["area", "centroid"])
+        pairs = self._mesh_enforce_overlap_threshold(eng.mesh_overlap_pairs(ids, q, e) if T > 1 else np.zeros((0, 3), np.float32),
+                                                     props)[:, :2].astype(np.int32)
+        field = DataArray(self._ids_to_host(eng, ids), dims=(self.timedim, self.xdim),
+                          coords={self.timedim: (self.timedim, self.time_values[:T])}, name="ID_field")
+        return field, props, pairs, self._mesh_merges_dataset(merges)
+
+    def _mesh_partition_step(self, eng, cur, m1, nbr, u, plan, cen_prev, mean_cell_area: float, stats: dict) -> None:
+        """Partition the children of ``plan`` in the slice ``cur`` among their parents in ``m1``, in place."""
+        import time
+
+        t0 = time.perf_counter()
+        vectors = []
+        for m in plan:
+            cen = np.array([cen_prev[p] for p in m["parents"]], dtype=np.float32)  # float32 (lat, lon) of the contract
+            vectors.append(mesh_unit_vectors(cen[:, 0], cen[:, 1]))
+        if self.nn_partitioning:
+            for m, pv in zip(plan, vectors):
+                r = eng.mesh_partition_nn(cur, m1, nbr, m["child"], m["parents"], pv, m["child_ids"],
+                                          mesh_nn_hop_cap(m["parent_areas"], mean_cell_area), u)
+                stats["hops"] += r["hops"]
+                stats["launches"] += r["launches"]
+                stats["reads"] += r["reads"]
+        else:
+            order = np.argsort([m["child"] for m in plan], kind="stable")
+            off = np.concatenate([[0], np.cumsum([len(plan[k]["parents"]) for k in order])])
+            eng.mesh_partition_centroid(cur, [plan[k]["child"] for k in order], off, np.concatenate([vectors[k] for k in order], axis=1),
+                                        [i for k in order for i in plan[k]["child_ids"]], u)
+            stats["launches"] += 1
+        stats["partitions"] += len(plan)
+        eng.sync()
+        stats["partition_s"] += time.perf_counter() - t0
+
+    def _mesh_merges_dataset(self, merges):
+        """merge_events of track.py:4751-4796: ``merges`` holds ``(timestep, child_ids, parent_ids, overlap areas)``."""
+        from .xr_compat import DataArray, Dataset
+
+        mp = max((len(m[2]) for m in merges), default=1)
+        mc = max((len(m[1]) for m in merges), default=1)
+        P = np.full((len(merges), mp), -1, np.int32)
+        Cc = np.full((len(merges), mc), -1, np.int32)
+        A = np.full((len(merges), mp), -1, np.float32)
+        for i, (_, ch, pa, ar) in enumerate(merges):
+            P[i, :len(pa)], Cc[i, :len(ch)], A[i, :len(ar)] = pa, ch, ar
+        times = self.time_values[np.array([m[0] for m in merges], dtype=np.int64)]
+        return Dataset({"parent_IDs": DataArray(P, dims=("merge_ID", "parent_idx")),
+                        "child_IDs": DataArray(Cc, dims=("merge_ID", "child_idx")),
+                        "overlap_areas": DataArray(A, dims=("merge_ID", "parent_idx")),
+                        "merge_time": DataArray(times, dims=("merge_ID",)),
+                        "n_parents": DataArray(np.array([len(m[2]) for m in merges], np.int8), dims=("merge_ID",)),
+                        "n_children": DataArray(np.array([len(m[1]) for m in merges], np.int8), dims=("merge_ID",))},
+                       attrs={"fill_value": -1})
 
 
 def _is_host(da) -> bool:
