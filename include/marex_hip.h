@@ -506,6 +506,12 @@ int marex_overlap_pairs_i32(marex_ctx* ctx, const int32_t* ids, int64_t T, int64
  *   (word 0 collects the low 32 bits of the partial sums and may itself exceed 2^32).
  * marex_mesh_area_i64: out[t] = sum over c of data[t][c] != 0 ? q0[c] : 0, data uint8 [T][C]; out uint64 [T], zeroed
  *   first.
+ * marex_mesh_event_rename_i64 (cluster_rename_objects_and_props on a mesh: the apply_ufunc map, process_timestep and
+ *   calculate_area_centroid_for_slice, track.py:2908-2926, 2948-2989, 3161-3210, in one pass): in place, ids[t][c] = ev =
+ *   lut[v] for 0 < v = ids[t][c] < lut_len, else 0; an ev outside 1 .. n_ev counts as background too.  For ev > 0 the
+ *   dense slot s = t * n_ev + ev - 1 takes acc[s][0..4] += 1, q[0..3][c] and gid[s] = max(gid[s], v): the largest
+ *   original ID under the slot.  lut: int32 [lut_len]; acc [T * n_ev][5] and gid int32 [T * n_ev] are zeroed first.
+ *   -1 for a null pointer or an empty shape, -4 for C or T of 2^31 - 1 or more.
  * All are asynchronous on the context's stream. */
 int marex_label_mesh_rank_i32(marex_ctx* ctx, const int32_t* labels, int64_t T, int64_t C, int32_t* rank, int32_t* ids,
                               int32_t* n_t);
@@ -517,6 +523,8 @@ int marex_mesh_overlap_pairs_i64(marex_ctx* ctx, const int32_t* ids, int64_t T, 
                                  uint64_t* keys, uint64_t* sums, uint64_t* stats, int64_t out_cap, uint64_t* out_keys,
                                  uint64_t* out_sums);
 int marex_mesh_area_i64(marex_ctx* ctx, const uint8_t* data, int64_t T, int64_t C, const int64_t* q0, uint64_t* out);
+int marex_mesh_event_rename_i64(marex_ctx* ctx, int32_t* ids, int64_t T, int64_t C, const int32_t* lut, int64_t lut_len,
+                                int n_ev, const int64_t* q, uint64_t* acc, int32_t* gid);
 
 /* Stages of the merge tracker on grids (tracker.split_and_merge_objects / consolidate_object_ids /
  * cluster_rename_objects_and_props, marEx/track.py:2554-3802).  Slices are int32 [ny][nx], fields int32 [T][ny][nx];

@@ -103,6 +103,7 @@ PROTOTYPES = {
     "marex_mesh_object_moments_i64": (_i32, [_p, _p, _i64, _i64, _p, _p, _p, _i64, _p]),
     "marex_mesh_overlap_pairs_i64": (_i32, [_p, _p, _i64, _i64, _p, _i64, _p, _p, _p, _i64, _p, _p]),
     "marex_mesh_area_i64": (_i32, [_p, _p, _i64, _i64, _p, _p]),
+    "marex_mesh_event_rename_i64": (_i32, [_p, _p, _i64, _i64, _p, _i64, _i32, _p, _p, _p]),
     "marex_mesh_partition_centroid_i32": (_i32, [_p, _p, _i64, _p, _i32, _p, _p, _p, _i32, _p]),
     "marex_mesh_nn_seed_i32": (_i32, [_p, _p, _p, _i64, _i32, _p, _i32, _p, _p]),
     "marex_mesh_nn_hops_i32": (_i32, [_p, _p, _p, _i64, _i32, _i32, _i32, _i32, _i32, _p, _p]),

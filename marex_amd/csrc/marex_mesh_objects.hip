@@ -250,6 +250,105 @@ extern "C" int marex_mesh_object_moments_i64(marex_ctx* ctx, const int32_t* ids,
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------------ events: rename and accumulate
+// One pass over the field, in place: ids[t][c] = ev = lut[v] for 0 < v = ids[t][c] < lut_len (anything else, and an ev
+// outside 1..n_ev: 0), and for ev > 0 the dense slot s = t n_ev + ev - 1 takes acc[s][0..4] += 1, q0..q3[c] and
+// gid[s] = max(gid[s], v).  k_mesh_moments with the event as the group key: a cell is read and written by one lane only,
+// the run of an event is carried across the pieces of the wave and flushed once.
+__global__ void __launch_bounds__(256)
+k_mesh_event_rename(int* ids, long T, long C, const int* __restrict__ lut, long lut_len, int n_ev,
+                    const long long* __restrict__ q, u64* __restrict__ acc, int* __restrict__ gid) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long rw = mobj_piece0(wave);
+    for (long t = blockIdx.y; t < T; t += gridDim.y) {
+        int* row = ids + t * C;
+        int v[MOBJ_ITERS], ev[MOBJ_ITERS];
+#pragma unroll
+        for (int k = 0; k < MOBJ_ITERS; ++k) {
+            const long r = rw + 64 * k + lane;
+            v[k] = r < C ? row[r] : 0;
+        }
+#pragma unroll
+        for (int k = 0; k < MOBJ_ITERS; ++k) {
+            const long r = rw + 64 * k + lane;
+            int e = (v[k] > 0 && (long)v[k] < lut_len) ? lut[v[k]] : 0;
+            e = (e > 0 && e <= n_ev) ? e : 0;  // the slot index below never comes from an unchecked value
+            ev[k] = e;
+            if (r < C && e != v[k]) row[r] = e;
+        }
+        int cur = 0, big = 0;
+        long long n = 0, s0 = 0, s1 = 0, s2 = 0, s3 = 0;
+        auto flush = [&]() {
+            if (cur > 0 && lane == 0) {
+                const size_t s = (size_t)t * (size_t)n_ev + (size_t)(cur - 1);
+                u64* p = acc + s * MOBJ_MOM;
+                atomicAdd(p + 0, (u64)n);
+                atomicAdd(p + 1, (u64)s0);
+                atomicAdd(p + 2, (u64)s1);
+                atomicAdd(p + 3, (u64)s2);
+                atomicAdd(p + 4, (u64)s3);
+                atomicMax(gid + s, big);
+            }
+        };
+#pragma unroll  // v[k], ev[k] must stay in registers: no dynamic indexing
+        for (int k = 0; k < MOBJ_ITERS; ++k) {
+            const long r0 = rw + 64 * k;
+            if (r0 >= C) break;  // wave-uniform
+            const int id = ev[k];
+            u64 todo = __ballot(id > 0);
+            if (!todo) continue;
+            long long q0 = 0, q1 = 0, q2 = 0, q3 = 0;
+            if (id > 0) {  // id > 0 implies r0 + lane < C
+                const long c = r0 + lane;
+                q0 = q[c];
+                q1 = q[C + c];
+                q2 = q[2 * C + c];
+                q3 = q[3 * C + c];
+            }
+            while (todo) {
+                const int lead = __ffsll((long long)todo) - 1;
+                const int il = __shfl(id, lead, 64);
+                const u64 same = __ballot(id == il) & todo;
+                todo &= ~same;
+                const bool in = (same >> lane) & 1ull;
+                const long long g0 = mobj_wave_sum_i64(in ? q0 : 0), g1 = mobj_wave_sum_i64(in ? q1 : 0),
+                                g2 = mobj_wave_sum_i64(in ? q2 : 0), g3 = mobj_wave_sum_i64(in ? q3 : 0);
+                const int gm = wave_max_i32(in ? v[k] : 0);  // v > 0 wherever ev > 0
+                if (il != cur) {
+                    flush();
+                    cur = il;
+                    n = s0 = s1 = s2 = s3 = 0;
+                    big = 0;
+                }
+                n += __popcll(same);
+                s0 += g0;
+                s1 += g1;
+                s2 += g2;
+                s3 += g3;
+                big = gm > big ? gm : big;
+            }
+        }
+        flush();
+    }
+}
+
+extern "C" int marex_mesh_event_rename_i64(marex_ctx* ctx, int32_t* ids, int64_t T, int64_t C, const int32_t* lut,
+                                           int64_t lut_len, int n_ev, const int64_t* q, uint64_t* acc, int32_t* gid) {
+    if (!ctx) return -1;
+    if (!ids || !lut || !q || !acc || !gid || T <= 0 || C <= 0 || lut_len <= 0 || n_ev <= 0)
+        return fail(ctx, -1, "marex_mesh_event_rename_i64: null pointer or empty shape");
+    if (C >= 2147483647L || T >= 2147483647L) return fail(ctx, -4, "marex_mesh_event_rename_i64: a slice or the time axis has 2^31 - 1 or more entries");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    LaunchTimer lt(ctx, MAREX_K_MORPH);
+    const size_t slots = (size_t)T * (size_t)n_ev;
+    HIP_TRY(ctx, hipMemsetAsync(acc, 0, slots * MOBJ_MOM * sizeof(u64), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(gid, 0, slots * sizeof(int), ctx->stream));
+    hipLaunchKernelGGL(k_mesh_event_rename, mobj_slice_grid(T, C), dim3(256), 0, ctx->stream, ids, (long)T, (long)C, lut,
+                       (long)lut_len, n_ev, (const long long*)q, (u64*)acc, gid);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------------------ weighted overlaps
 // key = a << 32 | b for every cell with a = ids[t] > 0 and b = ids[t + 1] > 0; each run of equal keys adds the sum of
 // q0 over its cells to the key's entry of an open-addressing table (linear probing, CAS on the key, 0 = empty);

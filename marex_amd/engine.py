@@ -19,6 +19,7 @@ from . import _lib
 from .binning import BinTable
 from .calendar import N_DOY, CalendarPlan
 from .exceptions import ConfigurationError, ProcessingError, TrackingError
+from .track_mesh import mesh_moments_finish
 
 
 import logging
@@ -956,15 +957,34 @@ class HotPath:
         mom_h = mom[:n].cpu().numpy()
         order = np.argsort((tid_h[:, 0] << 32) | tid_h[:, 1])  # (t, id) order: the device compacts in no particular order
         tid_h, mom_h = tid_h[order], mom_h[order]
-        s0, s1, s2, s3 = (mom_h[:, k].astype(np.float64) for k in range(1, 5))
-        norm = np.sqrt(s1 * s1 + s2 * s2 + s3 * s3)
-        norm = np.where(norm > 0, norm, 1.0)
-        lat = np.degrees(np.arcsin(np.clip(s3 / norm, -1.0, 1.0)))
-        lon = np.degrees(np.arctan2(s2 / norm, s1 / norm))
-        lon = np.where(lon > 180.0, lon - 360.0, np.where(lon < -180.0, lon + 360.0, lon))  # track.py:2226-2230
-        out.update(t=tid_h[:, 0], id=tid_h[:, 1], cells=mom_h[:, 0].copy(), area=np.ldexp(s0, -int(e)).astype(np.float32),
-                   centroid=np.stack([lat, lon]).astype(np.float32))
+        area, centroid = mesh_moments_finish(mom_h, e)
+        out.update(t=tid_h[:, 0], id=tid_h[:, 1], cells=mom_h[:, 0].copy(), area=area, centroid=centroid)
         return out
+
+    def mesh_event_rename(self, ids: torch.Tensor, lut, n_ev: int, q: torch.Tensor, e: int) -> Dict[str, np.ndarray]:
+        """The device pass of cluster_rename_objects_and_props on a mesh (track.py:2908-2989, 3161-3210), in one kernel and
+        in place: ``ids`` int32 ``[T, C]`` -> ``lut[id]`` for ``0 < id < len(lut)``, else 0 (``lut``: int32 event numbers
+        0..n_ev); per (timestep, event) ``mom`` int64 ``[T, n_ev, 5]`` (cells and the sums of ``q[0..3]`` over the event's
+        cells) and ``gid`` int32 ``[T, n_ev]`` (the largest original ID under the slot, 0 when the event is absent).
+        ``q``, ``e``: the weight table and its exponent, as in every mesh call; the device adds integers and does not need
+        ``e`` -- :func:`marex_amd.track_mesh.mesh_moments_finish` does, to turn ``mom`` into areas and centroids."""
+        T, Cn = self._ids_check(ids)
+        self._mesh_weights_check(q, Cn, "mesh_event_rename")
+        n_ev, e = int(n_ev), int(e)
+        lut_h = np.asarray(lut)
+        if lut_h.dtype != np.int32 or lut_h.ndim != 1 or lut_h.size == 0:
+            raise ProcessingError("mesh_event_rename: the table must be a non-empty int32 vector",
+                                  details=f"got {lut_h.dtype} {lut_h.shape}")
+        if n_ev <= 0 or int(lut_h.max()) > n_ev:
+            raise ProcessingError("mesh_event_rename: the table must map to events 0..n_ev, n_ev > 0",
+                                  details=f"largest entry {int(lut_h.max())}, n_ev={n_ev}")
+        slots = T * n_ev
+        self._check_fits(44 * slots + 4 * lut_h.size, "mesh event properties",
+                         f"{T} x {n_ev} dense (timestep, event) slots of 44 bytes and a table of {lut_h.size} IDs")
+        acc = self._buf(None, "mev_acc", (slots, 5), torch.int64, self.device)
+        gid = self._buf(None, "mev_gid", (slots,), torch.int32, self.device)
+        self.call("marex_mesh_event_rename_i64", ids, T, Cn, self._dev(lut_h), lut_h.size, n_ev, q, acc, gid)
+        return {"mom": acc.cpu().numpy().reshape(T, n_ev, 5), "gid": gid.cpu().numpy().reshape(T, n_ev)}
 
     def mesh_overlap_pairs(self, ids: torch.Tensor, q: torch.Tensor, e: int) -> np.ndarray:
         """``(n, 3)`` float32 ``[id at t, id at t + 1, overlap area]`` over every t < T - 1 of ``ids`` int32 ``[T, C]``: the area

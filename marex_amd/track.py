@@ -206,7 +206,7 @@ class _Props:
 
 class tracker(_MeshStages):  # noqa: N801 -- the reference's public name (marEx.tracker)
     """Identify extreme events as connected regions in (time, y, x) of a binary field on a grid; on an unstructured mesh,
-    the stages of the merge tracker up to and including split-and-merge.
+    the merge tracker from the pre-processing to the events.
 
     The constructor takes the reference's arguments (track.py:323-348).  Supported here: gridded data, with
     ``allow_merging=False`` (the reference's "basic" tracker) and with ``allow_merging=True`` (the default: merging and
@@ -226,12 +226,14 @@ class tracker(_MeshStages):  # noqa: N801 -- the reference's public name (marEx.
     (``(n, 3)`` float32 ``[id, id, overlap area]``), :meth:`enforce_overlap_threshold` and
     :meth:`split_and_merge_objects_parallel` (the reference's merge algorithm for meshes: it walks the time chunks of
     ``data_bin`` or of ``timechunks=``, no chunk of one step, and raises :class:`TrackingError` after ``max_iteration``
-    iterations).  Areas are integer sums of the fixed-point weights of :func:`mesh_weight_tables`: bitwise reproducible,
-    and within the rounding bound of the reference's float32 sums.  Cluster renaming and the end-to-end run are not built
-    on a mesh: :meth:`run`, :meth:`run_tracking`, :meth:`track_objects`, :meth:`split_and_merge_objects` (the gridded
-    algorithm), :meth:`consolidate_object_ids` and :meth:`cluster_rename_objects_and_props` raise
-    :class:`ConfigurationError` there.  The constructor needs no time chunking on a mesh (only
-    :meth:`split_and_merge_objects_parallel` does); ``temp_dir`` is not required (nothing is written to disk).
+    iterations), :meth:`cluster_rename_objects_and_props` (events with float32 area and centroid on the sphere per
+    timestep) and, over them, :meth:`track_objects`, :meth:`run_tracking` (always through :meth:`track_objects`, as in the
+    reference) and :meth:`run`.  Areas are integer sums of the fixed-point weights of :func:`mesh_weight_tables`: bitwise
+    reproducible, and within the rounding bound of the reference's float32 sums.  The constructor needs no time chunking
+    on a mesh, but every stage from split-and-merge on does: without one, :meth:`run`, :meth:`run_tracking`,
+    :meth:`track_objects` and :meth:`cluster_rename_objects_and_props` raise :class:`ConfigurationError` before any device
+    work.  :meth:`split_and_merge_objects` and :meth:`consolidate_object_ids` are the gridded algorithm and raise
+    :class:`ConfigurationError` on a mesh.  ``temp_dir`` is not required (nothing is written to disk).
 
     ``grid_resolution`` and ``cell_areas`` weight the final area and centroid of merge tracking (object properties count
     cells, as the reference's do, track.py:1499-1518, 2337).  Accepted and ignored: ``temp_dir``,
@@ -542,8 +544,9 @@ class tracker(_MeshStages):  # noqa: N801 -- the reference's public name (marEx.
         """``run_preprocess`` -> ``run_tracking`` -> ``run_stats_attributes``; returns the events Dataset, and with
         ``return_merges`` and merging also the merge events: ``(events_ds, merges_ds)`` (track.py:1162-1232)."""
         if self.unstructured_grid:
-            raise _not_built("tracker.run")
-        if self.allow_merging:
+            self._mesh_need_chunks("tracker.run")
+            self._mesh_merge_chunks()  # a chunk of one step is refused before the pre-processing, not after it
+        if self.allow_merging or self.unstructured_grid:
             self._check_size(self.data_bin.shape)
         else:
             self._check_memory(self.data_bin.shape)
@@ -605,8 +608,8 @@ class tracker(_MeshStages):  # noqa: N801 -- the reference's public name (marEx.
         from .xr_compat import DataArray, Dataset
 
         if self.unstructured_grid:
-            raise _not_built("tracker.run_tracking")
-        if self.allow_merging:  # track.py:1388-1390
+            self._mesh_need_chunks("tracker.run_tracking")
+        if self.allow_merging or self.unstructured_grid:  # track.py:1388-1390
             return self.track_objects(data_bin_preprocessed)
         ids, _, N_events_final = self.identify_objects(data_bin_preprocessed, time_connectivity=True)
         # IDs are >= 0 by construction (the reference's `where(ID_field > 0, other=0)` is a no-op here)
@@ -649,7 +652,8 @@ class tracker(_MeshStages):  # noqa: N801 -- the reference's public name (marEx.
 
     def _latlon_coords(self) -> dict:
         """The input's lat / lon as coordinate entries ``name -> (dims, host values)``."""
-        return {self.ycoord: (_coord_dims(self.lat_init, (self.ydim,)), _host(self.lat_init)),
+        ydim = self.xdim if self.unstructured_grid else self.ydim  # on a mesh lat runs over the cells too
+        return {self.ycoord: (_coord_dims(self.lat_init, (ydim,)), _host(self.lat_init)),
                 self.xcoord: (_coord_dims(self.lon_init, (self.xdim,)), _host(self.lon_init))}
 
     def _remap_coordinates(self, events_ds):
@@ -1119,11 +1123,14 @@ class tracker(_MeshStages):  # noqa: N801 -- the reference's public name (marEx.
         tpos = {v: i for i, v in enumerate(self.time_values.tolist())}
         return np.array([tpos[v] for v in np.asarray(merges_ds["merge_time"].values).tolist()], dtype=np.int64)
 
-    def _cluster_rename(self, eng, ids, ny: int, nx: int, overlaps, merges_ds, merge_tidx):
-        """cluster_rename_objects_and_props (track.py:2809-3335), grids, with ``ids`` on the device (relabelled in place
-        to event IDs)."""
-        import torch
-
+    def _cluster_rename_events(self, eng, ids, overlaps, merges_ds, merge_tidx, device_pass, field_dims, field_shape):
+        """cluster_rename_objects_and_props (track.py:2809-3335) around the device pass, for grids and meshes alike: the
+        events are the connected components of the overlap pairs over the IDs of the field and of the pair list, numbered
+        by their smallest ID; ``device_pass(lut, N)`` relabels ``ids`` (int32 ``[T, C]`` on the device) in place through the
+        ID -> event table and returns ``(gid, area, lat, lon)`` over the ``[T, N]`` (timestep, event) slots -- the largest
+        original ID (0: the event is absent), float32 area and the centroid in degrees, whatever they hold where the event
+        is absent.  Presence, time_start / time_end and the merge ledger follow from ``gid`` and ``merges_ds``.  Returns
+        ``(events Dataset, N)``."""
         from .xr_compat import DataArray, Dataset
 
         T = ids.shape[0]
@@ -1140,42 +1147,18 @@ class tracker(_MeshStages):  # noqa: N801 -- the reference's public name (marEx.
         lut[valid[keep]] = comp[keep] + 1
         coords = {self.timecoord: (self.timedim, self.time_values), "ID": ("ID", np.arange(1, N + 1, dtype=np.int32))}
         if N == 0:
-            mom = np.zeros((T, 0, 5), np.int64)
             gid = np.zeros((T, 0), np.int32)
-            ev = ids
+            area_all, lat_all, lon_all = (np.zeros((T, 0), np.float32) for _ in range(3))
         else:
-            orig = ids.clone()
-            eng.relabel(ids, lut)
-            ev = ids
-            w = None if self._cell_weights is None else torch.from_numpy(self._cell_weights.reshape(-1)).to(eng.device)
-            r = eng.event_moments(ev, orig, ny, nx, N, w)
-            mom, gid = r["mom"], r["gid"]
-            del orig
+            gid, area_all, lat_all, lon_all = device_pass(lut, N)
+        ev = ids
         pres = gid > 0
         t_first = np.argmax(pres, axis=0)
         t_last = T - 1 - np.argmax(pres[::-1], axis=0)
-        cnt = mom[..., 0]
-        with np.errstate(invalid="ignore", divide="ignore"):
-            if self._cell_weights is None:
-                tot = cnt.astype(np.float64)
-                sy, sx, sxs = mom[..., 1], mom[..., 2], mom[..., 3]
-                area = np.where(pres, cnt.astype(np.float32), np.float32(np.nan))
-            else:
-                wm = r["wmom"] if N else np.zeros((T, 0, 4))
-                tot = wm[..., 0].astype(np.float32).astype(np.float64)  # the reference's float32 np.sum of the cell areas
-                sy, sx, sxs = wm[..., 1], wm[..., 2], wm[..., 3]
-                area = np.where(pres, wm[..., 0].astype(np.float32), np.float32(np.nan))
-            cy = sy / tot
-            cx = sx / tot
-            if not self.regional_mode:
-                seam = (mom[..., 4] & 3) == 3
-                cxs = sxs / tot
-                cxs = np.where(cxs < 0, cxs + nx, cxs)
-                cx = np.where(seam, cxs, cx)
-        lat, lon = np.asarray(self.lat), np.asarray(self.lon)
+        area = np.where(pres, area_all, np.float32(np.nan))
         cen = np.full((2, T, N), np.nan, np.float32)
-        cen[0][pres] = np.interp(cy[pres], np.arange(len(lat)), lat)
-        cen[1][pres] = np.interp(cx[pres], np.arange(len(lon)), lon)
+        cen[0][pres] = lat_all[pres]
+        cen[1][pres] = lon_all[pres]
         P = np.asarray(merges_ds["parent_IDs"].values)
         ledger = np.full((T, N + 1, P.shape[1]), -1, np.int32)
         newP = lut[np.clip(np.where(P > 0, P, 0), 0, lut.size - 1)]
@@ -1186,7 +1169,7 @@ class tracker(_MeshStages):  # noqa: N801 -- the reference's public name (marEx.
         idc = {"ID": coords["ID"]}
         tid = dict(tc, **idc)
         data = {
-            "ID_field": DataArray(ev.cpu().numpy().reshape(T, ny, nx), dims=self._out_dims(), coords=tc),
+            "ID_field": DataArray(self._ids_to_host(eng, ev).reshape(field_shape), dims=field_dims, coords=tc),
             "global_ID": DataArray(gid, dims=(self.timedim, "ID"), coords=tid),
             "area": DataArray(area, dims=(self.timedim, "ID"), coords=tid),
             "centroid": DataArray(cen, dims=("component", self.timedim, "ID"),
@@ -1197,6 +1180,43 @@ class tracker(_MeshStages):  # noqa: N801 -- the reference's public name (marEx.
             "merge_ledger": DataArray(ledger[:, 1:, :], dims=(self.timedim, "ID", "sibling_ID"), coords=tid),
         }
         return Dataset(data), N
+
+    def _cluster_rename(self, eng, ids, ny: int, nx: int, overlaps, merges_ds, merge_tidx):
+        """cluster_rename_objects_and_props (track.py:2809-3335), grids, with ``ids`` on the device (relabelled in place
+        to event IDs): relabel, then the event moments over the relabelled field and a copy of the original one."""
+        import torch
+
+        T = ids.shape[0]
+
+        def device_pass(lut, N):
+            orig = ids.clone()
+            eng.relabel(ids, lut)
+            w = None if self._cell_weights is None else torch.from_numpy(self._cell_weights.reshape(-1)).to(eng.device)
+            r = eng.event_moments(ids, orig, ny, nx, N, w)
+            del orig
+            mom = r["mom"]
+            cnt = mom[..., 0]
+            with np.errstate(invalid="ignore", divide="ignore"):
+                if self._cell_weights is None:
+                    tot = cnt.astype(np.float64)
+                    sy, sx, sxs = mom[..., 1], mom[..., 2], mom[..., 3]
+                    area = cnt.astype(np.float32)
+                else:
+                    wm = r["wmom"]
+                    tot = wm[..., 0].astype(np.float32).astype(np.float64)  # the reference's float32 np.sum of the cell areas
+                    sy, sx, sxs = wm[..., 1], wm[..., 2], wm[..., 3]
+                    area = wm[..., 0].astype(np.float32)
+                cy = sy / tot
+                cx = sx / tot
+                if not self.regional_mode:
+                    seam = (mom[..., 4] & 3) == 3
+                    cxs = sxs / tot
+                    cxs = np.where(cxs < 0, cxs + nx, cxs)
+                    cx = np.where(seam, cxs, cx)
+            lat, lon = np.asarray(self.lat), np.asarray(self.lon)
+            return r["gid"], area, np.interp(cy, np.arange(len(lat)), lat), np.interp(cx, np.arange(len(lon)), lon)
+
+        return self._cluster_rename_events(eng, ids, overlaps, merges_ds, merge_tidx, device_pass, self._out_dims(), (T, ny, nx))
 
     def _remap_merge_coordinates(self, events_ds):
         """_remap_coordinates (track.py:978-1021) of the merge tracker's Dataset: the input's lat / lon as coordinates and
@@ -1229,11 +1249,13 @@ class tracker(_MeshStages):  # noqa: N801 -- the reference's public name (marEx.
     def track_objects(self, data_bin):
         """Events with merging and splitting (track.py:2734-2807), gridded data, on the device: per-timestep objects,
         their properties, split_and_merge_objects and cluster_rename_objects_and_props.  Returns ``(events_ds, merges_ds,
-        N_events)``."""
+        N_events)``.  On a mesh (with a known time chunking): per-timestep objects made unique in time, their area-weighted
+        properties, split_and_merge_objects_parallel and the cluster renaming, chained on one device tensor."""
         import time
 
         if self.unstructured_grid:
-            raise _not_built("tracker.track_objects")
+            self._mesh_need_chunks("tracker.track_objects")
+            return self._mesh_track_objects(data_bin)
         self._check_size(data_bin.shape)  # merge tracking keeps refusing fields of 2^31 - 1 cells and more
         eng = self._engine()
         st = self._stage_times = {}
@@ -1298,7 +1320,8 @@ class tracker(_MeshStages):  # noqa: N801 -- the reference's public name (marEx.
         (track.py:2809-3335), on the device.  ``merge_events`` are the merge records of :meth:`split_and_merge_objects`; each
         merge is placed on the time axis by its ``merge_time``."""
         if self.unstructured_grid:
-            raise _not_built("tracker.cluster_rename_objects_and_props")
+            self._mesh_need_chunks("tracker.cluster_rename_objects_and_props")
+            return self._mesh_cluster_rename_stage(object_id_field_unique, overlap_objects_list, merge_events)
         eng = self._engine()
         ids, T, ny, nx = self._device_ids(object_id_field_unique, eng)
         ids = ids.clone()

@@ -1,8 +1,8 @@
 """The tracker on unstructured meshes (``marEx.tracker(unstructured_grid=True)``): the stages of ``track_objects``
-(track.py:2734-2807) up to and including split-and-merge -- per-timestep objects, IDs unique in time, area-weighted
-object properties with centroids on the sphere, area-weighted time overlaps, the overlap threshold, and the reference's
-parallel split-and-merge for meshes (``split_and_merge_objects_parallel``, track.py:3804-4814) -- on the device.  The cluster
-renaming that follows (track.py:2809-3335) and the end-to-end ``run()`` over it are not built.
+(track.py:2734-2807) -- per-timestep objects, IDs unique in time, area-weighted object properties with centroids on the
+sphere, area-weighted time overlaps, the overlap threshold, the reference's parallel split-and-merge for meshes
+(``split_and_merge_objects_parallel``, track.py:3804-4814) and the cluster renaming into events (track.py:2809-3335) -- on
+the device, and ``track_objects`` itself, which chains them on one device tensor for the end-to-end ``run()``.
 
 Arithmetic.  The reference sums cell areas and area-weighted unit vectors in float32 with ``np.add.at`` in cell order
 (track.py:2190-2208, 2436-2439); a parallel float sum cannot reproduce that bit for bit, and float atomics differ from
@@ -58,6 +58,21 @@ def mesh_weight_tables(cell_areas, lat_deg, lon_deg) -> Tuple[int, np.ndarray]:
     q[2] = np.rint(np.ldexp(a * (cl * np.sin(lon_r)), e))
     q[3] = np.rint(np.ldexp(a * np.sin(lat_r), e))
     return e, q
+
+
+def mesh_moments_finish(mom, e: int) -> Tuple[np.ndarray, np.ndarray]:
+    """The float64 finish of the contract, shared by objects and events: ``mom`` int64 ``[..., 5]`` holds cells and the
+    integer sums ``S0..S3`` of ``q[0..3]``; returns ``(area, centroid)`` with ``area = float32(S0 / 2^e)`` of shape
+    ``[...]`` and ``centroid`` float32 ``[2, ...]``, the direction of ``(S1, S2, S3)`` as latitude and longitude in degrees
+    (a zero vector gives (0, 0)), longitude folded into [-180, 180] (track.py:2226-2230, 3192-3207)."""
+    mom = np.asarray(mom)
+    s0, s1, s2, s3 = (mom[..., k].astype(np.float64) for k in range(1, 5))
+    norm = np.sqrt(s1 * s1 + s2 * s2 + s3 * s3)
+    norm = np.where(norm > 0, norm, 1.0)
+    lat = np.degrees(np.arcsin(np.clip(s3 / norm, -1.0, 1.0)))
+    lon = np.degrees(np.arctan2(s2 / norm, s1 / norm))
+    lon = np.where(lon > 180.0, lon - 360.0, np.where(lon < -180.0, lon + 360.0, lon))
+    return np.ldexp(s0, -int(e)).astype(np.float32), np.stack([lat, lon]).astype(np.float32)
 
 
 MESH_MAX_MERGES = 20    # merges per timestep and iteration (track.py:3828)
@@ -168,11 +183,10 @@ def check_temporary_id_ranges(drawn: dict) -> None:
 def _not_built(what: str) -> ConfigurationError:
     return ConfigurationError(
         f"{what} is not built for unstructured grids: the split-and-merge stage is missing",
-        details="built on a mesh: run_preprocess, compute_area, identify_objects, unique_ids_in_time, "
-                "calculate_object_properties, check_overlap_slice, find_overlapping_objects, enforce_overlap_threshold, "
-                "split_and_merge_objects_parallel; the reference's cluster_rename_objects_and_props on meshes "
-                "(track.py:2809-3335) and the end-to-end run over it are not",
-        suggestions=["Use the stage methods up to split_and_merge_objects_parallel", "Track gridded data"])
+        details="the sequential split_and_merge_objects and its consolidate_object_ids are the reference's algorithm for "
+                "grids (track.py:2554-2656, 3337-3802); on a mesh the merge stage is split_and_merge_objects_parallel, which "
+                "run, run_tracking and track_objects go through",
+        suggestions=["Call split_and_merge_objects_parallel, or run() / track_objects() over it", "Track gridded data"])
 
 
 class _MeshStages:
@@ -604,27 +618,39 @@ class _MeshStages:
         overlap_objects_list (n, 2) int32, merge_events)``.  The ID field stays on the device; per timestep with pending
         children only the overlap and property tables of two slices reach the host.  Areas and fractions follow the
         fixed-point contract of this module, the nearest centroid is decided on float64 unit vectors."""
-        import torch
-
-        from .xr_compat import DataArray, Dataset
+        from .xr_compat import DataArray
 
         if not self.unstructured_grid:
             raise ConfigurationError("split_and_merge_objects_parallel is the merge stage of unstructured grids",
                                      details="gridded data is tracked by the sequential algorithm (track.py:3337-3802)",
                                      suggestions=["Call split_and_merge_objects on gridded data"])
         ranges = self._mesh_merge_chunks()
-        timechunks = ranges[0][1] - ranges[0][0]
-        thr = self.overlap_threshold
         eng = self._engine()
         ids = self._mesh_device_ids(object_id_field_unique, eng)
         T, Cn = (int(k) for k in ids.shape)
-        if ranges[-1][1] != T:
-            raise create_data_validation_error("The ID field does not cover the time axis of data_bin",
-                                               details=f"{T} timesteps, time chunks of data_bin {tuple(self._time_chunks)}")
+        self._mesh_check_time_axis(T, ranges)
         self._check_fits(eng, {"ID field int32": 4 * T * Cn, "iteration snapshot int32": 4 * T * Cn,
                                "two-slice views int32": 8 * Cn, "unit vectors float64": 24 * Cn,
                                "owner words uint32": 4 * Cn}, "tracker.split_and_merge_objects_parallel")
-        ids = ids.clone()
+        ids, props, pairs, merges = self._mesh_split_and_merge(eng, ids.clone(), object_props, ranges)
+        field = DataArray(self._ids_to_host(eng, ids), dims=(self.timedim, self.xdim),
+                          coords={self.timedim: (self.timedim, self.time_values[:T])}, name="ID_field")
+        return field, props, pairs, self._mesh_merges_dataset(merges)
+
+    def _mesh_check_time_axis(self, T: int, ranges) -> None:
+        if ranges[-1][1] != T:
+            raise create_data_validation_error("The ID field does not cover the time axis of data_bin",
+                                               details=f"{T} timesteps, time chunks of data_bin {tuple(self._time_chunks)}")
+
+    def _mesh_split_and_merge(self, eng, ids, object_props, ranges):
+        """:meth:`split_and_merge_objects_parallel` on the device tensor ``ids`` (int32 ``[T, C]``, changed in place and
+        returned) over the chunk ``ranges`` of :meth:`_mesh_merge_chunks`: ``(ids, object_props, overlap_objects_list,
+        merges)``, ``merges`` the records :meth:`_mesh_merges_dataset` takes.  Nothing of the field reaches the host."""
+        import torch
+
+        timechunks = ranges[0][1] - ranges[0][0]
+        thr = self.overlap_threshold
+        T, Cn = (int(k) for k in ids.shape)
         q, nbr, _ = self._mesh_tables(eng)
         u = self._mesh_unit_vectors_dev(eng)
         e = self._mesh_e
@@ -729,9 +755,7 @@ class _MeshStages:
         props = self._mesh_object_properties(self._mesh_wrap(ids, "ID_field"), ["area", "centroid"])
         pairs = self._mesh_enforce_overlap_threshold(eng.mesh_overlap_pairs(ids, q, e) if T > 1 else np.zeros((0, 3), np.float32),
                                                      props)[:, :2].astype(np.int32)
-        field = DataArray(self._ids_to_host(eng, ids), dims=(self.timedim, self.xdim),
-                          coords={self.timedim: (self.timedim, self.time_values[:T])}, name="ID_field")
-        return field, props, pairs, self._mesh_merges_dataset(merges)
+        return ids, props, pairs, merges
 
     def _mesh_partition_step(self, eng, cur, m1, nbr, u, plan, cen_prev, mean_cell_area: float, stats: dict) -> None:
         """Partition the children of ``plan`` in the slice ``cur`` among their parents in ``m1``, in place."""
@@ -778,6 +802,92 @@ class _MeshStages:
                         "n_parents": DataArray(np.array([len(m[2]) for m in merges], np.int8), dims=("merge_ID",)),
                         "n_children": DataArray(np.array([len(m[1]) for m in merges], np.int8), dims=("merge_ID",))},
                        attrs={"fill_value": -1})
+
+    # ------------------------------------------------------------------ events and the end-to-end run (track.py:2734-3331)
+    def _mesh_need_chunks(self, what: str) -> None:
+        """The first statement of :meth:`run`, :meth:`run_tracking`, :meth:`track_objects` and
+        :meth:`cluster_rename_objects_and_props` on a mesh: every stage from split-and-merge on needs a known time
+        chunking, because the merges depend on it."""
+        if self._time_chunks is None:
+            raise ConfigurationError(
+                f"{what} is not built for unstructured grids: the split-and-merge stage has no time chunking to walk",
+                details="on a mesh every stage from split_and_merge_objects_parallel on walks the time chunks of data_bin, and "
+                        "the merges depend on them (track.py:4452-4459); data_bin carries none and timechunks= was not given",
+                suggestions=["Pass timechunks=<steps per chunk>", "Chunk data_bin in time"])
+
+    def _mesh_cluster_rename(self, eng, ids, overlaps, merges_ds, merge_tidx):
+        """cluster_rename_objects_and_props on a mesh, with ``ids`` on the device (relabelled in place to event IDs): one
+        kernel renames the field and adds up the fixed-point weights per (timestep, event); the finish is the one of the
+        object properties.  Returns ``(events Dataset, N)``."""
+        T, Cn = (int(k) for k in ids.shape)
+        if T != len(self.time_values):
+            raise create_data_validation_error("The ID field does not cover the time axis of data_bin",
+                                               details=f"{T} timesteps, {len(self.time_values)} time values")
+        q, e = self._mesh_tables(eng)[0], self._mesh_e
+
+        def device_pass(lut, N):
+            r = eng.mesh_event_rename(ids, lut, N, q, e)
+            area, cen = mesh_moments_finish(r["mom"], e)
+            return r["gid"], area, cen[0], cen[1]
+
+        return self._cluster_rename_events(eng, ids, overlaps, merges_ds, merge_tidx, device_pass, (self.timedim, self.xdim),
+                                           (T, Cn))
+
+    def _mesh_cluster_rename_stage(self, object_id_field_unique, overlap_objects_list, merge_events):
+        eng = self._engine()
+        ids = self._mesh_device_ids(object_id_field_unique, eng)
+        self._check_fits(eng, {"ID field int32": 4 * int(ids.numel()), "event field int32": 4 * int(ids.numel())},
+                         "tracker.cluster_rename_objects_and_props")
+        ov = np.zeros((0, 2), np.int64) if overlap_objects_list is None else np.asarray(overlap_objects_list)
+        ov = ov.reshape(-1, ov.shape[-1] if ov.ndim == 2 else 2)[:, :2]  # [id, id] or [id, id, overlap area] rows
+        ds, _ = self._mesh_cluster_rename(eng, ids.clone(), ov, merge_events, self._merge_time_index(merge_events))
+        return ds
+
+    def _mesh_track_objects(self, data_bin):
+        """track_objects on a mesh (track.py:2755-2807): per-timestep objects, IDs unique in time, object properties,
+        split-and-merge and cluster renaming chained on one device tensor; the ID field reaches the host once, as the
+        event field."""
+        import time
+
+        from .engine import plan_time_blocks
+
+        ranges = self._mesh_merge_chunks()
+        eng = self._engine()
+        st = self._stage_times = {}
+        t0 = time.perf_counter()
+        shape = tuple(int(k) for k in data_bin.shape)
+        if len(shape) != 2:
+            raise create_data_validation_error("Invalid dimensions for unstructured data",
+                                               details=f"Expected (time, {self._mesh_q.shape[1]} cells), got {shape}")
+        T, Cn = shape[::-1] if self._mesh_perm(data_bin) else shape
+        self._check_size((T, Cn))  # merge tracking keeps refusing fields of 2^31 - 1 cells and more
+        self._mesh_check_time_axis(T, ranges)
+        n = T * Cn
+        block = None if self.label_block_steps is None else self.label_block_steps * Cn
+        blk = max(b - a for a, b in plan_time_blocks(T, Cn, block)) * Cn
+        mask = {"mask uint8": n} if _is_host(data_bin) else {}
+        labelling = dict(mask, **{"ID field int32": 4 * n, "labelling scratch (one block)": 8 * blk})
+        merging = {"ID field int32": 4 * n, "per-timestep IDs, then the iteration snapshot int32": 4 * n,
+                   "two-slice views int32": 8 * Cn, "unit vectors float64": 24 * Cn, "owner words uint32": 4 * Cn}
+        self._check_fits(eng, max(labelling, merging, key=lambda d: sum(d.values())), "tracker.track_objects")
+        x = self._mesh_device_u8(data_bin, eng)  # the first device allocation: after the checks
+        q, nbr, mk = self._mesh_tables(eng)
+        r = eng.label_objects_mesh(x, mk, nbr, max_block_cells=block)
+        del x
+        ids = eng.unique_ids_in_time(r["ids"])
+        del r
+        props = self._mesh_object_properties(self._mesh_wrap(ids, "ID_field"), ["area", "centroid"])
+        eng.sync()
+        st["objects"] = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        ids, _, pairs, merges = self._mesh_split_and_merge(eng, ids, props, ranges)
+        merges_ds = self._mesh_merges_dataset(merges)
+        eng.sync()
+        st["split_and_merge"] = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        events_ds, N = self._mesh_cluster_rename(eng, ids, pairs, merges_ds, np.array([m[0] for m in merges], dtype=np.int64))
+        st["cluster_rename"] = time.perf_counter() - t0
+        return events_ds, merges_ds, N
 
 
 def _is_host(da) -> bool:
