@@ -401,6 +401,15 @@ int marex_label_apply_table_i32(marex_ctx* ctx, int32_t* ids, int64_t n, const i
 int marex_filter_by_area_u8(marex_ctx* ctx, const int32_t* labels, const int32_t* areas, int64_t n,
                             double area_threshold, int drop_label, uint8_t* out);
 
+/* Ordered stream compaction: the positive entries of v[0..n) (n <= 2^31 - 2), in index order, to out[0..cap) -- the
+ * per-object areas that marex_label2d_i32 / marex_label_mesh_i32 leave at the root cells, as a list ordered by (time,
+ * first cell).  *n_out (device) = their number, *first_index (device) = the index of the first one, -1 when there is none.
+ * Synchronises the stream once to learn the count: with more than cap positive entries the first cap are written,
+ * *n_out still holds the full count and the call returns -7.  Separate launches (tile counts, scan, scatter): no
+ * workgroup waits on another. */
+int marex_compact_positive_i32(marex_ctx* ctx, const int32_t* v, int64_t n, int32_t* out, int64_t cap, int64_t* n_out,
+                               int64_t* first_index);
+
 /* The same two stages on an unstructured mesh (track.py:1543-1606 and 1932-2004): nbr int32 [3, C], 0-based, -1 = no
  * neighbour (the reference's `neighbours - 1`).  fill_holes: dilation by R = R sweeps of "OR over the cell and its listed
  * neighbours"; closing with the land set True before the erosion, then opening, NO final land mask (as in the reference).

@@ -67,6 +67,7 @@ PROTOTYPES = {
     "marex_label_table_resolve_i32": (_i32, [_p, _p, _i64, _p, _p, _p]),
     "marex_label_apply_table_i32": (_i32, [_p, _p, _i64, _p, _i64, _i32]),
     "marex_filter_by_area_u8": (_i32, [_p, _p, _p, _i64, _f64, _i32, _p]),
+    "marex_compact_positive_i32": (_i32, [_p, _p, _i64, _p, _i64, _p, _p]),
     "marex_fill_holes_mesh_u8": (_i32, [_p, _p, _p, _p, _i64, _i64, _i32, _p]),
     "marex_label_mesh_i32": (_i32, [_p, _p, _p, _p, _i64, _i64, _p, _p]),
     "marex_validation_summary": (_i32, [_p, _p, _p, _i64, _i64, _p]),

@@ -864,3 +864,86 @@ extern "C" int marex_label_mesh_i32(marex_ctx* ctx, const uint8_t* data, const u
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }
+
+// ------------------------------------------------------------------------------------------------
+// Ordered stream compaction of the positive entries of an int32 array: the per-object areas that marex_label2d_i32 /
+// marex_label_mesh_i32 leave at the root cells, as a list in index order (time, then first cell) -- what the blocked
+// pre-processing appends to its per-object list instead of torch's `a[a > 0]` (4 bytes per cell of temporaries).
+// Three launches and no workgroup waits on another: counts per tile of CCL_TILE consecutive entries (ballot + popcount
+// per wave, the four wave counts through LDS), the exclusive scan of the tile counts by k_ccl_scan_tiles, and a scatter
+// that ranks the entries of its tile the same way again.  v is read twice; the pass is bandwidth-bound.
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256)
+k_compact_count(const int* __restrict__ v, long n, int* __restrict__ tile_cnt) {
+    __shared__ int wcnt[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long tile0 = (long)blockIdx.x * CCL_TILE;
+    int mine = 0;
+    for (int k = 0; k < CCL_TILE / 256; ++k) {
+        const long i = tile0 + k * 256 + threadIdx.x;
+        mine += (i < n && v[i] > 0) ? 1 : 0;
+    }
+    for (int d = 32; d > 0; d >>= 1) mine += __shfl_down(mine, d, 64);
+    if (lane == 0) wcnt[wave] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) tile_cnt[blockIdx.x] = wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+}
+
+// out[rank] = v[i] for the positive entries with rank < cap; the entry of rank 0 reports its index, and the first
+// thread of the grid the total (and -1 as the first index when there is none): every result has exactly one writer.
+__global__ void __launch_bounds__(256)
+k_compact_scatter(const int* __restrict__ v, long n, const int* __restrict__ tile_off, const int* __restrict__ total,
+                  int* __restrict__ out, long cap, long long* __restrict__ n_out, long long* __restrict__ first_index) {
+    __shared__ int wcnt[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long tile0 = (long)blockIdx.x * CCL_TILE;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const int tot = *total;
+        *n_out = tot;
+        if (tot == 0) *first_index = -1;
+    }
+    int run = tile_off[blockIdx.x];
+    for (int k = 0; k < CCL_TILE / 256; ++k) {
+        const long i = tile0 + k * 256 + threadIdx.x;
+        const int val = i < n ? v[i] : 0;
+        const bool keep = val > 0;
+        const unsigned long long b = __ballot(keep);
+        if (lane == 0) wcnt[wave] = __popcll(b);
+        __syncthreads();
+        if (keep) {
+            long r = run + __popcll(b & ((1ull << lane) - 1ull));
+            for (int w = 0; w < wave; ++w) r += wcnt[w];
+            if (r < cap) out[r] = val;
+            if (r == 0) *first_index = i;
+        }
+        run += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+        __syncthreads();
+    }
+}
+
+extern "C" int marex_compact_positive_i32(marex_ctx* ctx, const int32_t* v, int64_t n, int32_t* out, int64_t cap,
+                                          int64_t* n_out, int64_t* first_index) {
+    if (!ctx) return -1;
+    if (!v || !out || !n_out || !first_index || n <= 0 || cap < 0) return fail(ctx, -1, "marex_compact_positive_i32: null pointer, empty array or negative capacity");
+    if (n > 2147483646L) return fail(ctx, -4, "marex_compact_positive_i32: more than 2^31 - 2 entries");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    LaunchTimer lt(ctx, MAREX_K_MORPH);
+    const long ntiles = (n + CCL_TILE - 1) / CCL_TILE;
+    // scratch: tile counts and tile offsets [ntiles] each, the total
+    if (int rc = ensure_scratch(ctx, (size_t)(2 * ntiles + 1) * sizeof(int))) return rc;
+    int* tile_cnt = reinterpret_cast<int*>(ctx->morph_scratch);
+    int* tile_off = tile_cnt + ntiles;
+    int* total = tile_off + ntiles;
+    hipLaunchKernelGGL(k_compact_count, dim3((unsigned)ntiles), dim3(256), 0, ctx->stream, v, (long)n, tile_cnt);
+    hipLaunchKernelGGL(k_ccl_scan_tiles, dim3(1), dim3(1024), 0, ctx->stream, tile_cnt, ntiles, tile_off, total);
+    hipLaunchKernelGGL(k_compact_scatter, dim3((unsigned)ntiles), dim3(256), 0, ctx->stream, v, (long)n, tile_off, total, out,
+                       (long)cap, reinterpret_cast<long long*>(n_out), reinterpret_cast<long long*>(first_index));
+    HIP_TRY(ctx, hipGetLastError());
+    int count = 0;  // the caller sizes its list by the count: the one host read of this call
+    HIP_TRY(ctx, hipMemcpyAsync(&count, total, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if ((int64_t)count > cap)
+        return fail(ctx, -7, "marex_compact_positive_i32: %d positive entries, capacity %lld (the first %lld written)", count,
+                    (long long)cap, (long long)cap);
+    return 0;
+}

@@ -1242,6 +1242,170 @@ class HotPath:
         return {"filtered": out, "area_threshold": thr, "object_areas": obj_areas, "n_before": n_before, "n_after": n_after,
                 "labels": blocks[0][1] if len(blocks) == 1 else [b[1] for b in blocks]}
 
+    # ------------------------------------------------------------------ pre-processing in time blocks
+    def compact_positive(self, areas: torch.Tensor, out: Optional[torch.Tensor] = None, used: int = 0):
+        """The positive entries of an int32 tensor in index order (``marex_compact_positive_i32``): the per-object areas
+        that the per-timestep labellings leave at the root cells.  Returns ``(list, count, first_index)``: ``list`` int32
+        with the entries at ``[used, used + count)`` -- ``out`` when its room sufficed, else a larger tensor that carries
+        ``out[:used]`` over --, ``count`` a host int (the call's one host read) and ``first_index`` an int64 ``[1]`` device
+        tensor, the index of the first positive entry or -1."""
+        flat = areas.reshape(-1)
+        n = int(flat.numel())
+        if flat.dtype != torch.int32 or n <= 0 or n > LABEL_BLOCK_CELLS:
+            raise ProcessingError("compact_positive: needs a non-empty int32 tensor of at most 2^31 - 2 entries",
+                                  details=f"got {flat.dtype} with {n} entries")
+        used = int(used)
+        if out is None:
+            out = torch.empty((max(1024, n // 64),), dtype=torch.int32, device=self.device)
+        res = torch.empty((2,), dtype=torch.int64, device=self.device)  # n_out, first_index
+        for _ in range(2):
+            self._bind_stream()
+            tail = out[used:]
+            rc = self.lib.marex_compact_positive_i32(self.ctx.handle, flat.data_ptr(), n, tail.data_ptr() if tail.numel() else
+                                                     res.data_ptr(), int(tail.numel()), res.data_ptr(), res.data_ptr() + 8)
+            if rc != -7:
+                break
+            count = int(res[0].item())  # the list was too short: grow it (at least doubling) and compact again
+            grown = torch.empty((max(2 * int(out.numel()), used + count),), dtype=torch.int32, device=self.device)
+            grown[:used] = out[:used]
+            out = grown
+        self.ctx.check(rc, "marex_compact_positive_i32")
+        return out, int(res[0].item()), res[1:2]
+
+    def preprocess_blocked(self, data: Optional[torch.Tensor], mask: torch.Tensor, R_fill: int, T_fill: int, block_steps: int,
+                           area_filter_quartile: float = 0.5, area_filter_absolute: Optional[float] = None, *,
+                           ny: Optional[int] = None, nx: Optional[int] = None, regional_mode: bool = False,
+                           nbr: Optional[torch.Tensor] = None, q: Optional[torch.Tensor] = None, e: int = 0,
+                           fetch=None, shape: Optional[Tuple[int, int]] = None, wsp: Optional[dict] = None) -> Dict[str, object]:
+        """``fill_holes`` -> ``fill_time_gaps`` -> ``filter_small_objects`` over a ``[T, C]`` uint8 field in blocks of
+        ``block_steps`` timesteps: bit for bit the three whole-field calls, at one full-size uint8
+        output plus a window of ``block_steps + 2 T_fill`` steps.  Grid form: ``ny``, ``nx`` (and ``regional_mode``); mesh
+        form: ``nbr`` int32 ``[3, C]``, the weight table ``q`` and its exponent ``e`` (sizes in cells, the percentile over
+        the clusters larger than 50 (5) cells, keep strictly above the threshold, no first-object rule).
+
+        ``data`` is the field on the device; or ``data=None`` with ``shape=(T, C)`` and ``fetch(t0, t1, buf)``, which fills
+        the uint8 ``[t1 - t0, C]`` device tensor ``buf`` with the rows ``[t0, t1)`` of a field that lives on the host: only
+        one window of it is on the device at a time.
+
+        Returns the dict of :meth:`filter_small_objects` without ``labels``, plus ``raw_area`` and ``processed_area``: the
+        cells set in the input and in ``filtered`` (grid), the float64 area-weighted sums over the timesteps (mesh)."""
+        mesh = nbr is not None
+        T, Cn = (int(k) for k in (data.shape if data is not None else shape))
+        if T <= 0 or Cn <= 0:
+            raise ProcessingError("preprocess_blocked: empty field", details=f"{T} steps of {Cn} cells")
+        if Cn > LABEL_BLOCK_CELLS:
+            raise TrackingError(f"one timestep of {Cn} cells exceeds the labelling block of {LABEL_BLOCK_CELLS} cells")
+        if not mesh:
+            assert Cn == int(ny) * int(nx)
+        R, Tf = int(R_fill), int(T_fill)
+        B = max(1, min(int(block_steps), T, LABEL_BLOCK_CELLS // Cn))
+        W = min(T, B + 2 * Tf)
+        wsp = {} if wsp is None else wsp
+        dev, u8 = self.device, torch.uint8
+        out = self._buf(None, "filtered", (T, Cn), u8, dev)
+        # the window buffers at their largest, once: no block allocates
+        if data is None:
+            self._buf(wsp, "window_in", (W, Cn), u8, dev)
+        if Tf > 0:
+            self._buf(wsp, "window_filled", (W, Cn), u8, dev)
+            self._buf(wsp, "window_closed", (W, Cn), u8, dev)
+        self._buf(wsp, "block_labels", (B, Cn), torch.int32, dev)
+        self._buf(wsp, "block_areas", (B, Cn), torch.int32, dev)
+        wrap = 0 if regional_mode else 1
+        absolute = area_filter_absolute is not None
+
+        def holes(src, rows, radius, dst):
+            if mesh:
+                self.call("marex_fill_holes_mesh_u8", src, mask, nbr, rows, Cn, radius, dst)
+            else:
+                self.call("marex_fill_holes_u8", src, mask, rows, int(ny), int(nx), radius, int(bool(regional_mode)), dst)
+
+        def label(t0, t1):
+            labels = self._buf(wsp, "block_labels", (t1 - t0, Cn), torch.int32, dev)
+            areas = self._buf(wsp, "block_areas", (t1 - t0, Cn), torch.int32, dev)
+            if mesh:
+                self.call("marex_label_mesh_i32", out[t0:t1], mask, nbr, t1 - t0, Cn, labels, areas)
+            else:
+                self.call("marex_label2d_i32", out[t0:t1], t1 - t0, int(ny), int(nx), wrap, labels, areas)
+            return labels, areas
+
+        # areas per timestep, raw and processed: integer sums of the mesh's weights, of unit weights on a grid (the cell
+        # count; torch's own sum of a uint8 block would widen it to 8 bytes per cell first)
+        if mesh:
+            self._mesh_weights_check(q, Cn, "preprocess_blocked")
+            weights = q[0]
+        else:
+            weights = torch.ones((Cn,), dtype=torch.int64, device=dev)
+        area_t = torch.zeros((2, T), dtype=torch.int64, device=dev)
+
+        def count_area(which, rows, t0, t1):
+            self.call("marex_mesh_area_i64", rows, t1 - t0, Cn, weights, area_t[which, t0:t1])
+
+        def keep(labels, areas, thr, first, t0, t1):  # in place: the kernel reads labels and areas, not the mask
+            level = float(np.floor(thr) + 1.0) if mesh else thr  # strict ">" on integer sizes
+            self.call("marex_filter_by_area_u8", labels, areas, labels.numel(), level, first, out[t0:t1])
+            count_area(1, out[t0:t1], t0, t1)
+
+        blocks = [(t0, min(T, t0 + B)) for t0 in range(0, T, B)]
+        lst = torch.empty((1024,), dtype=torch.int32, device=dev)
+        n_list = 0
+        first = None  # (t0 of the first block with an object, its root's index in the block: int64 [1] on the device)
+        thr = float(area_filter_absolute) if absolute else None
+        # ---- pass 1: morphology into `out`, per-timestep labelling, the per-object list
+        for t0, t1 in blocks:
+            w0, w1 = max(0, t0 - Tf), min(T, t1 + Tf)
+            if data is not None:
+                win = data[w0:w1]
+            else:
+                win = self._buf(wsp, "window_in", (w1 - w0, Cn), u8, dev)
+                fetch(w0, w1, win)
+            count_area(0, win[t0 - w0:t1 - w0], t0, t1)
+            if Tf > 0:
+                a = self._buf(wsp, "window_filled", (w1 - w0, Cn), u8, dev)
+                holes(win, w1 - w0, R, a)
+                c = self._buf(wsp, "window_closed", (w1 - w0, Cn), u8, dev)
+                self.call("marex_time_closing_u8", a, w1 - w0, Cn, Tf, c)
+                holes(c[t0 - w0:t1 - w0], t1 - t0, R // 2, out[t0:t1])
+            else:
+                holes(win, t1 - t0, R, out[t0:t1])
+            labels, areas = label(t0, t1)
+            lst, cnt, fidx = self.compact_positive(areas, lst, n_list)
+            drop = 0
+            if cnt and first is None and not mesh:
+                first = (t0, fidx.clone())
+                if absolute:
+                    drop = int(fidx.item()) + 1  # the first object is known when it is met
+            n_list += cnt
+            if absolute:  # one pass is enough
+                keep(labels, areas, thr, drop, t0, t1)
+        obj = lst[:n_list]
+        if mesh:
+            obj = obj[obj > (5 if absolute else 50)]
+        n_before = int(obj.numel())
+        if n_before == 0:
+            raise ProcessingError("No objects found for area-based filtering")
+        if not absolute:
+            thr = _linear_percentile(obj, area_filter_quartile)
+        if mesh:
+            n_after = int((obj.to(torch.float64) > thr).sum().item())
+        else:
+            n_after = int((obj.to(torch.float64) >= thr).sum().item())
+            if float(obj[0].item()) >= thr:  # the reference's `object_ids_keep[0] = -1`
+                n_after -= 1
+        # ---- pass 2 (percentile filter): label the owned rows again and filter them in place
+        if not absolute:
+            first_t0, first_root = (first[0], int(first[1].item())) if first is not None else (-1, -1)
+            for t0, t1 in blocks:
+                labels, areas = label(t0, t1)
+                keep(labels, areas, thr, first_root + 1 if t0 == first_t0 else 0, t0, t1)
+        sums = area_t.cpu().numpy()
+        if mesh:  # as mesh_area forms them: S / 2^e per timestep, then the float64 sum over the timesteps
+            raw, processed = (float(np.ldexp(v.astype(np.float64), -int(e)).sum()) for v in sums)
+        else:
+            raw, processed = (float(int(v.sum())) for v in sums)
+        return {"filtered": out, "area_threshold": thr, "object_areas": obj, "n_before": n_before, "n_after": n_after,
+                "raw_area": raw, "processed_area": processed}
+
     def fill_holes_mesh(self, data_bin: torch.Tensor, mask: torch.Tensor, nbr: torch.Tensor, R_fill: int,
                         wsp: Optional[dict] = None) -> torch.Tensor:
         """``fill_holes`` on an unstructured mesh (track.py:1543-1606): ``nbr`` int32 ``[3, C]``, 0-based, -1 = none."""

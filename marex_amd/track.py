@@ -71,6 +71,76 @@ def tracking_memory_need(T: int, ny: int, nx: int, R_fill: int, T_fill: int, res
     return need
 
 
+#: the name of the input's entry in :func:`preprocess_memory_need` when it is allocated already (not taken from free memory)
+_RESIDENT_INPUT = "input mask uint8 (resident, allocated already)"
+
+
+def preprocess_memory_need(T: int, ny: Optional[int], C: int, R_fill: int, T_fill: int, block_steps: int,
+                           resident: bool = False, host_input: bool = False) -> Dict[str, int]:
+    """Bytes of the device buffers of the time-blocked pre-processing (``HotPath.preprocess_blocked``)
+    of a ``[T, C]`` field in blocks of ``block_steps`` steps, by name; ``ny`` is the grid's row count, None on a mesh.
+    The input (one byte per cell; no entry with ``host_input``: only a window of a host array is ever uploaded), the
+    full-size uint8 output, three uint8 windows of ``B + 2 T_fill`` steps (the uploaded input, the hole-filled and the
+    time-closed rows), the int32 labels and areas of ``B`` steps, the int64 raw and processed areas per timestep (with
+    the unit weights that count cells on a grid), and the library's scratch at its largest: the bit-packed
+    padded images of ``fill_holes`` over the window (two byte copies of it on a mesh) or the int32 copy of the labelled
+    block with the compaction's tile counts.  The per-object list (4 bytes per object) is not known before and left out.
+    :func:`preprocess_alloc_bytes` is what of this has yet to be allocated."""
+    T, C, R, Tf = int(T), int(C), int(R_fill), int(T_fill)
+    B = max(1, min(int(block_steps), T))
+    W = min(T, B + 2 * Tf)
+    n = T * C
+    if ny is None:
+        morph = 2 * W * C
+    else:
+        nx = C // int(ny)
+        morph = 16 * W * (int(ny) + 4 * R) * ((nx + 4 * R + 63) // 64) + 256 if R > 0 else 0
+    tiles = (B * C + 4095) // 4096
+    need = {}
+    if not host_input:
+        need[_RESIDENT_INPUT if resident else "input mask uint8"] = n
+    need["pre-processed mask uint8"] = n
+    need["window buffers 3 x uint8"] = 3 * W * C
+    need["block labels int32"] = 4 * B * C
+    need["block areas int32"] = 4 * B * C
+    need["areas per timestep and unit weights int64"] = 16 * T + (8 * C if ny is not None else 0)
+    need["library scratch"] = max(morph, 4 * B * C, 4 * (2 * tiles + 1))
+    return need
+
+
+def preprocess_alloc_bytes(need: Dict[str, int]) -> int:
+    """The bytes of a :func:`preprocess_memory_need` that come out of the free device memory: all but a resident input."""
+    return sum(v for k, v in need.items() if k != _RESIDENT_INPUT)
+
+
+def plan_preprocess_blocks(T: int, C: int, T_fill: int, free_bytes: int, ny: Optional[int] = None, R_fill: int = 0,
+                           resident: bool = False, host_input: bool = False) -> int:
+    """The largest number of owned steps ``B`` (at most ``T``, and at most what one labelling call takes: 2^31 - 2 cells)
+    whose :func:`preprocess_memory_need`, less a resident input, fits ``free_bytes``.  :class:`TrackingError` with both
+    numbers when even one step does not fit.  Needs no GPU."""
+    T, C = int(T), int(C)
+    if T <= 0 or C <= 0:
+        raise TrackingError(f"cannot plan pre-processing blocks for an empty field ({T} steps of {C} cells)")
+    if C > _BLOCK_CELLS:
+        raise TrackingError(f"one timestep of {C} cells exceeds the labelling block of {_BLOCK_CELLS} cells")
+    need = lambda b: preprocess_memory_need(T, ny, C, R_fill, T_fill, b, resident, host_input)  # noqa: E731
+    fits = lambda b: preprocess_alloc_bytes(need(b)) <= int(free_bytes)  # noqa: E731
+    if not fits(1):
+        n1 = need(1)
+        raise TrackingError(f"pre-processing in time blocks: one step per block needs {preprocess_alloc_bytes(n1) / 1e9:.3f} GB "
+                            f"of device memory, {int(free_bytes) / 1e9:.3f} GB are free",
+                            details="; ".join(f"{k} {v / 1e9:.3f} GB" for k, v in n1.items()),
+                            suggestions=["Keep the input on the host", "Free device memory held by other arrays"])
+    lo, hi = 1, max(1, min(T, _BLOCK_CELLS // C))  # the need grows with B: bisect
+    while lo < hi:
+        mid = (lo + hi + 1) // 2
+        if fits(mid):
+            lo = mid
+        else:
+            hi = mid - 1
+    return lo
+
+
 def _tensor_of(da):
     """The torch tensor behind a device-resident DataArray, else None (never copies)."""
     t = getattr(da, "device_tensor", None)
@@ -255,6 +325,12 @@ class tracker(_MeshStages):  # noqa: N801 -- the reference's public name (marEx.
     (:func:`tracking_memory_need`, about 12 bytes per cell) exceed the free device memory -- before anything is allocated,
     with both numbers -- and by merge tracking (``allow_merging=True``) for fields of 2^31 - 1 cells and more.
 
+    ``preprocess_block_steps`` (None: the whole-field path above) runs :meth:`run_preprocess` in time blocks of that many
+    steps, or with ``"auto"`` of as many as the free device memory takes: the same mask and statistics, at the input, the
+    output and a window of ``B + 2 T_fill`` steps (:func:`preprocess_memory_need`, about 2 bytes per cell); a host
+    ``data_bin`` is then uploaded one window at a time.  :meth:`run` checks the larger of that and
+    :func:`labelling_memory_need` instead.  On grids and on meshes.
+
     ``data_bin`` may be device resident -- a DataArray whose data is a torch tensor (bool or uint8) on the GPU, e.g. from
     ``zarr_io.open_dataarray_device`` -- and is then consumed without a host round trip.  ``device`` picks the GPU.
     """
@@ -287,8 +363,14 @@ class tracker(_MeshStages):  # noqa: N801 -- the reference's public name (marEx.
         device: int = 0,
         timechunks: Optional[int] = None,
         label_block_steps: Optional[int] = None,
+        preprocess_block_steps: Union[int, str, None] = None,
     ) -> None:
         supported = "gridded data without checkpointing"
+        pbs = preprocess_block_steps
+        if pbs is not None and pbs != "auto" and (isinstance(pbs, (bool, str)) or not isinstance(pbs, (int, np.integer)) or pbs <= 0):
+            raise ConfigurationError("preprocess_block_steps must be a positive number of timesteps, 'auto' or None",
+                                     details=f"preprocess_block_steps={pbs!r}")
+        self.preprocess_block_steps = pbs if pbs is None or isinstance(pbs, str) else int(pbs)
         if label_block_steps is not None and (isinstance(label_block_steps, bool) or not isinstance(label_block_steps, (int, np.integer))
                                               or label_block_steps <= 0):
             raise ConfigurationError("label_block_steps must be a positive number of timesteps",
@@ -469,7 +551,15 @@ class tracker(_MeshStages):  # noqa: N801 -- the reference's public name (marEx.
         return tuple(dims.index(k) for k in self._out_dims()) if set(dims) == set(self._out_dims()) else (0, 1, 2)
 
     @staticmethod
-    def _check_fits(eng, need: Dict[str, int], what: str) -> None:
+    def _free_bytes(eng) -> int:
+        """What the driver reports free plus what torch's allocator holds cached."""
+        import torch
+
+        free, _ = torch.cuda.mem_get_info(eng.device)
+        return int(free + torch.cuda.memory_reserved(eng.device) - torch.cuda.memory_allocated(eng.device))
+
+    @staticmethod
+    def _check_fits(eng, need: Dict[str, int], what: str, suggestions: Optional[List[str]] = None) -> None:
         """:class:`TrackingError` with both numbers when the ``[T, C]`` buffers of ``need`` (name -> bytes) exceed the free
         device memory -- what the driver reports free plus what torch's allocator holds cached -- instead of a torch
         out-of-memory error half way through."""
@@ -481,13 +571,36 @@ class tracker(_MeshStages):  # noqa: N801 -- the reference's public name (marEx.
         if total > free:
             raise TrackingError(f"{what}: needs {total / 1e9:.3f} GB of device memory, {free / 1e9:.3f} GB are free",
                                 details="; ".join(f"{k} {v / 1e9:.3f} GB" for k, v in need.items()),
-                                suggestions=["Track a shorter record", "Free device memory held by other arrays"])
+                                suggestions=["Track a shorter record", "Free device memory held by other arrays"]
+                                + list(suggestions or []))
+
+    def _preprocess_plan(self, eng, T: int, ny: Optional[int], C: int, resident: bool) -> Tuple[int, Dict[str, int]]:
+        """``(B, need)`` of the blocked pre-processing: ``preprocess_block_steps`` as given, or with ``"auto"`` the largest
+        block that fits fifteen sixteenths of the free device memory (the rest is left to the per-object list, the small
+        tables and the allocator's rounding)."""
+        if self.preprocess_block_steps == "auto":
+            free = self._free_bytes(eng)
+            B = plan_preprocess_blocks(T, C, self.T_fill, free - free // 16, ny=ny, R_fill=self.R_fill, resident=resident,
+                                       host_input=not resident)
+        else:
+            B = min(int(self.preprocess_block_steps), T, max(1, _BLOCK_CELLS // C))
+        return B, preprocess_memory_need(T, ny, C, self.R_fill, self.T_fill, B, resident=resident, host_input=not resident)
 
     def _check_memory(self, shape) -> None:
         """The basic tracker's buffers at their peak against the free device memory."""
         T, ny, nx = (int(shape[k]) for k in self._perm)
-        need = tracking_memory_need(T, ny, nx, self.R_fill, self.T_fill, resident=_tensor_of(self.data_bin) is not None)
-        self._check_fits(self._engine(), need, "tracker.run")
+        resident = _tensor_of(self.data_bin) is not None
+        if self.preprocess_block_steps is not None:
+            # blocked pre-processing: its own need, or the labelling that follows it (the pre-processed mask + the ID field)
+            eng = self._engine()
+            _, pre = self._preprocess_plan(eng, T, ny, ny * nx, resident)
+            pre = {k: v for k, v in pre.items() if k != _RESIDENT_INPUT}
+            block = None if self.label_block_steps is None else self.label_block_steps * ny * nx
+            lab = labelling_memory_need(T, ny * nx, block, resident=False)
+            self._check_fits(eng, pre if sum(pre.values()) >= sum(lab.values()) else lab, "tracker.run")
+            return
+        need = tracking_memory_need(T, ny, nx, self.R_fill, self.T_fill, resident=resident)
+        self._check_fits(self._engine(), need, "tracker.run", suggestions=["Pass preprocess_block_steps='auto'"])
 
     @staticmethod
     def _ids_to_host(eng, ids) -> np.ndarray:
@@ -571,9 +684,24 @@ class tracker(_MeshStages):  # noqa: N801 -- the reference's public name (marEx.
         if self.unstructured_grid:
             return self._mesh_run_preprocess()
         eng = self._engine()
+        absolute = float(self.area_filter_absolute) if self._use_absolute_filtering else None
+        if self.preprocess_block_steps is not None:
+            from .track_pre import _preprocess_blocked_device
+
+            T, ny, nx = (int(self.data_bin.shape[k]) for k in self._perm_of(self.data_bin))
+            mk = torch.from_numpy(self._mask_host.reshape(-1).astype(np.uint8)).to(eng.device)
+            if _tensor_of(self.data_bin) is not None:
+                x, host = self._device_u8(self.data_bin, eng)[0], None
+            else:  # stays on the host: the blocks upload their windows
+                x, host = None, np.asarray(self.data_bin.values)
+                if self._perm_of(self.data_bin) != (0, 1, 2):
+                    host = np.transpose(host, self._perm_of(self.data_bin))
+            B, _ = self._preprocess_plan(eng, T, ny, ny * nx, resident=x is not None)
+            filtered, stats = _preprocess_blocked_device(eng, x, host, mk, ny, nx, self.R_fill, self.T_fill,
+                                                         self.area_filter_quartile, absolute, self.regional_mode, B)
+            return self._wrap_device(filtered, T, ny, nx, "data_bin_preproc"), stats
         x, T, ny, nx = self._device_u8(self.data_bin, eng)
         mk = torch.from_numpy(self._mask_host.reshape(-1).astype(np.uint8)).to(eng.device)
-        absolute = float(self.area_filter_absolute) if self._use_absolute_filtering else None
         filtered, stats = _preprocess_device(eng, x, mk, ny, nx, self.R_fill, self.T_fill, self.area_filter_quartile, absolute,
                                              self.regional_mode)
         return self._wrap_device(filtered, T, ny, nx, "data_bin_preproc"), stats

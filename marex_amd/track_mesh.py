@@ -427,6 +427,8 @@ class _MeshStages:
         import torch
 
         eng = self._engine()
+        if getattr(self, "preprocess_block_steps", None) is not None:
+            return self._mesh_run_preprocess_blocked(eng)
         x = self._mesh_device_u8(self.data_bin, eng)
         n = int(x.numel())
         need = {"hole-filled mask uint8": n, "labels int32": 4 * n, "sizes int32": 4 * n, "filtered mask uint8": n,
@@ -451,6 +453,30 @@ class _MeshStages:
         stats = (total, r["n_before"], r["n_after"], r["area_threshold"], accepted / total,
                  raw_area / processed if processed else float("nan"))
         return self._mesh_wrap(r["filtered"], "data_bin_preproc"), stats
+
+    def _mesh_run_preprocess_blocked(self, eng):
+        """:meth:`_mesh_run_preprocess` in time blocks (``preprocess_block_steps``): the same mask and
+        statistics; a host ``data_bin`` is uploaded one window at a time."""
+        from .track import _RESIDENT_INPUT, _tensor_of
+        from .track_pre import _blocked_stats, _upload_rows
+
+        T, Cn = (int(self.data_bin.shape[k]) for k in self._perm)
+        resident = _tensor_of(self.data_bin) is not None
+        B, need = self._preprocess_plan(eng, T, None, Cn, resident)
+        self._check_fits(eng, {k: v for k, v in need.items() if k != _RESIDENT_INPUT}, "tracker.run_preprocess")
+        q, nbr, mk = self._mesh_tables(eng)
+        absolute = float(self.area_filter_absolute) if self._use_absolute_filtering else None
+        kw = dict(nbr=nbr, q=q, e=self._mesh_e)
+        if resident:
+            r = eng.preprocess_blocked(self._mesh_device_u8(self.data_bin, eng), mk, self.R_fill, int(self.T_fill), B,
+                                       self.area_filter_quartile, absolute, **kw)
+        else:
+            host = np.asarray(self.data_bin.values)
+            host = host.T if self._mesh_perm(self.data_bin) else host
+            r = eng.preprocess_blocked(None, mk, self.R_fill, int(self.T_fill), B, self.area_filter_quartile, absolute,
+                                       shape=(T, Cn), fetch=lambda t0, t1, buf: _upload_rows(host, t0, t1, buf), **kw)
+        eng.sync()
+        return self._mesh_wrap(r["filtered"], "data_bin_preproc"), _blocked_stats(r)
 
     def _mesh_compute_area(self, data_bin):
         from .xr_compat import DataArray

@@ -158,18 +158,66 @@ def _preprocess_device(eng, x, mk, ny: int, nx: int, R_fill: int, T_fill: int, a
     return r["filtered"], stats
 
 
+def _upload_rows(host: np.ndarray, t0: int, t1: int, buf) -> None:
+    """Rows ``[t0, t1)`` of a host field (bool or 0 / 1 bytes, time first) into the uint8 ``[t1 - t0, C]`` device tensor
+    ``buf``: the only way a host input of the blocked pre-processing reaches the device."""
+    import torch
+
+    rows = np.ascontiguousarray(host[t0:t1]).astype(np.uint8, copy=False).reshape(t1 - t0, -1)
+    buf.copy_(torch.from_numpy(rows))
+
+
+def _blocked_stats(r: dict):
+    """``object_stats`` from the result of ``HotPath.preprocess_blocked``, as :func:`_preprocess_device` forms them."""
+    import torch
+
+    areas = r["object_areas"].to(torch.float64)
+    total = float(areas.sum().item())
+    accepted = float(areas[areas > r["area_threshold"]].sum().item())  # strictly above, as track.py:1337
+    processed = r["processed_area"]
+    return (total, r["n_before"], r["n_after"], r["area_threshold"], accepted / total,
+            r["raw_area"] / processed if processed else float("nan"))
+
+
+def _preprocess_blocked_device(eng, x, host, mk, ny: int, nx: int, R_fill: int, T_fill: int, area_filter_quartile: float,
+                               area_filter_absolute, regional_mode: bool, block_steps: int):
+    """:func:`_preprocess_device` in time blocks of ``block_steps`` steps (``HotPath.preprocess_blocked``): the same
+    filtered tensor and ``object_stats``.  The field is ``x`` (uint8 ``[T, ny * nx]`` on the device) or, with ``x=None``,
+    the host array ``host`` (time first), of which one window at a time is uploaded."""
+    if x is None:
+        T = int(host.shape[0])
+        r = eng.preprocess_blocked(None, mk, int(R_fill), int(T_fill), int(block_steps), area_filter_quartile,
+                                   area_filter_absolute, ny=ny, nx=nx, regional_mode=regional_mode, shape=(T, ny * nx),
+                                   fetch=lambda t0, t1, buf: _upload_rows(host, t0, t1, buf))
+    else:
+        r = eng.preprocess_blocked(x, mk, int(R_fill), int(T_fill), int(block_steps), area_filter_quartile,
+                                   area_filter_absolute, ny=ny, nx=nx, regional_mode=regional_mode)
+    eng.sync()
+    return r["filtered"], _blocked_stats(r)
+
+
 def run_preprocess(extreme_events, mask, R_fill: int, T_fill: int = 2, area_filter_quartile: float = 0.5,
-                   area_filter_absolute=None, regional_mode: bool = False, device: int = 0):
+                   area_filter_absolute=None, regional_mode: bool = False, device: int = 0, block_steps=None):
     """The whole pre-processing stage of ``marEx.tracker.run_preprocess`` (track.py:1283-1360) for gridded data, on the
     device without intermediate host copies: ``fill_holes`` -> ``fill_time_gaps`` -> ``filter_small_objects``.
 
     Returns ``(data_bin_filtered, object_stats)`` with ``object_stats = (total_area_IDed, N_objects_prefiltered,
     N_objects_filtered, area_threshold, accepted_area_fraction, preprocessed_area_fraction)`` as in the reference
-    (areas in cells; ``accepted_area`` sums the objects STRICTLY above the threshold, as track.py:1337 does)."""
+    (areas in cells; ``accepted_area`` sums the objects STRICTLY above the threshold, as track.py:1337 does).
+
+    ``block_steps`` (a positive number of timesteps) runs the stage in time blocks of that many steps: the same results,
+    with only one window of the input on the device at a time."""
     from .detect import get_engine
 
     d, m = _check(extreme_events, mask, R_fill, T_fill)
     eng = get_engine(device)
+    if block_steps is not None:
+        if isinstance(block_steps, bool) or not isinstance(block_steps, (int, np.integer)) or block_steps <= 0:
+            raise ConfigurationError("block_steps must be a positive number of timesteps", details=f"block_steps={block_steps!r}")
+        _, ny, nx = d.shape
+        filtered, stats = _preprocess_blocked_device(eng, None, d, _upload(eng, _as_u8(m).reshape(-1)), ny, nx, R_fill, T_fill,
+                                                     area_filter_quartile, area_filter_absolute, regional_mode, int(block_steps))
+        return _wrap(extreme_events, filtered), stats
     x, mk, ny, nx = _upload_grid(eng, d, m)
     filtered, stats = _preprocess_device(eng, x, mk, ny, nx, R_fill, T_fill, area_filter_quartile, area_filter_absolute,
                                          regional_mode)
