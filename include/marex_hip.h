@@ -557,7 +557,17 @@ int marex_mesh_event_rename_i64(marex_ctx* ctx, int32_t* ids, int64_t T, int64_t
  *   slot s = t * n_ev + e - 1 of the event field ev (1 .. n_ev): acc[s][0..4] = cells, sum y, sum x, sum of
  *   (x > nx / 2 ? x - nx : x), flags (1: a cell with x < 100, 2: a cell with x >= nx - 100); gid[s] = the largest ID of
  *   orig under the slot's cells (0 when empty); with w (float32 [ny][nx]) also wacc[s][0..3] = float64 sums of w, w y,
- *   w x, w x_shifted.  acc, gid (and wacc) are zeroed first; integer sums are bitwise reproducible. */
+ *   w x, w x_shifted.  acc, gid (and wacc) are zeroed first; integer sums are bitwise reproducible.
+ * marex_event_rename_i32 (the apply_ufunc map of track.py:2897-2924 and the pass above fused, in place, with compact
+ *   slots): ids int32 [T][ny * nx]; e = lut[v] for 0 < v = ids[t][c] < lut_len, else 0, an e outside 1 .. n_ev becomes 0,
+ *   and e is written back where it differs from v.  Event e owns the slots ev_off[e] .. ev_off[e + 1] - 1, one per
+ *   timestep from ev_tmin[e] on (ev_tmin int32 [n_ev + 1], ev_off int64 [n_ev + 2], entry 0 unused / 0; n_slots =
+ *   ev_off[n_ev + 1]): a cell of e at t goes to s = ev_off[e] + t - ev_tmin[e].  acc uint64 [n_slots][5], gid int32
+ *   [n_slots] (the largest v under the slot) and, with w, wacc float64 [n_slots][4] as in marex_event_moments_i32; all
+ *   three and status are zeroed first.  A cell whose event lies outside its declared span (t < ev_tmin[e] or
+ *   s >= ev_off[e + 1], or s >= n_slots) is renamed but not accumulated and adds one to status[0] (uint64 [1]): no slot
+ *   index that was not range-checked addresses acc, gid or wacc.  -1: null pointer or empty shape; -4: ny * nx or T of
+ *   2^31 - 1 or more (the field itself may hold any number of cells: it is addressed with 64-bit offsets). */
 int marex_relabel_i32(marex_ctx* ctx, int32_t* ids, int64_t n, const int32_t* keys, const int32_t* vals, int n_keys);
 int marex_partition_centroid_i32(marex_ctx* ctx, int32_t* ids, int ny, int nx, const int32_t* child_keys, int n_child,
                                  const int32_t* off, const double* pcy, const double* pcx, const int32_t* lab, int wrap);
@@ -572,6 +582,9 @@ int marex_partition_nn_i32(marex_ctx* ctx, int32_t* ids, const int32_t* prev, in
                            int wrap);
 int marex_event_moments_i32(marex_ctx* ctx, const int32_t* ev, const int32_t* orig, int64_t T, int ny, int nx, int n_ev,
                             const float* w, uint64_t* acc, double* wacc, int32_t* gid);
+int marex_event_rename_i32(marex_ctx* ctx, int32_t* ids, int64_t T, int ny, int nx, const int32_t* lut, int64_t lut_len,
+                           int n_ev, const int32_t* ev_tmin, const int64_t* ev_off, int64_t n_slots, const float* w,
+                           uint64_t* acc, double* wacc, int32_t* gid, uint64_t* status);
 
 /* The partition kernels of the split-and-merge stage on an unstructured mesh (tracker.split_and_merge_objects_parallel,
  * marEx/track.py:3804-4814, 5246-5419).  A slice is int32 [C], values <= 0 are background, C below 2^31 - 1.  u: float64

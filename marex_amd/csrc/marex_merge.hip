@@ -276,6 +276,131 @@ k_mrg_event_moments(const int* __restrict__ ev, const int* __restrict__ orig, lo
     }
 }
 
+#define MRG_ITERS 16                  // 64-cell pieces per wave of the rename pass
+#define MRG_BATCH 4                   // pieces loaded together (loads in flight per lane); MRG_ITERS is a multiple
+#define MRG_CHUNK (256 * MRG_ITERS)   // cells of a slice per workgroup (4 waves)
+#define MRG_TSTRIDE 64                // slices in flight: a workgroup walks every MRG_TSTRIDE-th slice
+
+// cluster_rename_objects_and_props in one pass over the field, in place: ids[t][c] = e = lut[v] for 0 < v = ids[t][c] <
+// lut_len (anything else, and an e outside 1 .. n_ev: 0), written back only where it differs, and for e > 0 the compact
+// slot s = ev_off[e] + (t - ev_tmin[e]) takes the sums of k_mrg_event_moments (same definitions) and gid[s] = max v.
+// A cell is read and written by one lane only.  A wave walks MRG_ITERS consecutive 64-cell pieces of a slice, groups the
+// lanes of a piece by event (ballot) and carries the run of an event across its pieces in uniform registers (the pieces
+// are loaded MRG_BATCH at a time: unrolling all of them costs more registers than the loads in flight are worth); the run is
+// flushed once, when the event changes: lanes 0 .. 3 add the four integer sums (and the four float64 sums) of the slot as
+// ONE wave instruction over 32 contiguous bytes each, lane 4 sets the flags, lane 5 the largest original ID -- the
+// interior of a large event costs one set of atomics per 1024 cells, not one per piece.  The slot index is checked against
+// the event's own span [ev_off[e], ev_off[e + 1]) and against n_slots before it addresses anything; a run outside it adds
+// its cells to status[0] instead.
+template <bool WEIGHTED>
+__global__ void __launch_bounds__(256)
+k_mrg_event_rename(int* ids, long T, int ny, int nx, const int* __restrict__ lut, long lut_len, int n_ev,
+                   const int* __restrict__ ev_tmin, const long long* __restrict__ ev_off, long long n_slots,
+                   const float* __restrict__ w, u64* __restrict__ acc, double* __restrict__ wacc, int* __restrict__ gid,
+                   u64* __restrict__ status) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long C = (long)ny * nx;
+    const long rw = (long)blockIdx.x * MRG_CHUNK + (long)wave * (64 * MRG_ITERS);
+    for (long t = blockIdx.y; t < T; t += gridDim.y) {
+        int* row = ids + t * C;
+        int cur = 0, big = 0;
+        unsigned cfl = 0;
+        long long n = 0, sy = 0, sx = 0, sxs = 0;
+        double wa = 0, wy = 0, wx = 0, wxs = 0;
+        auto flush = [&]() {
+            if (cur <= 0) return;  // wave-uniform
+            const int tm = ev_tmin[cur];
+            const long long o0 = ev_off[cur], o1 = ev_off[cur + 1];
+            const long long s = o0 + ((long long)t - tm);
+            if (t < tm || o0 < 0 || s >= o1 || s >= n_slots) {  // outside the declared span: counted, not accumulated
+                if (lane == 0) atomicAdd(status, (u64)n);
+                return;
+            }
+            u64* p = acc + (size_t)s * MRG_NMOM;
+            if (lane < 4) {
+                atomicAdd(p + lane, (u64)(lane == 0 ? n : lane == 1 ? sy : lane == 2 ? sx : sxs));
+                if (WEIGHTED) atomicAdd(wacc + (size_t)s * MRG_NWMOM + lane, lane == 0 ? wa : lane == 1 ? wy : lane == 2 ? wx : wxs);
+            } else if (lane == 4) {
+                if (cfl) atomicOr(p + 4, (u64)cfl);
+            } else if (lane == 5) {
+                atomicMax(gid + s, big);
+            }
+        };
+#pragma unroll 1
+        for (int b = 0; b < MRG_ITERS; b += MRG_BATCH) {
+            if (rw + 64 * b >= C) break;  // wave-uniform
+            int v[MRG_BATCH], ev[MRG_BATCH];
+#pragma unroll
+            for (int k = 0; k < MRG_BATCH; ++k) {
+                const long r = rw + 64 * (b + k) + lane;
+                v[k] = r < C ? row[r] : 0;
+            }
+#pragma unroll
+            for (int k = 0; k < MRG_BATCH; ++k) {
+                const long r = rw + 64 * (b + k) + lane;
+                int e = (v[k] > 0 && (long)v[k] < lut_len) ? lut[v[k]] : 0;
+                e = (e > 0 && e <= n_ev) ? e : 0;  // ev_tmin / ev_off below are never indexed by an unchecked value
+                ev[k] = e;
+                if (r < C && e != v[k]) row[r] = e;
+            }
+#pragma unroll  // v[k], ev[k] must stay in registers: no dynamic indexing
+            for (int k = 0; k < MRG_BATCH; ++k) {
+                const long r0 = rw + 64 * (b + k);
+                if (r0 >= C) break;  // wave-uniform
+                const int e = ev[k];
+                u64 todo = __ballot(e > 0);
+                if (!todo) continue;
+                const unsigned r = (unsigned)(r0 + lane);  // below 2^31 - 1 wherever e > 0
+                const int y = (int)(r / (unsigned)nx), x = (int)(r % (unsigned)nx);
+                const int xs = 2 * x > nx ? x - nx : x;
+                const unsigned fl = (x < 100 ? 1u : 0u) | (x >= nx - 100 ? 2u : 0u);
+                float wc = 0.f;
+                if (WEIGHTED && e > 0) wc = w[r0 + lane];  // e > 0 implies r0 + lane < C
+                while (todo) {
+                    const int lead = __ffsll((long long)todo) - 1;
+                    const int el = __shfl(e, lead, 64);
+                    const u64 same = __ballot(e == el) & todo;
+                    todo &= ~same;
+                    const bool me = (same >> lane) & 1ull;
+                    const long long gy = mrg_wave_sum_i64(me ? y : 0), gx = mrg_wave_sum_i64(me ? x : 0),
+                                    gxs = mrg_wave_sum_i64(me ? xs : 0);
+                    const u64 bl = __ballot(me && (fl & 1u)), br = __ballot(me && (fl & 2u));
+                    const int gm = mrg_wave_max_i32(me ? v[k] : 0);  // v > 0 wherever e > 0
+                    double ga = 0, gwy = 0, gwx = 0, gwxs = 0;
+                    if (WEIGHTED) {
+                        const double a = me ? (double)wc : 0.0;
+                        ga = mrg_wave_sum_f64(a);
+                        gwy = mrg_wave_sum_f64(a * (double)y);
+                        gwx = mrg_wave_sum_f64(a * (double)x);
+                        gwxs = mrg_wave_sum_f64(a * (double)xs);
+                    }
+                    if (el != cur) {
+                        flush();
+                        cur = el;
+                        n = sy = sx = sxs = 0;
+                        wa = wy = wx = wxs = 0;
+                        big = 0;
+                        cfl = 0;
+                    }
+                    n += __popcll(same);
+                    sy += gy;
+                    sx += gx;
+                    sxs += gxs;
+                    cfl |= (bl ? 1u : 0u) | (br ? 2u : 0u);
+                    big = gm > big ? gm : big;
+                    if (WEIGHTED) {
+                        wa += ga;
+                        wy += gwy;
+                        wx += gwx;
+                        wxs += gwxs;
+                    }
+                }
+            }
+        }
+        flush();
+    }
+}
+
 static inline unsigned mrg_grid(long n) { return (unsigned)(n < 256L * 8192 ? (n + 255) / 256 : 8192); }
 
 extern "C" int marex_relabel_i32(marex_ctx* ctx, int32_t* ids, int64_t n, const int32_t* keys, const int32_t* vals,
@@ -365,6 +490,33 @@ extern "C" int marex_event_moments_i32(marex_ctx* ctx, const int32_t* ev, const 
     const unsigned gy = (unsigned)(T < 64 ? T : 64);
     hipLaunchKernelGGL(k_mrg_event_moments, dim3(gx, gy), dim3(256), 0, ctx->stream, ev, orig, (long)T, ny, nx, n_ev, w,
                        (u64*)acc, wacc, gid);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
+extern "C" int marex_event_rename_i32(marex_ctx* ctx, int32_t* ids, int64_t T, int ny, int nx, const int32_t* lut,
+                                      int64_t lut_len, int n_ev, const int32_t* ev_tmin, const int64_t* ev_off,
+                                      int64_t n_slots, const float* w, uint64_t* acc, double* wacc, int32_t* gid,
+                                      uint64_t* status) {
+    if (!ctx) return -1;
+    if (!ids || !lut || !ev_tmin || !ev_off || !acc || !gid || !status || (w && !wacc) || T <= 0 || ny <= 0 || nx <= 0 ||
+        lut_len <= 0 || n_ev <= 0 || n_slots <= 0)
+        return fail(ctx, -1, "marex_event_rename_i32: null pointer, empty field, empty table or no slot");
+    const long C = (long)ny * nx;
+    if (C >= 2147483647L || T >= 2147483647L) return fail(ctx, -4, "marex_event_rename_i32: a slice or the time axis has 2^31 - 1 or more entries");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    LaunchTimer lt(ctx, MAREX_K_MORPH);
+    HIP_TRY(ctx, hipMemsetAsync(acc, 0, (size_t)n_slots * MRG_NMOM * sizeof(u64), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(gid, 0, (size_t)n_slots * sizeof(int32_t), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(status, 0, sizeof(u64), ctx->stream));
+    if (w) HIP_TRY(ctx, hipMemsetAsync(wacc, 0, (size_t)n_slots * MRG_NWMOM * sizeof(double), ctx->stream));
+    const dim3 grid((unsigned)((C + MRG_CHUNK - 1) / MRG_CHUNK), (unsigned)(T < MRG_TSTRIDE ? T : MRG_TSTRIDE));
+    if (w)
+        hipLaunchKernelGGL(k_mrg_event_rename<true>, grid, dim3(256), 0, ctx->stream, ids, (long)T, ny, nx, lut, (long)lut_len, n_ev,
+                           ev_tmin, (const long long*)ev_off, (long long)n_slots, w, (u64*)acc, wacc, gid, (u64*)status);
+    else
+        hipLaunchKernelGGL(k_mrg_event_rename<false>, grid, dim3(256), 0, ctx->stream, ids, (long)T, ny, nx, lut, (long)lut_len, n_ev,
+                           ev_tmin, (const long long*)ev_off, (long long)n_slots, w, (u64*)acc, wacc, gid, (u64*)status);
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }

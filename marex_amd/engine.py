@@ -1205,6 +1205,53 @@ class HotPath:
             out["wmom"] = wacc.cpu().numpy().reshape(T, n_ev, 4)
         return out
 
+    def event_rename(self, ids: torch.Tensor, ny: int, nx: int, lut, ev_tmin, ev_tmax,
+                     weights: Optional[torch.Tensor] = None) -> Dict[str, np.ndarray]:
+        """The device pass of cluster_rename_objects_and_props on a grid (track.py:2897-2976, 3140-3247), in one kernel and
+        in place, with compact slots: ``ids`` int32 ``[T, ny * nx]`` -> ``lut[id]`` for ``0 < id < len(lut)``, else 0
+        (``lut``: int32 event numbers 0..n_ev).  ``ev_tmin`` / ``ev_tmax`` (int, ``[n_ev + 1]``, entry 0 unused) declare the
+        first and last timestep of every event (``tmax < tmin``: absent); event ``e`` owns one slot per step of that span,
+        ``off[e] + t - ev_tmin[e]``, with ``off`` (int64 ``[n_ev + 2]``) the exclusive scan of the span lengths.  Returns
+        ``off`` and, over the ``off[-1]`` slots, ``mom`` int64 ``[n, 5]`` and ``gid`` int32 ``[n]`` as
+        :meth:`event_moments` defines them and, with float32 ``weights`` of a slice, ``wmom`` float64 ``[n, 4]``.  A cell of an
+        event outside its declared span is renamed but raises :class:`ProcessingError` (nothing is written out of range)."""
+        T, Cn = self._ids_check(ids)
+        if Cn != ny * nx:
+            raise ProcessingError(f"event_rename: {Cn} cells per slice, ny * nx = {ny * nx}")
+        lut_h = np.asarray(lut)
+        tmin_h, tmax_h = np.asarray(ev_tmin, dtype=np.int64), np.asarray(ev_tmax, dtype=np.int64)
+        n_ev = int(tmin_h.size) - 1
+        if lut_h.dtype != np.int32 or lut_h.ndim != 1 or lut_h.size == 0:
+            raise ProcessingError("event_rename: the table must be a non-empty int32 vector", details=f"got {lut_h.dtype} {lut_h.shape}")
+        if n_ev <= 0 or tmin_h.ndim != 1 or tmax_h.shape != tmin_h.shape or int(lut_h.max()) > n_ev:
+            raise ProcessingError("event_rename: ev_tmin and ev_tmax must have one entry per event 0..n_ev, n_ev > 0, and the "
+                                  "table must map to those events",
+                                  details=f"largest entry {int(lut_h.max())}, spans {tmin_h.shape} / {tmax_h.shape}")
+        length = np.where((tmax_h >= tmin_h) & (tmin_h >= 0) & (tmax_h < T), tmax_h - tmin_h + 1, 0)
+        length[0] = 0
+        off = np.zeros(n_ev + 2, np.int64)
+        np.cumsum(length, out=off[1:])
+        n_slots = int(off[-1])
+        per = 44 + (32 if weights is not None else 0)
+        self._check_fits(per * n_slots + 4 * lut_h.size + 12 * (n_ev + 2), "event properties",
+                         f"{n_slots} (timestep, event) slots between each event's first and last timestep, {per} bytes each, "
+                         f"and the tables of {lut_h.size} IDs and {n_ev} events")
+        alloc = max(n_slots, 1)  # no event has a step: one slot that nothing addresses
+        acc = torch.empty((alloc, 5), dtype=torch.int64, device=self.device)
+        gid = torch.empty(alloc, dtype=torch.int32, device=self.device)
+        wacc = torch.empty((alloc, 4), dtype=torch.float64, device=self.device) if weights is not None else None
+        status = torch.empty(1, dtype=torch.int64, device=self.device)
+        self.call("marex_event_rename_i32", ids, T, int(ny), int(nx), self._dev(lut_h), lut_h.size, n_ev,
+                  self._dev(np.clip(tmin_h, 0, 2**31 - 1).astype(np.int32)), self._dev(off), alloc, weights, acc, wacc, gid, status)
+        bad = int(status.item())
+        if bad:
+            raise ProcessingError(f"event_rename: {bad} cells belong to an event outside its declared span of timesteps",
+                                  details="ev_tmin / ev_tmax do not cover the field; the cells were renamed, not accumulated")
+        out = {"off": off, "mom": acc[:n_slots].cpu().numpy(), "gid": gid[:n_slots].cpu().numpy()}
+        if wacc is not None:
+            out["wmom"] = wacc[:n_slots].cpu().numpy()
+        return out
+
     def filter_small_objects(self, data_bin: torch.Tensor, ny: int, nx: int, area_filter_quartile: float = 0.5,
                              area_filter_absolute: Optional[float] = None, regional_mode: bool = False,
                              wsp: Optional[dict] = None) -> Dict[str, object]:

@@ -141,6 +141,74 @@ def plan_preprocess_blocks(T: int, C: int, T_fill: int, free_bytes: int, ny: Opt
     return lo
 
 
+def merge_memory_need(T: int, ny: int, nx: int, block_steps: int, resident: bool = False, weights: bool = False) -> Dict[str, int]:
+    """Bytes of the ``[T, C]`` device buffers alive at the peak of merge tracking with ``merge_block_steps=block_steps``
+    (``tracker.track_objects``), by name.  The peak is inside the per-timestep labelling: the
+    pre-processed uint8 mask (unless it is ``resident`` already), the int32 ID field, the labelling's scratch of one block
+    -- its int32 areas and the library's int32 rank array, 8 bytes per cell of ``min(block_steps, T)`` steps, of at most
+    2^31 - 2 cells -- and, with ``weights``, the float32 cell areas of one slice.  Everything after it runs on the ID field
+    alone: the merge loop works on two slices, the cluster renaming is in place.
+
+    Not knowable before the run, and therefore not in here: the hash table of the final overlap pass (32 bytes per run of
+    equal pairs of one block), the compact (timestep, event) slots of the renaming (44 bytes each, 76 with weights) and
+    the per-object tables (about 100 bytes per (timestep, object) slot of the properties, 16 per ID).  Each of them is
+    checked against the free device memory where it is allocated."""
+    T, C = int(T), int(ny) * int(nx)
+    n = T * C
+    steps = max(1, min(int(block_steps), T, max(1, _BLOCK_CELLS // C)))
+    need = {} if resident else {"pre-processed mask uint8": n}
+    need["ID field int32"] = 4 * n
+    need["labelling scratch int32 (areas and ranks of one block)"] = 8 * steps * C
+    if weights:
+        need["cell areas float32 (one slice)"] = 4 * C
+    return need
+
+
+def plan_merge_blocks(T: int, ny: int, nx: int, free_bytes: int, resident: bool = False, weights: bool = False) -> int:
+    """The largest ``merge_block_steps`` (at most ``T``, and at most 2^31 - 2 cells a block) whose :func:`merge_memory_need`
+    fits ``free_bytes``.  :class:`TrackingError` with both numbers when even one step does not fit.  Needs no GPU."""
+    T, C = int(T), int(ny) * int(nx)
+    if T <= 0 or C <= 0:
+        raise TrackingError(f"cannot plan merge-tracking blocks for an empty field ({T} steps of {C} cells)")
+    if C > _BLOCK_CELLS:
+        raise TrackingError(f"one timestep of {C} cells exceeds the labelling block of {_BLOCK_CELLS} cells")
+    need = lambda b: merge_memory_need(T, ny, nx, b, resident, weights)  # noqa: E731
+    fits = lambda b: sum(need(b).values()) <= int(free_bytes)  # noqa: E731
+    if not fits(1):
+        n1 = need(1)
+        raise TrackingError(f"merge tracking in time blocks: one step per block needs {sum(n1.values()) / 1e9:.3f} GB "
+                            f"of device memory, {int(free_bytes) / 1e9:.3f} GB are free",
+                            details="; ".join(f"{k} {v / 1e9:.3f} GB" for k, v in n1.items()),
+                            suggestions=["Track a shorter record", "Free device memory held by other arrays"])
+    lo, hi = 1, max(1, min(T, _BLOCK_CELLS // C))  # the need grows with B: bisect
+    while lo < hi:
+        mid = (lo + hi + 1) // 2
+        if fits(mid):
+            lo = mid
+        else:
+            hi = mid - 1
+    return lo
+
+
+def merge_block_pairs(lists) -> np.ndarray:
+    """One overlap list out of the lists of consecutive time blocks (each ``(n, 3)`` ``[id at t, id at t + 1, cells]``, the
+    blocks sharing one step across every seam, so that every pair of steps is counted in exactly one of them): equal pairs
+    are merged and their counts summed -- after merging an ID lives through many steps and meets the same neighbour in
+    several blocks -- and the rows come out sorted lexicographically, ``(n, 3)`` int32, as ``HotPath.overlap_pairs`` over the
+    whole field gives them.  :class:`ProcessingError` when a sum does not fit int32."""
+    rows = [np.asarray(r, dtype=np.int64).reshape(-1, 3) for r in lists if len(r)]
+    if not rows:
+        return np.zeros((0, 3), np.int32)
+    a = np.concatenate(rows)
+    k, inv = np.unique((a[:, 0] << 32) | a[:, 1], return_inverse=True)
+    c = np.zeros(k.size, np.int64)
+    np.add.at(c, inv.reshape(-1), a[:, 2])
+    if c.max() > _I32_MAX:
+        raise ProcessingError("overlap pairs: a pair overlaps in 2^31 or more cells, which int32 cannot hold",
+                              details=f"largest overlap {int(c.max())} cells")
+    return np.stack([k >> 32, k & 0xFFFFFFFF, c], axis=1).astype(np.int32)
+
+
 def _tensor_of(da):
     """The torch tensor behind a device-resident DataArray, else None (never copies)."""
     t = getattr(da, "device_tensor", None)
@@ -323,13 +391,22 @@ class tracker(_MeshStages):  # noqa: N801 -- the reference's public name (marEx.
     ``allow_merging=False`` and :meth:`identify_objects`.  :class:`TrackingError` is raised for a single timestep of
     2^31 - 1 cells or more, for more than 2^31 - 2 objects before the seams are joined, when the buffers of the run
     (:func:`tracking_memory_need`, about 12 bytes per cell) exceed the free device memory -- before anything is allocated,
-    with both numbers -- and by merge tracking (``allow_merging=True``) for fields of 2^31 - 1 cells and more.
+    with both numbers -- and by merge tracking (``allow_merging=True``) for fields of 2^31 - 1 cells and more unless
+    ``merge_block_steps`` is given.
 
     ``preprocess_block_steps`` (None: the whole-field path above) runs :meth:`run_preprocess` in time blocks of that many
     steps, or with ``"auto"`` of as many as the free device memory takes: the same mask and statistics, at the input, the
     output and a window of ``B + 2 T_fill`` steps (:func:`preprocess_memory_need`, about 2 bytes per cell); a host
     ``data_bin`` is then uploaded one window at a time.  :meth:`run` checks the larger of that and
     :func:`labelling_memory_need` instead.  On grids and on meshes.
+
+    ``merge_block_steps`` (None: merge tracking refuses fields of 2^31 - 1 cells and more, as above) lifts that limit for
+    ``allow_merging=True`` on grids: with a number of timesteps ``B``, or with ``"auto"`` the largest ``B`` that the free
+    device memory takes, :meth:`run` and :meth:`track_objects` label the objects and collect the final overlap pairs in
+    time blocks of at most ``B`` steps and 2^31 - 2 cells; every other pass addresses the field with 64-bit offsets and
+    stays whole.  The results do not depend on ``B``.  :meth:`run` then checks the larger of the pre-processing's need and
+    :func:`merge_memory_need` (the mask, the int32 ID field and 8 bytes per cell of one block) against the free device
+    memory; a single timestep of 2^31 - 1 cells or more stays refused.  Composes with ``preprocess_block_steps``.
 
     ``data_bin`` may be device resident -- a DataArray whose data is a torch tensor (bool or uint8) on the GPU, e.g. from
     ``zarr_io.open_dataarray_device`` -- and is then consumed without a host round trip.  ``device`` picks the GPU.
@@ -364,6 +441,7 @@ class tracker(_MeshStages):  # noqa: N801 -- the reference's public name (marEx.
         timechunks: Optional[int] = None,
         label_block_steps: Optional[int] = None,
         preprocess_block_steps: Union[int, str, None] = None,
+        merge_block_steps: Union[int, str, None] = None,
     ) -> None:
         supported = "gridded data without checkpointing"
         pbs = preprocess_block_steps
@@ -376,6 +454,15 @@ class tracker(_MeshStages):  # noqa: N801 -- the reference's public name (marEx.
             raise ConfigurationError("label_block_steps must be a positive number of timesteps",
                                      details=f"label_block_steps={label_block_steps!r}")
         self.label_block_steps = None if label_block_steps is None else int(label_block_steps)
+        mbs = merge_block_steps
+        if mbs is not None and mbs != "auto" and (isinstance(mbs, (bool, str)) or not isinstance(mbs, (int, np.integer)) or mbs <= 0):
+            raise ConfigurationError("merge_block_steps must be a positive number of timesteps, 'auto' or None",
+                                     details=f"merge_block_steps={mbs!r}")
+        if mbs is not None and (unstructured_grid or not allow_merging):
+            raise ConfigurationError("merge_block_steps is for merge tracking on grids (allow_merging=True, unstructured_grid=False)",
+                                     details="the basic tracker and the mesh tracker take fields of any length already",
+                                     suggestions=["Pass merge_block_steps=None"])
+        self.merge_block_steps = mbs if mbs is None or isinstance(mbs, str) else int(mbs)
         self._time_chunks = None
         if allow_merging and not unstructured_grid:
             # merge results depend on the time chunks the per-timestep loop walks (track.py:3379-3382, 3602-3615)
@@ -602,6 +689,37 @@ class tracker(_MeshStages):  # noqa: N801 -- the reference's public name (marEx.
         need = tracking_memory_need(T, ny, nx, self.R_fill, self.T_fill, resident=resident)
         self._check_fits(self._engine(), need, "tracker.run", suggestions=["Pass preprocess_block_steps='auto'"])
 
+    def _merge_plan(self, eng, T: int, ny: int, nx: int, resident: bool) -> Tuple[int, Dict[str, int]]:
+        """``(B, need)`` of merge tracking in time blocks: ``merge_block_steps`` as given, or with ``"auto"`` the largest
+        block that fits fifteen sixteenths of the free device memory (the rule of :meth:`_preprocess_plan`); never more
+        than 2^31 - 2 cells a block.  A single slice of 2^31 - 1 cells or more stays refused."""
+        C = ny * nx
+        if C > _BLOCK_CELLS:
+            raise TrackingError(f"one timestep of {C} cells exceeds the labelling block of {_BLOCK_CELLS} cells",
+                                details="merge tracking in time blocks needs a single slice below 2^31 - 1 cells")
+        weights = self._cell_weights is not None
+        if self.merge_block_steps == "auto":
+            free = self._free_bytes(eng)
+            B = plan_merge_blocks(T, ny, nx, free - free // 16, resident=resident, weights=weights)
+        else:
+            B = min(int(self.merge_block_steps), T, max(1, _BLOCK_CELLS // C))
+        return B, merge_memory_need(T, ny, nx, B, resident=resident, weights=weights)
+
+    def _check_merge_memory(self, shape) -> None:
+        """Merge tracking with ``merge_block_steps``: the larger of the pre-processing's buffers and of
+        :func:`merge_memory_need` against the free device memory, before any device work."""
+        T, ny, nx = (int(shape[k]) for k in self._perm)
+        resident = _tensor_of(self.data_bin) is not None
+        eng = self._engine()
+        if self.preprocess_block_steps is not None:
+            _, pre = self._preprocess_plan(eng, T, ny, ny * nx, resident)
+            pre = {k: v for k, v in pre.items() if k != _RESIDENT_INPUT}
+        else:
+            pre = tracking_memory_need(T, ny, nx, self.R_fill, self.T_fill, resident=resident)
+        _, mrg = self._merge_plan(eng, T, ny, nx, resident=False)
+        self._check_fits(eng, pre if sum(pre.values()) >= sum(mrg.values()) else mrg, "tracker.run",
+                         suggestions=[] if self.preprocess_block_steps is not None else ["Pass preprocess_block_steps='auto'"])
+
     @staticmethod
     def _ids_to_host(eng, ids) -> np.ndarray:
         """The int32 ``[T, C]`` ID field as a NumPy array; a large one goes through the engine's pinned staging buffers
@@ -659,8 +777,10 @@ class tracker(_MeshStages):  # noqa: N801 -- the reference's public name (marEx.
         if self.unstructured_grid:
             self._mesh_need_chunks("tracker.run")
             self._mesh_merge_chunks()  # a chunk of one step is refused before the pre-processing, not after it
-        if self.allow_merging or self.unstructured_grid:
+        if self.unstructured_grid or (self.allow_merging and self.merge_block_steps is None):
             self._check_size(self.data_bin.shape)
+        elif self.allow_merging:
+            self._check_merge_memory(self.data_bin.shape)
         else:
             self._check_memory(self.data_bin.shape)
         data_bin_preprocessed, object_stats = self.run_preprocess(checkpoint=checkpoint)
@@ -1198,10 +1318,12 @@ class tracker(_MeshStages):  # noqa: N801 -- the reference's public name (marEx.
         if it == 10:
             logger.warning(f"Resolving mergers at timestep {t} did not converge after 10 iterations")
 
-    def _split_and_merge(self, eng, ids, props: _Props, nx: int):
+    def _split_and_merge(self, eng, ids, props: _Props, nx: int, block_steps: Optional[int] = None):
         """split_and_merge_objects (track.py:3337-3802) on the device field ``ids`` int32 [T, C], in place: returns the
         final overlap pairs (n, 2) and the merge records.  After the merges of step u, step u is consolidated against
-        u - 1 (at relative step u + 1 of its chunk, or by the end-of-chunk pass), except when u is alone in its chunk."""
+        u - 1 (at relative step u + 1 of its chunk, or by the end-of-chunk pass), except when u is alone in its chunk.
+        With ``block_steps`` the final overlap pass over the whole field runs in time blocks of that many steps, one step
+        shared across each seam (its hash table then has the size of one block's runs), merged by :func:`merge_block_pairs`."""
         T = ids.shape[0]
         chunks = self._time_chunks or [T]
         if sum(chunks) != T:
@@ -1218,7 +1340,14 @@ class tracker(_MeshStages):  # noqa: N801 -- the reference's public name (marEx.
             if L >= 2:
                 self._consolidate(eng, ids, start + L - 1, props, nx)
             start += L
-        ov = self._enforce(eng.overlap_pairs(ids), props)
+        if block_steps is None:
+            ov = eng.overlap_pairs(ids)
+        else:
+            from .engine import plan_time_blocks
+
+            blocks = plan_time_blocks(T, ids.shape[1], int(block_steps) * ids.shape[1])
+            ov = merge_block_pairs([eng.overlap_pairs(ids[t0:min(t1 + 1, T)]) for t0, t1 in blocks])
+        ov = self._enforce(ov, props)
         if len(ov):
             uc, cc = np.unique(ov[:, 1], return_counts=True)
             if (cc > 1).any():
@@ -1254,7 +1383,7 @@ class tracker(_MeshStages):  # noqa: N801 -- the reference's public name (marEx.
     def _cluster_rename_events(self, eng, ids, overlaps, merges_ds, merge_tidx, device_pass, field_dims, field_shape):
         """cluster_rename_objects_and_props (track.py:2809-3335) around the device pass, for grids and meshes alike: the
         events are the connected components of the overlap pairs over the IDs of the field and of the pair list, numbered
-        by their smallest ID; ``device_pass(lut, N)`` relabels ``ids`` (int32 ``[T, C]`` on the device) in place through the
+        by their smallest ID; ``device_pass(lut, N, spans)`` (``spans``: :meth:`HotPath.id_spans` of the field) relabels ``ids`` (int32 ``[T, C]`` on the device) in place through the
         ID -> event table and returns ``(gid, area, lat, lon)`` over the ``[T, N]`` (timestep, event) slots -- the largest
         original ID (0: the event is absent), float32 area and the centroid in degrees, whatever they hold where the event
         is absent.  Presence, time_start / time_end and the merge ledger follow from ``gid`` and ``merges_ds``.  Returns
@@ -1278,7 +1407,7 @@ class tracker(_MeshStages):  # noqa: N801 -- the reference's public name (marEx.
             gid = np.zeros((T, 0), np.int32)
             area_all, lat_all, lon_all = (np.zeros((T, 0), np.float32) for _ in range(3))
         else:
-            gid, area_all, lat_all, lon_all = device_pass(lut, N)
+            gid, area_all, lat_all, lon_all = device_pass(lut, N, sp)
         ev = ids
         pres = gid > 0
         t_first = np.argmax(pres, axis=0)
@@ -1311,38 +1440,53 @@ class tracker(_MeshStages):  # noqa: N801 -- the reference's public name (marEx.
 
     def _cluster_rename(self, eng, ids, ny: int, nx: int, overlaps, merges_ds, merge_tidx):
         """cluster_rename_objects_and_props (track.py:2809-3335), grids, with ``ids`` on the device (relabelled in place
-        to event IDs): relabel, then the event moments over the relabelled field and a copy of the original one."""
+        to event IDs) by one pass, :meth:`HotPath.event_rename`: an event's span of timesteps is the union of the spans of
+        its IDs, its compact slots are turned into area and centroid and scattered into the dense ``[T, N]`` host arrays."""
         import torch
 
         T = ids.shape[0]
 
-        def device_pass(lut, N):
-            orig = ids.clone()
-            eng.relabel(ids, lut)
+        def device_pass(lut, N, spans):
+            tmin, tmax = spans if spans is not None else (np.zeros(0, np.int32), np.zeros(0, np.int32))  # None: no ID > 0
+            live = np.nonzero(tmax[:lut.size] >= 0)[0]
+            live = live[(live > 0) & (lut[live] > 0)]
+            ev_tmin = np.full(N + 1, _I32_MAX, np.int64)
+            ev_tmax = np.full(N + 1, -1, np.int64)
+            np.minimum.at(ev_tmin, lut[live], tmin[live])
+            np.maximum.at(ev_tmax, lut[live], tmax[live])
             w = None if self._cell_weights is None else torch.from_numpy(self._cell_weights.reshape(-1)).to(eng.device)
-            r = eng.event_moments(ids, orig, ny, nx, N, w)
-            del orig
+            r = eng.event_rename(ids, ny, nx, lut, ev_tmin, ev_tmax, w)
             mom = r["mom"]
-            cnt = mom[..., 0]
+            cnt = mom[:, 0]
             with np.errstate(invalid="ignore", divide="ignore"):
                 if self._cell_weights is None:
                     tot = cnt.astype(np.float64)
-                    sy, sx, sxs = mom[..., 1], mom[..., 2], mom[..., 3]
+                    sy, sx, sxs = mom[:, 1], mom[:, 2], mom[:, 3]
                     area = cnt.astype(np.float32)
                 else:
                     wm = r["wmom"]
-                    tot = wm[..., 0].astype(np.float32).astype(np.float64)  # the reference's float32 np.sum of the cell areas
-                    sy, sx, sxs = wm[..., 1], wm[..., 2], wm[..., 3]
-                    area = wm[..., 0].astype(np.float32)
+                    tot = wm[:, 0].astype(np.float32).astype(np.float64)  # the reference's float32 np.sum of the cell areas
+                    sy, sx, sxs = wm[:, 1], wm[:, 2], wm[:, 3]
+                    area = wm[:, 0].astype(np.float32)
                 cy = sy / tot
                 cx = sx / tot
                 if not self.regional_mode:
-                    seam = (mom[..., 4] & 3) == 3
+                    seam = (mom[:, 4] & 3) == 3
                     cxs = sxs / tot
                     cxs = np.where(cxs < 0, cxs + nx, cxs)
                     cx = np.where(seam, cxs, cx)
             lat, lon = np.asarray(self.lat), np.asarray(self.lon)
-            return r["gid"], area, np.interp(cy, np.arange(len(lat)), lat), np.interp(cx, np.arange(len(lon)), lon)
+            # slot -> (timestep, event): event e owns off[e] .. off[e + 1] - 1, one slot per step from ev_tmin[e] on
+            off = r["off"]
+            e_of = np.repeat(np.arange(N + 1), np.diff(off))
+            t_of = np.arange(e_of.size) - off[e_of] + ev_tmin[e_of]
+            dense = []
+            for v, dt in ((r["gid"], np.int32), (area, np.float32), (np.interp(cy, np.arange(len(lat)), lat), np.float64),
+                          (np.interp(cx, np.arange(len(lon)), lon), np.float64)):
+                d = np.zeros((T, N), dt)
+                d[t_of, e_of - 1] = v
+                dense.append(d)
+            return tuple(dense)
 
         return self._cluster_rename_events(eng, ids, overlaps, merges_ds, merge_tidx, device_pass, self._out_dims(), (T, ny, nx))
 
@@ -1384,12 +1528,20 @@ class tracker(_MeshStages):  # noqa: N801 -- the reference's public name (marEx.
         if self.unstructured_grid:
             self._mesh_need_chunks("tracker.track_objects")
             return self._mesh_track_objects(data_bin)
-        self._check_size(data_bin.shape)  # merge tracking keeps refusing fields of 2^31 - 1 cells and more
-        eng = self._engine()
+        B = None
+        if self.merge_block_steps is None:
+            self._check_size(data_bin.shape)  # without merge_block_steps: fields of 2^31 - 1 cells and more stay refused
+            eng = self._engine()
+        else:
+            eng = self._engine()
+            T, ny, nx = (int(data_bin.shape[k]) for k in self._perm_of(data_bin))
+            B, need = self._merge_plan(eng, T, ny, nx, resident=_tensor_of(data_bin) is not None)
+            self._check_fits(eng, need, "tracker.track_objects")
         st = self._stage_times = {}
         t0 = time.perf_counter()
         x, T, ny, nx = self._device_u8(data_bin, eng)
-        r = eng.label_objects_3d(x, ny, nx, wrap_x=not self.regional_mode, connect_t=False)
+        r = eng.label_objects_3d(x, ny, nx, wrap_x=not self.regional_mode, connect_t=False,
+                                 max_block_cells=None if B is None else B * ny * nx)
         ids = r["ids"].reshape(T, ny * nx)
         del x, r
         m = eng.object_moments(ids, ny, nx, wrap=not self.regional_mode)
@@ -1397,7 +1549,7 @@ class tracker(_MeshStages):  # noqa: N801 -- the reference's public name (marEx.
         eng.sync()
         st["objects"] = time.perf_counter() - t0
         t0 = time.perf_counter()
-        overlaps, merges = self._split_and_merge(eng, ids, props, nx)
+        overlaps, merges = self._split_and_merge(eng, ids, props, nx, block_steps=B)
         merges_ds = self._merges_dataset(merges)
         eng.sync()
         st["split_and_merge"] = time.perf_counter() - t0

@@ -851,7 +851,7 @@ class _MeshStages:
                                                details=f"{T} timesteps, {len(self.time_values)} time values")
         q, e = self._mesh_tables(eng)[0], self._mesh_e
 
-        def device_pass(lut, N):
+        def device_pass(lut, N, spans):  # dense slots on a mesh: the spans are not needed
             r = eng.mesh_event_rename(ids, lut, N, q, e)
             area, cen = mesh_moments_finish(r["mom"], e)
             return r["gid"], area, cen[0], cen[1]
