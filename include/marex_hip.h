@@ -586,6 +586,33 @@ int marex_event_rename_i32(marex_ctx* ctx, int32_t* ids, int64_t T, int ny, int 
                            int n_ev, const int32_t* ev_tmin, const int64_t* ev_off, int64_t n_slots, const float* w,
                            uint64_t* acc, double* wacc, int32_t* gid, uint64_t* status);
 
+/* Per-(timestep, event) intensity of tracked events: the event field joined with the anomaly field it was detected in (the
+ * reference leaves this to notebook code, groupby / where over ID_field and dat_anomaly).
+ *
+ * marex_event_intensity_f32: ids int32 [Tb][C] and anom float32 [Tb][C] are the rows t0 .. t0 + Tb - 1 of the field (a grid
+ *   slice flattened, or a mesh); values of ids outside 1 .. n_ev are background.  The slots are those of
+ *   marex_event_rename_i32: event e owns ev_off[e] .. ev_off[e + 1] - 1, one per timestep from ev_tmin[e] on (ev_tmin int32
+ *   [n_ev + 1], ev_off int64 [n_ev + 2], entry 0 unused / 0), and a cell of e in row r goes to s = ev_off[e] + (t0 + r) -
+ *   ev_tmin[e].  w: float32 [C] cell weights, or NULL for unit weights.  A cell with a finite anomaly a adds cnt[s][0] += 1,
+ *   sums[s][0] += (double)w, sums[s][1] += (double)w * (double)a (an exact product) and vmax[s] = max(vmax[s], key(a)),
+ *   key the order-preserving map of a float32 to uint32 (b = the bits of a; key = b | 2^31 for b < 2^31, ~b otherwise):
+ *   key 0 belongs to no finite value and means "no finite cell".  A cell whose anomaly is NaN or +-inf adds cnt[s][1] += 1
+ *   and nothing else.  cnt uint64 [n_slots][2], sums float64 [n_slots][2], vmax uint32 [n_slots], status uint64 [1]: the
+ *   function only adds -- the caller zeroes all four before the first block, so a field is walked in time blocks into the
+ *   same slots.  A cell whose event lies outside its declared span (t < ev_tmin[e], s >= ev_off[e + 1] or s >= n_slots)
+ *   adds one to status[0] and nothing else: no slot index that was not range-checked addresses cnt, sums or vmax.  The
+ *   anomalies (and weights) are fetched only under cells of an event.
+ *   Arithmetic: the counts and the maximum are exact and independent of any order.  The float64 sums are atomic adds of
+ *   exact terms: bit for bit reproducible whenever the partial sums are exactly representable, otherwise within
+ *   2 n u sum|w a| of the exact sum (n the finite cells of the slot, u = 2^-53; the order-independent bound of recursive
+ *   summation) -- the precedent of the weighted moments wacc of marex_event_rename_i32, not the integer contract of the
+ *   mesh areas.
+ *   -1: null pointer, empty shape, t0 < 0, n_ev <= 0 or n_slots <= 0; -4: C or t0 + Tb of 2^31 - 1 or more (the field itself
+ *   may hold any number of cells: it is addressed with 64-bit offsets).  Asynchronous on the context's stream. */
+int marex_event_intensity_f32(marex_ctx* ctx, const int32_t* ids, const float* anom, int64_t t0, int64_t Tb, int64_t C,
+                              int n_ev, const int32_t* ev_tmin, const int64_t* ev_off, int64_t n_slots, const float* w,
+                              uint64_t* cnt, double* sums, uint32_t* vmax, uint64_t* status);
+
 /* The partition kernels of the split-and-merge stage on an unstructured mesh (tracker.split_and_merge_objects_parallel,
  * marEx/track.py:3804-4814, 5246-5419).  A slice is int32 [C], values <= 0 are background, C below 2^31 - 1.  u: float64
  * [3][C], the unit vectors of the cells; pv: float64 [3][n], the unit vectors of the parents' centroids.  "Nearest" is the

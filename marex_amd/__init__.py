@@ -21,6 +21,7 @@ from .exceptions import (
     create_data_validation_error,
 )
 from .dask_adapter import preprocess_data_lazy
+from .intensity import event_intensity
 from .track import tracker
 from .xr_compat import DataArray, Dataset
 
@@ -28,6 +29,6 @@ __all__ = [
     "preprocess_data", "preprocess_data_lazy", "compute_normalised_anomaly", "identify_extremes", "rolling_climatology",
     "smoothed_rolling_climatology", "MarExError", "DataValidationError", "ConfigurationError",
     "ProcessingError", "DependencyError", "create_data_validation_error", "DataArray", "Dataset",
-    "tracker", "TrackingError",
+    "tracker", "TrackingError", "event_intensity",
 ]
 __version__ = "0.1.0"

@@ -1205,6 +1205,78 @@ class HotPath:
             out["wmom"] = wacc.cpu().numpy().reshape(T, n_ev, 4)
         return out
 
+    @staticmethod
+    def event_slot_plan(ev_tmin, ev_tmax, T: Optional[int] = None) -> np.ndarray:
+        """The compact (timestep, event) slots of :meth:`event_rename` and :meth:`event_intensity`: ``off`` int64
+        ``[n_ev + 2]``, the exclusive scan of the span lengths ``ev_tmax[e] - ev_tmin[e] + 1`` over the events 0..n_ev (entry
+        0 unused).  An event with ``tmax < tmin``, a negative ``tmin`` or (with ``T``) a ``tmax`` past the field is absent and
+        gets no slot.  Needs no device."""
+        tmin_h, tmax_h = np.asarray(ev_tmin, dtype=np.int64), np.asarray(ev_tmax, dtype=np.int64)
+        ok = (tmax_h >= tmin_h) & (tmin_h >= 0)
+        if T is not None:
+            ok &= tmax_h < T
+        length = np.where(ok, tmax_h - tmin_h + 1, 0)
+        length[:1] = 0
+        off = np.zeros(tmin_h.size + 1, np.int64)
+        np.cumsum(length, out=off[1:])
+        return off
+
+    def event_intensity(self, ids: torch.Tensor, anom: torch.Tensor, ev_tmin, ev_tmax, weights: Optional[torch.Tensor] = None,
+                        t0: int = 0, acc: Optional[dict] = None, finish: bool = True) -> Dict[str, object]:
+        """Per (timestep, event) intensity sums of the rows ``t0 .. t0 + Tb - 1`` of a tracked field
+        (``marex_event_intensity_f32``): ``ids`` int32 ``[Tb, C]`` (events 1..n_ev, anything else background) and ``anom``
+        float32 ``[Tb, C]``.  ``ev_tmin`` / ``ev_tmax`` (``[n_ev + 1]``, entry 0 unused, global timesteps) declare the slots
+        as in :meth:`event_rename` (:meth:`event_slot_plan`).  ``weights``: float32 ``[C]`` or None for unit weights.  The
+        first block allocates zeroed accumulators; a later block passes the ``"acc"`` entry of the previous result and adds
+        into the same slots, whatever the block length.  Returns ``off``, ``acc`` and -- unless ``finish`` is False, which
+        defers them and the one host read to a later block -- ``cnt`` int64 ``[n, 2]`` (finite cells, non-finite cells),
+        ``sums`` float64 ``[n, 2]`` (sum of w, sum of w a over the finite cells) and ``vmax`` float32 ``[n]`` (NaN: no finite
+        cell).  A cell of an event outside its declared span raises :class:`ProcessingError` (it was counted, nothing was
+        written out of range)."""
+        Tb, Cn = self._ids_check(ids)
+        if anom.dtype != torch.float32 or tuple(anom.shape) != (Tb, Cn) or not anom.is_contiguous() or anom.device != self.device:
+            raise ProcessingError(f"event_intensity: the anomalies must be a contiguous float32 [{Tb}, {Cn}] tensor on the "
+                                  f"engine's device", details=f"got {anom.dtype} {tuple(anom.shape)} on {anom.device}")
+        if weights is not None and (weights.dtype != torch.float32 or tuple(weights.shape) != (Cn,) or not weights.is_contiguous()
+                                    or weights.device != self.device):
+            raise ProcessingError(f"event_intensity: the weights must be a contiguous float32 [{Cn}] tensor on the engine's "
+                                  f"device", details=f"got {weights.dtype} {tuple(weights.shape)} on {weights.device}")
+        tmin_h, tmax_h = np.asarray(ev_tmin, dtype=np.int64), np.asarray(ev_tmax, dtype=np.int64)
+        n_ev = int(tmin_h.size) - 1
+        t0 = int(t0)
+        if n_ev <= 0 or tmin_h.ndim != 1 or tmax_h.shape != tmin_h.shape or t0 < 0:
+            raise ProcessingError("event_intensity: ev_tmin and ev_tmax must have one entry per event 0..n_ev, n_ev > 0, and t0 "
+                                  "must not be negative", details=f"spans {tmin_h.shape} / {tmax_h.shape}, t0 = {t0}")
+        off = self.event_slot_plan(tmin_h, tmax_h)
+        n_slots = int(off[-1])
+        alloc = max(n_slots, 1)  # no event has a step: one slot that nothing addresses
+        if acc is None:
+            self._check_fits(36 * n_slots + 12 * (n_ev + 2), "event intensity",
+                             f"{n_slots} (timestep, event) slots between each event's first and last timestep, 36 bytes each, "
+                             f"and the tables of {n_ev} events")
+            acc = {"cnt": self._buf(None, "int_cnt", (alloc, 2), torch.int64, self.device).zero_(),
+                   "sums": self._buf(None, "int_sums", (alloc, 2), torch.float64, self.device).zero_(),
+                   "vmax": self._buf(None, "int_vmax", (alloc,), torch.int32, self.device).zero_(),
+                   "status": self._buf(None, "int_status", (1,), torch.int64, self.device).zero_(),
+                   "tmin": self._dev(np.clip(tmin_h, 0, 2**31 - 1).astype(np.int32)), "off": self._dev(off), "plan": off}
+        elif tuple(acc["cnt"].shape) != (alloc, 2) or not np.array_equal(acc["plan"], off):
+            raise ProcessingError("event_intensity: the accumulators were planned for other spans",
+                                  details=f"{tuple(acc['cnt'].shape)[0]} slots there, {alloc} here")
+        self.call("marex_event_intensity_f32", ids, anom, t0, Tb, Cn, n_ev, acc["tmin"], acc["off"], alloc, weights,
+                  acc["cnt"], acc["sums"], acc["vmax"], acc["status"])
+        out = {"off": off, "acc": acc}
+        if not finish:
+            return out
+        bad = int(acc["status"].item())
+        if bad:
+            raise ProcessingError(f"event_intensity: {bad} cells belong to an event outside its declared span of timesteps",
+                                  details="ev_tmin / ev_tmax do not cover the field; the cells were counted, not accumulated")
+        key = acc["vmax"][:n_slots].cpu().numpy().view(np.uint32)
+        bits = np.where(key & np.uint32(0x80000000), key & np.uint32(0x7FFFFFFF), ~key)  # key 0 -> all ones: a NaN
+        out.update(cnt=acc["cnt"][:n_slots].cpu().numpy(), sums=acc["sums"][:n_slots].cpu().numpy(),
+                   vmax=bits.astype(np.uint32).view(np.float32))
+        return out
+
     def event_rename(self, ids: torch.Tensor, ny: int, nx: int, lut, ev_tmin, ev_tmax,
                      weights: Optional[torch.Tensor] = None) -> Dict[str, np.ndarray]:
         """The device pass of cluster_rename_objects_and_props on a grid (track.py:2897-2976, 3140-3247), in one kernel and
@@ -1227,10 +1299,7 @@ class HotPath:
             raise ProcessingError("event_rename: ev_tmin and ev_tmax must have one entry per event 0..n_ev, n_ev > 0, and the "
                                   "table must map to those events",
                                   details=f"largest entry {int(lut_h.max())}, spans {tmin_h.shape} / {tmax_h.shape}")
-        length = np.where((tmax_h >= tmin_h) & (tmin_h >= 0) & (tmax_h < T), tmax_h - tmin_h + 1, 0)
-        length[0] = 0
-        off = np.zeros(n_ev + 2, np.int64)
-        np.cumsum(length, out=off[1:])
+        off = self.event_slot_plan(tmin_h, tmax_h, T)
         n_slots = int(off[-1])
         per = 44 + (32 if weights is not None else 0)
         self._check_fits(per * n_slots + 4 * lut_h.size + 12 * (n_ev + 2), "event properties",

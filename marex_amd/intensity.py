@@ -1,0 +1,363 @@
+"""Per-event intensity metrics: the events of a tracker's ``ID_field`` joined with the anomaly field they were detected in.
+
+The reference leaves this step to notebook code (``groupby`` / ``where`` over ``ID_field`` and ``dat_anomaly``; its docs
+list "statistical summaries (event frequency, duration, intensity)" as the third step of the workflow).  Here it is one
+streaming pass on the device (``marex_event_intensity_f32``): per (timestep, event) the finite cells,
+the sum of the cell weights, the sum of weight x anomaly and the largest anomaly, into compact slots -- one per timestep
+between an event's first and last.  The host turns the slots into the Dataset in float64, in ascending time.
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import numpy as np
+
+from .exceptions import ConfigurationError, ProcessingError, TrackingError, create_data_validation_error
+from .track import _BLOCK_CELLS, PINNED_ID_FIELD_BYTES, _host, _tensor_of
+
+_I32_MAX = 2**31 - 1
+
+
+def float_key(a) -> np.ndarray:
+    """The order-preserving uint32 key of float32 values that the device maximum works on: ``bits | 2^31`` for a clear
+    sign bit, ``~bits`` otherwise.  Strictly monotone from -inf to +inf (-0 below +0); no finite value and neither infinity
+    maps to 0, which the kernel keeps for "no finite cell"."""
+    b = np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+    return np.where(b & np.uint32(0x80000000), ~b, b | np.uint32(0x80000000)).astype(np.uint32)
+
+
+def key_float(k) -> np.ndarray:
+    """Inverse of :func:`float_key`; key 0 gives a NaN."""
+    k = np.ascontiguousarray(k, dtype=np.uint32)
+    return np.where(k & np.uint32(0x80000000), k & np.uint32(0x7FFFFFFF), ~k).astype(np.uint32).view(np.float32)
+
+
+def _check_block_steps(block_steps):
+    b = block_steps
+    if b is not None and b != "auto" and (isinstance(b, (bool, str)) or not isinstance(b, (int, np.integer)) or b <= 0):
+        raise ConfigurationError("block_steps must be a positive number of timesteps, 'auto' or None", details=f"block_steps={b!r}")
+    return b if b is None or isinstance(b, str) else int(b)
+
+
+def _dtype_name(x) -> str:
+    t = _tensor_of(x)
+    if t is not None:
+        return str(t.dtype).replace("torch.", "")
+    return str(x.dtype if hasattr(x, "dtype") else np.asarray(x).dtype)
+
+
+def _kind(x) -> str:
+    """'i' for an integer field, 'f' for a float one, '?' for anything else (bool, complex, objects)."""
+    t = _tensor_of(x)
+    if t is not None:
+        if t.dtype.is_floating_point:
+            return "f"
+        return "?" if t.dtype.is_complex or "bool" in str(t.dtype) else "i"
+    k = np.dtype(_dtype_name(x)).kind
+    return "i" if k in "iu" else "f" if k == "f" else "?"
+
+
+def _time_of(field, T: int):
+    """``(name, values or None)`` of the leading (time) dimension of a field."""
+    dims = tuple(getattr(field, "dims", ()) or ())
+    name = dims[0] if dims else "time"
+    coords = getattr(field, "coords", None)
+    if coords is None or not dims:
+        return name, None
+    c = coords[name] if name in coords else next((coords[k] for k in coords if tuple(getattr(coords[k], "dims", ())) == (name,)), None)
+    if c is None:
+        return name, None
+    v = np.asarray(_host(c))
+    return name, (v if v.shape == (T,) else None)
+
+
+def _validate(ID_field, dat_anomaly, cell_areas):
+    """Everything that can be refused without a device: ``(shape, time name, time values, weights float32 [C] or None)``."""
+    shape = tuple(int(k) for k in ID_field.shape)
+    if len(shape) not in (2, 3):
+        raise create_data_validation_error("ID_field must be (time, y, x) or (time, cells)", details=f"got shape {shape}")
+    ashape = tuple(int(k) for k in dat_anomaly.shape)
+    if ashape != shape:
+        raise create_data_validation_error("ID_field and dat_anomaly differ in shape", details=f"ID_field {shape}, dat_anomaly {ashape}")
+    d_i, d_a = tuple(getattr(ID_field, "dims", ()) or ()), tuple(getattr(dat_anomaly, "dims", ()) or ())
+    if d_i and d_a and d_i != d_a:
+        raise create_data_validation_error("ID_field and dat_anomaly differ in their dimensions",
+                                           details=f"ID_field {d_i}, dat_anomaly {d_a}; the order must agree too")
+    if _kind(ID_field) != "i":
+        raise create_data_validation_error("Object IDs must be integers", details=f"Found dtype {_dtype_name(ID_field)}",
+                                           data_info={"actual_dtype": _dtype_name(ID_field)})
+    if _kind(dat_anomaly) != "f":
+        raise create_data_validation_error("dat_anomaly must be a floating-point field",
+                                           details=f"Found dtype {_dtype_name(dat_anomaly)}",
+                                           data_info={"actual_dtype": _dtype_name(dat_anomaly)})
+    T = shape[0]
+    tname, tv = _time_of(ID_field, T)
+    _, tv_a = _time_of(dat_anomaly, T)
+    if tv is not None and tv_a is not None and not np.array_equal(tv, tv_a):
+        raise create_data_validation_error("ID_field and dat_anomaly differ in their time coordinate",
+                                           details=f"the first difference is at step {int(np.argmax(tv != tv_a))}")
+    tv = tv if tv is not None else tv_a if tv_a is not None else np.arange(T)
+    w = None
+    if cell_areas is not None:
+        a = np.asarray(_host(cell_areas))
+        sp = shape[1:]
+        if a.dtype.kind not in "fiu":
+            raise create_data_validation_error("cell_areas must be numbers", details=f"Found dtype {a.dtype}")
+        a = a.astype(np.float32)
+        if len(sp) == 2 and a.ndim == 2 and d_i and tuple(getattr(cell_areas, "dims", ())) == (d_i[2], d_i[1]):
+            a = a.T
+        if a.shape == sp or a.shape == (int(np.prod(sp)),):
+            a = a.reshape(-1)
+        elif len(sp) == 2 and a.shape == (sp[0],):
+            a = np.broadcast_to(a[:, None], sp).reshape(-1)
+        else:
+            raise create_data_validation_error("cell_areas do not match the spatial shape of ID_field",
+                                               details=f"cell_areas {a.shape}, a timestep {sp}")
+        if not np.isfinite(a).all() or (a < 0).any():
+            raise create_data_validation_error("cell_areas must be finite and non-negative",
+                                               details=f"{int((~np.isfinite(a)).sum())} non-finite, {int((a < 0).sum())} negative")
+        w = np.ascontiguousarray(a, dtype=np.float32)
+    return shape, tname, tv, w
+
+
+def _free_bytes(eng) -> int:
+    import torch
+
+    free, _ = torch.cuda.mem_get_info(eng.device)
+    return int(free + torch.cuda.memory_reserved(eng.device) - torch.cuda.memory_allocated(eng.device))
+
+
+class _Windows:
+    """The rows ``a .. b`` of a ``[T, C]`` field as a device tensor of one dtype: a view of a resident field (converted per
+    window when its type differs), an upload of a host one -- through the engine's pinned pipe where the window is large."""
+
+    def __init__(self, eng, field, T: int, C: int, np_dtype, is_ids: bool):
+        import torch
+
+        self.eng, self.np_dtype, self.is_ids = eng, np.dtype(np_dtype), is_ids
+        self.tdt = torch.int32 if is_ids else torch.float32
+        t = _tensor_of(field)
+        self.dev = self.host = None
+        if t is not None:
+            if t.device != eng.device:
+                t = t.to(eng.device)
+            self.dev = t.reshape(T, C) if t.is_contiguous() else t.contiguous().reshape(T, C)
+        else:
+            self.host = np.asarray(field.values if hasattr(field, "values") else field).reshape(T, C)
+
+    @property
+    def upload_bytes_per_step(self) -> int:
+        if self.host is not None:
+            return 4 * self.host.shape[1]
+        return 0 if self.dev.dtype == self.tdt else 4 * self.dev.shape[1]
+
+    def _range_check(self, lo: int, hi: int) -> None:
+        if lo < 0 or hi > _I32_MAX:
+            from .track import tracker
+
+            raise tracker._id_range_error(lo, hi)
+
+    def get(self, a: int, b: int):
+        import torch
+
+        if self.dev is not None:
+            x = self.dev[a:b]
+            if x.dtype != self.tdt:
+                if self.is_ids and x.numel():
+                    self._range_check(int(x.min().item()), int(x.max().item()))
+                x = x.to(self.tdt)
+            return x
+        h = self.host[a:b]
+        if self.is_ids and h.dtype != np.int32 and h.size:
+            self._range_check(int(h.min()), int(h.max()))
+        if h.shape[0] * h.shape[1] * 4 >= PINNED_ID_FIELD_BYTES:
+            from .detect import _pipe
+
+            return _pipe(self.eng).upload(h, self.np_dtype)
+        return torch.from_numpy(np.ascontiguousarray(h, dtype=self.np_dtype)).to(self.eng.device)
+
+
+def _plan_windows(eng, T: int, C: int, per_step: int, block_steps):
+    """Steps per window.  ``per_step``: bytes a window takes per timestep beyond what is resident already."""
+    cap = max(1, _BLOCK_CELLS // C)  # the span kernels take blocks below 2^31 - 1 cells
+    if block_steps is None:
+        free = _free_bytes(eng)
+        if T * per_step > free:
+            raise TrackingError(f"event_intensity: needs {T * per_step / 1e9:.3f} GB of device memory, {free / 1e9:.3f} GB are free",
+                                details=f"the ID field and the anomalies of {T} timesteps of {C} cells, 4 bytes per cell each, "
+                                        "as far as they are not on the device already",
+                                suggestions=["Pass block_steps='auto'", "Pass block_steps=<timesteps per window>"])
+        return min(T, cap)
+    if block_steps == "auto":
+        free = _free_bytes(eng)
+        free -= free // 16  # the slots, the small tables and the allocator's rounding
+        return max(1, min(T, cap, free // per_step if per_step else T))
+    return min(int(block_steps), T, cap)
+
+
+def _device_slots(eng, ID_field, dat_anomaly, w, T: int, C: int, block_steps):
+    """The two passes over the field: the events' spans, then the sums.  ``(N, tmin, off, cnt, sums, vmax)`` on the host."""
+    import torch
+
+    ids_w = _Windows(eng, ID_field, T, C, np.int32, True)
+    an_w = _Windows(eng, dat_anomaly, T, C, np.float32, False)
+    B = _plan_windows(eng, T, C, ids_w.upload_bytes_per_step + an_w.upload_bytes_per_step, block_steps)
+    wins = [(a, min(T, a + B)) for a in range(0, T, B)]
+    kept = None
+    tmin, tmax = np.zeros(1, np.int64), np.zeros(1, np.int64)
+    tmin[0], tmax[0] = _I32_MAX, -1
+    for a, b in wins:
+        x = ids_w.get(a, b)
+        sp = eng.id_spans(x)
+        if len(wins) == 1:
+            kept = x
+        if sp is None:
+            continue
+        lo, hi = sp[0].astype(np.int64), sp[1].astype(np.int64)
+        if lo.size > tmin.size:
+            grow = lo.size - tmin.size
+            tmin = np.concatenate([tmin, np.full(grow, _I32_MAX, np.int64)])
+            tmax = np.concatenate([tmax, np.full(grow, -1, np.int64)])
+        seen = hi >= 0
+        n = lo.size
+        tmin[:n] = np.where(seen, np.minimum(tmin[:n], lo + a), tmin[:n])
+        tmax[:n] = np.where(seen, np.maximum(tmax[:n], hi + a), tmax[:n])
+        del x
+    N = int(tmin.size) - 1
+    tmin[0], tmax[0] = _I32_MAX, -1
+    if N <= 0:
+        return 0, tmin, np.zeros(2, np.int64), np.zeros((0, 2), np.int64), np.zeros((0, 2)), np.zeros(0, np.float32)
+    wd = None if w is None else torch.from_numpy(w).to(eng.device)
+    acc, r = None, None
+    for i, (a, b) in enumerate(wins):
+        x = kept if kept is not None else ids_w.get(a, b)
+        r = eng.event_intensity(x, an_w.get(a, b), tmin, tmax, wd, t0=a, acc=acc, finish=i == len(wins) - 1)
+        acc = r["acc"]
+    return N, tmin, r["off"], r["cnt"], r["sums"], r["vmax"]
+
+
+def _time_of_max_values(tv: np.ndarray, t_idx: np.ndarray, has: np.ndarray) -> np.ndarray:
+    """``tv[t_idx]`` with a missing value where ``has`` is False: NaT for dates, NaN otherwise (an integer axis then
+    becomes float64)."""
+    out = tv[np.where(has, t_idx, 0)] if tv.size else tv[:0]
+    if has.all():
+        return out
+    if out.dtype.kind in "mM":
+        out = out.copy()
+        out[~has] = np.array("NaT", dtype=out.dtype)
+        return out
+    out = out.astype(np.float64)
+    out[~has] = np.nan
+    return out
+
+
+def _finish(N: int, T: int, tmin, off, cnt, sums, vmax, tname: str, tv, per_timestep: bool, tcoord: Optional[str] = None):
+    """The Dataset from the compact slots, in float64 and in ascending time per event (the slots of an event are in time
+    order, and ``np.add.at`` adds one element after the other)."""
+    from .xr_compat import DataArray, Dataset
+
+    tv = np.asarray(tv)
+    ids = np.arange(1, N + 1, dtype=np.int32)
+    idc = {"ID": ("ID", ids)}
+    tid = {tcoord or tname: (tname, tv), **idc}
+    e_of = np.repeat(np.arange(N + 1), np.diff(off)[:N + 1])
+    t_of = np.arange(e_of.size) - off[e_of] + tmin[e_of]
+    fin, bad = cnt[:, 0], cnt[:, 1]
+    W, S = sums[:, 0], sums[:, 1]
+    here = (fin + bad) > 0
+    some = fin > 0
+    with np.errstate(invalid="ignore", divide="ignore"):
+        ratio = np.where(some & (W != 0), S / np.where(W != 0, W, 1.0), np.nan)
+    data = {}
+    if per_timestep:
+        def dense(v, dt, fill):
+            d = np.full((T, N), fill, dt)
+            d[t_of[here], e_of[here] - 1] = v[here]
+            return DataArray(d, dims=(tname, "ID"), coords=tid)
+
+        data["intensity_max"] = dense(np.where(some, vmax, np.float32(np.nan)).astype(np.float32), np.float32, np.nan)
+        data["intensity_mean"] = dense(ratio.astype(np.float32), np.float32, np.nan)
+        data["intensity_integral"] = dense(np.where(some, S, np.nan), np.float64, np.nan)
+        data["intensity_cells"] = dense(fin.astype(np.int64), np.int64, 0)
+    duration = np.bincount(e_of[here], minlength=N + 1)[1:N + 1].astype(np.int32)
+    emax = np.full(N + 1, -np.inf, np.float64)
+    np.maximum.at(emax, e_of[some], vmax[some].astype(np.float64))
+    has = np.zeros(N + 1, bool)
+    has[e_of[some]] = True
+    first = np.full(N + 1, np.iinfo(np.int64).max, np.int64)
+    at_max = some & (vmax.astype(np.float64) == emax[e_of])
+    np.minimum.at(first, e_of[at_max], t_of[at_max])
+    sS, sW, cum = np.zeros(N + 1), np.zeros(N + 1), np.zeros(N + 1)
+    np.add.at(sS, e_of[some], S[some])
+    np.add.at(sW, e_of[some], W[some])
+    ok = ~np.isnan(ratio)
+    np.add.at(cum, e_of[ok], ratio[ok])
+    has_w = np.zeros(N + 1, bool)
+    has_w[e_of[ok]] = True
+    with np.errstate(invalid="ignore", divide="ignore"):
+        emean = np.where(has & (sW != 0), sS / np.where(sW != 0, sW, 1.0), np.nan)
+    invalid = np.zeros(N + 1, np.int64)
+    np.add.at(invalid, e_of, bad)
+    data["event_duration"] = DataArray(duration, dims=("ID",), coords=idc)
+    data["event_intensity_max"] = DataArray(np.where(has, emax, np.nan)[1:].astype(np.float32), dims=("ID",), coords=idc)
+    data["event_time_of_max"] = DataArray(_time_of_max_values(tv, first[1:], has[1:]), dims=("ID",), coords=idc)
+    data["event_intensity_mean"] = DataArray(emean[1:].astype(np.float32), dims=("ID",), coords=idc)
+    data["event_intensity_cumulative"] = DataArray(np.where(has_w, cum, np.nan)[1:].astype(np.float32), dims=("ID",), coords=idc)
+    data["event_invalid_cells"] = DataArray(invalid[1:], dims=("ID",), coords=idc)
+    return Dataset(data, coords=tid)
+
+
+def _event_intensity(ID_field, dat_anomaly, cell_areas, per_timestep, block_steps, device, n_events: Optional[int] = None,
+                     time: Optional[tuple] = None):
+    block_steps = _check_block_steps(block_steps)
+    shape, tname, tv, w = _validate(ID_field, dat_anomaly, cell_areas)
+    tcoord = None
+    if time is not None:  # the tracker's own names: (time dimension, time coordinate, values)
+        tname, tcoord, tv = time
+    T = shape[0]
+    C = int(np.prod(shape[1:]))
+    if T == 0 or C == 0:
+        N, tmin, off, cnt, sums, vmax = 0, np.zeros(1, np.int64), np.zeros(2, np.int64), np.zeros((0, 2), np.int64), \
+            np.zeros((0, 2)), np.zeros(0, np.float32)
+    else:
+        if C >= _I32_MAX or T >= _I32_MAX:
+            raise TrackingError(f"event_intensity: a timestep of {C} cells or a record of {T} steps reaches 2^31 - 1",
+                                details="the field may hold any number of cells, a single timestep and the time axis may not")
+        from .detect import get_engine
+
+        N, tmin, off, cnt, sums, vmax = _device_slots(get_engine(device), ID_field, dat_anomaly, w, T, C, block_steps)
+    if n_events is not None:
+        if N > n_events:
+            raise ProcessingError(f"event_intensity: the ID field holds event {N}, the events Dataset ends at {n_events}")
+        if N < n_events:  # trailing events without a cell: no slot
+            tmin = np.concatenate([tmin, np.full(n_events - N, _I32_MAX, np.int64)])
+            off = np.concatenate([off[:N + 2], np.full(n_events - N, off[N + 1], np.int64)])
+            N = n_events
+    return _finish(N, T, tmin, off, cnt, sums, vmax, tname, tv, bool(per_timestep), tcoord)
+
+
+def event_intensity(ID_field, dat_anomaly, cell_areas=None, per_timestep: bool = True, block_steps=None, device: int = 0):
+    """How strong every tracked event was: maximum, mean and cumulative intensity and duration, from one pass over the
+    event field and the anomaly field on the device.
+
+    ``ID_field``: an integer event field of the trackers, ``(time, y, x)`` or ``(time, cells)``; the positive values are
+    the event numbers (a negative value is refused, as by the trackers' other methods).  ``dat_anomaly``: the anomalies,
+    float32 (other float types are cast), same shape and dimension order.  Either may be a host array or DataArray, or
+    device resident (then it is read in place).  ``cell_areas``: None (every cell weighs 1), or non-negative float32 areas
+    per cell -- ``[C]``, ``[ny, nx]`` or ``[ny]`` (broadcast along x), an array or a DataArray.
+
+    ``block_steps``: None takes the field whole (:class:`TrackingError` with both numbers when it does not fit the device
+    memory); a number uploads host inputs one window of that many timesteps at a time, and walks resident inputs in those
+    windows; ``"auto"`` takes the largest window the free memory allows.  The results do not depend on it.
+
+    Returns a Dataset over ``time`` and ``ID = 1 .. N`` (N: the largest event number).  With ``per_timestep``, dense
+    ``(time, ID)`` like the trackers' ``area``, NaN where the event is absent: ``intensity_max`` (float32),
+    ``intensity_mean`` (float32 of S / W; NaN without a finite cell or with W = 0), ``intensity_integral`` (float64 S, the
+    sum of anomaly x area -- anomaly x cells without areas) and ``intensity_cells`` (int64, the finite cells; 0 where
+    absent).  Always, per ``ID``: ``event_duration`` (int32, timesteps with at least one cell, finite or not),
+    ``event_intensity_max`` (float32), ``event_time_of_max`` (the first time value reaching it), ``event_intensity_mean``
+    (float32 of sum S / sum W), ``event_intensity_cumulative`` (float32 of the float64 sum of S_t / W_t in ascending t over
+    the steps with W_t > 0: anomaly x timesteps, degree-days on a daily axis) and ``event_invalid_cells`` (int64, cells
+    whose anomaly is NaN or infinite: they count for the duration and for nothing else).  S and W are float64 sums of exact
+    terms (DESIGN.md section 4 has the bound); counts and maxima are exact."""
+    return _event_intensity(ID_field, dat_anomaly, cell_areas, per_timestep, block_steps, device)

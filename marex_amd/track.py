@@ -898,6 +898,37 @@ class tracker(_MeshStages):  # noqa: N801 -- the reference's public name (marEx.
         at.update(self.data_attrs)
         return self._remap_coordinates(events_ds)
 
+    def event_intensity(self, events_ds, dat_anomaly, per_timestep: bool = True, block_steps: Union[int, str, None] = None):
+        """The events Dataset of :meth:`run` with the intensity of every event added
+        (:func:`marex_amd.intensity.event_intensity` has the variables): ``events_ds["ID_field"]`` joined with
+        ``dat_anomaly`` (float, same dimensions in the same order; host or device resident) on this tracker's device, under
+        its time names and its area weights -- on a grid the float32 cell areas of the merge tracker's area pass (unit
+        weights without ``cell_areas`` / ``grid_resolution``), on a mesh the float32 ``cell_areas``.  Returns a new Dataset;
+        ``events_ds`` is not changed.  The ``ID`` axis and ``presence`` of a merge tracker's Dataset are checked against
+        what the pass found (:class:`ProcessingError`)."""
+        from .intensity import _event_intensity
+        from .xr_compat import Dataset
+
+        w = np.asarray(self.cell_area, np.float32) if self.unstructured_grid else getattr(self, "_cell_weights", None)
+        n = int(np.asarray(events_ds["ID"].values).size) if "ID" in events_ds else None
+        out = _event_intensity(events_ds["ID_field"], dat_anomaly, w, per_timestep, block_steps, self.device, n_events=n,
+                               time=(self.timedim, self.timecoord, self.time_values))
+        if n is not None and not np.array_equal(np.asarray(out["ID"].values), np.asarray(events_ds["ID"].values)):
+            raise ProcessingError("event_intensity: the events of the ID field are not those of the events Dataset",
+                                  details=f"IDs 1..{int(np.asarray(out['ID'].values).size)} found, the Dataset lists {n}")
+        if "presence" in events_ds:
+            dur = np.asarray(events_ds["presence"].values).sum(axis=0)
+            if not np.array_equal(dur, np.asarray(out["event_duration"].values)):
+                k = int(np.argmax(dur != np.asarray(out["event_duration"].values)))
+                raise ProcessingError("event_intensity: an event's duration differs from its presence in the events Dataset",
+                                      details=f"event {k + 1}: {int(np.asarray(out['event_duration'].values)[k])} steps in the ID "
+                                              f"field, present in {int(dur[k])}")
+        data = dict(events_ds.data_vars)
+        data.update(out.data_vars)
+        ds = Dataset(data)
+        ds.attrs.update(events_ds.attrs)
+        return ds
+
     def _latlon_coords(self) -> dict:
         """The input's lat / lon as coordinate entries ``name -> (dims, host values)``."""
         ydim = self.xdim if self.unstructured_grid else self.ydim  # on a mesh lat runs over the cells too
