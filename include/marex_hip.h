@@ -613,6 +613,38 @@ int marex_event_intensity_f32(marex_ctx* ctx, const int32_t* ids, const float* a
                               int n_ev, const int32_t* ev_tmin, const int64_t* ev_off, int64_t n_slots, const float* w,
                               uint64_t* cnt, double* sums, uint32_t* vmax, uint64_t* status);
 
+/* Occurrence statistics of an event mask (extreme_events) or a tracked ID field, from one streaming pass (the reference
+ * leaves them to notebook code: 03_visualise_events over ID_field, 01_preprocess_extremes over extreme_events).
+ *
+ * marex_occurrence_u8 / marex_occurrence_i32: x uint8 / int32 [Tb][C] are the rows t0 .. t0 + Tb - 1 of the field (a grid
+ *   slice flattened, or a mesh).  A cell is present when x > 0 (match == 0) or when x == match (match > 0).  A negative
+ *   int32 cell is never present and adds one to status[0].
+ *   cell_cnt uint32 [G][C]: cell_cnt[grp[t]][c] += 1 per present row -- (ID_field > 0).mean("time") with G = 1,
+ *   .groupby("time.season").mean("time") with season labels, (ID_field == id).sum("time") with match = id; the caller
+ *   divides.  grp int32 [T] is indexed by the global step t = t0 + row and must reach t0 + Tb; NULL with G == 1: every
+ *   step is group 0.  A label outside 0 .. G - 1 addresses nothing: its present cells add to status[1].
+ *   run_state uint32 [3][C], or NULL: per cell the length of the run of present rows that is open after the rows seen so
+ *   far, the number of runs begun, and the longest run.  It is read at the start and written at the end of a call, so a
+ *   field walked in any sequence of time windows gives the arrays of one call.
+ *   sec_cnt uint64 [G2][R] with sgrp int32 [T] and cls int32 [C], or all three NULL: sec_cnt[sgrp[t]][cls[c]] += 1 per
+ *   present cell -- (ID_field > 0).mean("lon").resample(time="ME").mean() with cls = the grid row and sgrp = the month of
+ *   the series, .groupby("time.dayofyear").mean(), groupby_bins(lat, bins).mean("ncells") with cls = the latitude bin of
+ *   a mesh cell.  A cell whose class lies outside 0 .. R - 1 is counted nowhere; a label of sgrp outside 0 .. G2 - 1
+ *   addresses nothing, the present cells with a class add to status[1].  G2 may be as large as T.
+ *   status uint64 [2].  The functions only add: the caller zeroes cell_cnt, run_state, sec_cnt and status before the
+ *   first window.  All results are integers, exact and independent of the order of execution and of the windows.
+ *   The uint8 function reads four cells per lane through 32-bit loads when C % 4 == 0, x is 4-byte and cell_cnt and
+ *   run_state are 16-byte aligned, one cell per lane otherwise: same results.
+ *   -1: null x, cell_cnt or status, empty shape, t0 < 0, match < 0, G <= 0, NULL grp with G != 1, sec_cnt / sgrp / cls
+ *   given in part or with G2 <= 0 or R <= 0; -4: C or t0 + Tb of 2^31 - 1 or more (the field itself may hold any number
+ *   of cells: it is addressed with 64-bit offsets).  Asynchronous on the context's stream. */
+int marex_occurrence_u8(marex_ctx* ctx, const uint8_t* x, int64_t t0, int64_t Tb, int64_t C, int match, const int32_t* grp,
+                        int G, const int32_t* sgrp, int G2, const int32_t* cls, int R, uint32_t* run_state,
+                        uint32_t* cell_cnt, uint64_t* sec_cnt, uint64_t* status);
+int marex_occurrence_i32(marex_ctx* ctx, const int32_t* x, int64_t t0, int64_t Tb, int64_t C, int match, const int32_t* grp,
+                         int G, const int32_t* sgrp, int G2, const int32_t* cls, int R, uint32_t* run_state,
+                         uint32_t* cell_cnt, uint64_t* sec_cnt, uint64_t* status);
+
 /* The partition kernels of the split-and-merge stage on an unstructured mesh (tracker.split_and_merge_objects_parallel,
  * marEx/track.py:3804-4814, 5246-5419).  A slice is int32 [C], values <= 0 are background, C below 2^31 - 1.  u: float64
  * [3][C], the unit vectors of the cells; pv: float64 [3][n], the unit vectors of the parents' centroids.  "Nearest" is the

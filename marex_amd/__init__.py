@@ -22,6 +22,7 @@ from .exceptions import (
 )
 from .dask_adapter import preprocess_data_lazy
 from .intensity import event_intensity
+from .occurrence import event_occurrence
 from .track import tracker
 from .xr_compat import DataArray, Dataset
 
@@ -29,6 +30,6 @@ __all__ = [
     "preprocess_data", "preprocess_data_lazy", "compute_normalised_anomaly", "identify_extremes", "rolling_climatology",
     "smoothed_rolling_climatology", "MarExError", "DataValidationError", "ConfigurationError",
     "ProcessingError", "DependencyError", "create_data_validation_error", "DataArray", "Dataset",
-    "tracker", "TrackingError", "event_intensity",
+    "tracker", "TrackingError", "event_intensity", "event_occurrence",
 ]
 __version__ = "0.1.0"

@@ -1277,6 +1277,100 @@ class HotPath:
                    vmax=bits.astype(np.uint32).view(np.float32))
         return out
 
+    def occurrence(self, x: torch.Tensor, t0: int = 0, grp=None, G: int = 1, sgrp=None, G2: int = 0, cls=None, R: int = 0,
+                   runs: bool = True, event_ids=(), acc: Optional[dict] = None, finish: bool = True) -> Dict[str, object]:
+        """Occurrence statistics of the rows ``t0 .. t0 + Tb - 1`` of a mask or an ID field (``marex_occurrence_u8`` /
+        ``marex_occurrence_i32``): ``x`` uint8, bool (read as uint8) or int32 ``[Tb, C]``; a cell is present where
+        ``x > 0``.  ``grp`` (int ``[T]``, global steps, or None with ``G == 1``) labels the steps for the per-cell counts,
+        ``sgrp`` (int ``[T]``) and ``cls`` (int ``[C]``; outside ``0 .. R - 1``: counted nowhere) the steps and the cells for
+        the section counts, given together or not at all.  ``event_ids``: positive IDs, each counted on its own
+        (``x == id``, one launch per ID on the same window).  The first window allocates zeroed accumulators and uploads the
+        tables; a later window passes the ``"acc"`` entry of the previous result -- the window lengths do not matter, the
+        run statistics are carried.  Returns ``acc`` and -- unless ``finish`` is False, which defers them and the one host
+        read -- ``cell_cnt`` uint32 ``[G, C]``, ``runs`` uint32 ``[3, C]`` (open run, runs begun, longest run; None without
+        ``runs``), ``sec_cnt`` uint64 ``[G2, R]`` (None without sections) and ``dur`` uint32 ``[K, C]``.  A negative ID
+        raises the trackers' "Object IDs must be non-negative" error, a step label outside its range a
+        :class:`ProcessingError`; both were counted, nothing was written out of range."""
+        if x.dim() != 2 or not x.is_contiguous() or x.device != self.device or x.dtype not in (torch.uint8, torch.bool, torch.int32):
+            raise ProcessingError("occurrence: the field must be a contiguous uint8, bool or int32 [T, C] tensor on the engine's "
+                                  "device", details=f"got {x.dtype} {tuple(x.shape)} on {x.device}")
+        if x.dtype == torch.bool:
+            x = x.view(torch.uint8)
+        Tb, Cn = (int(k) for k in x.shape)
+        t0, G, G2, R = int(t0), int(G), int(G2), int(R)
+        ids = [int(k) for k in event_ids]
+        sect = sgrp is not None or cls is not None
+        if t0 < 0 or G <= 0 or (grp is None and G != 1) or any(k <= 0 or k > 2**31 - 1 for k in ids):
+            raise ProcessingError("occurrence: t0 must not be negative, G and the event IDs must be positive, and G > 1 needs labels",
+                                  details=f"t0 = {t0}, G = {G}, labels {'given' if grp is not None else 'missing'}, event_ids {ids[:8]}")
+        if sect and (sgrp is None or cls is None or G2 <= 0 or R <= 0):
+            raise ProcessingError("occurrence: the section counts need step labels, cell classes, G2 > 0 and R > 0 together",
+                                  details=f"G2 = {G2}, R = {R}")
+        if acc is None:
+            tabs = {}
+            for name, v, n in (("grp", grp, None), ("sgrp", sgrp if sect else None, None), ("cls", cls if sect else None, Cn)):
+                if v is None:
+                    tabs[name] = None
+                    continue
+                h = np.asarray(v)
+                if h.ndim != 1 or h.dtype.kind not in "iu" or (n is not None and h.size != n) or \
+                        (h.size and (int(h.min()) < -2**31 or int(h.max()) > 2**31 - 1)):
+                    raise ProcessingError(f"occurrence: {name} must be a vector of int32 values" + (f" of length {n}" if n else ""),
+                                          details=f"got {h.dtype} {h.shape}")
+                tabs[name] = h.astype(np.int32)
+            K = len(ids)
+            need = 4 * G * Cn + (12 * Cn if runs else 0) + (8 * G2 * R if sect else 0) + 4 * K * Cn + 16 + \
+                sum(4 * v.size for v in tabs.values() if v is not None)
+            self._check_fits(need, "occurrence",
+                             f"{G} x {Cn} uint32 counts, {'3 x ' + str(Cn) + ' uint32 run statistics, ' if runs else ''}"
+                             f"{G2 if sect else 0} x {R if sect else 0} uint64 section counts, {K} x {Cn} uint32 counts of "
+                             f"selected events, and the label tables")
+            acc = {"cell_cnt": self._buf(None, "occ_cnt", (G, Cn), torch.int32, self.device).zero_(),
+                   "runs": self._buf(None, "occ_runs", (3, Cn), torch.int32, self.device).zero_() if runs else None,
+                   "sec_cnt": self._buf(None, "occ_sec", (G2, R), torch.int64, self.device).zero_() if sect else None,
+                   "dur": self._buf(None, "occ_dur", (K, Cn), torch.int32, self.device).zero_() if K else None,
+                   "status": self._buf(None, "occ_status", (2,), torch.int64, self.device).zero_(),
+                   "len": {k: (None if v is None else int(v.size)) for k, v in tabs.items()},
+                   "tabs": {k: (None if v is None else self._dev(v)) for k, v in tabs.items()},
+                   "plan": (G, Cn, G2 if sect else 0, R if sect else 0, bool(runs), tuple(ids))}
+        elif acc["plan"] != (G, Cn, G2 if sect else 0, R if sect else 0, bool(runs), tuple(ids)):
+            raise ProcessingError("occurrence: the accumulators were planned for another call",
+                                  details=f"{acc['plan']} there, {(G, Cn, G2 if sect else 0, R if sect else 0, bool(runs), tuple(ids))} here")
+        for name in ("grp", "sgrp"):
+            n = acc["len"][name]
+            if n is not None and n < t0 + Tb:
+                raise ProcessingError(f"occurrence: {name} has {n} labels, the window ends at step {t0 + Tb}")
+        if Tb == 0 or Cn == 0:
+            raise ProcessingError(f"occurrence: an empty window ({Tb} steps of {Cn} cells)")
+        fn = "marex_occurrence_i32" if x.dtype == torch.int32 else "marex_occurrence_u8"
+        tb = acc["tabs"]
+        self.call(fn, x, t0, Tb, Cn, 0, tb["grp"], G, tb["sgrp"], G2 if sect else 0, tb["cls"], R if sect else 0, acc["runs"],
+                  acc["cell_cnt"], acc["sec_cnt"], acc["status"])
+        for k, ev in enumerate(ids):  # the window is resident: one more pass over it per selected event
+            self.call(fn, x, t0, Tb, Cn, ev, None, 1, None, 0, None, 0, None, acc["dur"][k], None, acc["status"])
+        out: Dict[str, object] = {"acc": acc}
+        if not finish:
+            return out
+        neg, lost = (int(v) for v in acc["status"].cpu().numpy())
+        if neg:
+            from .exceptions import create_data_validation_error
+
+            raise create_data_validation_error("Object IDs must be non-negative",
+                                               details=f"{neg // (1 + len(ids))} negative cells; 0 is background",
+                                               data_info={"negative_cells": neg // (1 + len(ids))})
+        if lost:
+            raise ProcessingError(f"occurrence: {lost} present cells lie under a step label outside its range",
+                                  details=f"grp must hold 0 .. {G - 1}, sgrp 0 .. {G2 - 1}; the cells were counted, nothing was "
+                                          "written out of range")
+
+        def host(t, dt):
+            return None if t is None else t.cpu().numpy().view(dt)
+
+        out.update(cell_cnt=host(acc["cell_cnt"], np.uint32), runs=host(acc["runs"], np.uint32),
+                   sec_cnt=host(acc["sec_cnt"], np.uint64),
+                   dur=host(acc["dur"], np.uint32) if ids else np.zeros((0, Cn), np.uint32))
+        return out
+
     def event_rename(self, ids: torch.Tensor, ny: int, nx: int, lut, ev_tmin, ev_tmax,
                      weights: Optional[torch.Tensor] = None) -> Dict[str, np.ndarray]:
         """The device pass of cluster_rename_objects_and_props on a grid (track.py:2897-2976, 3140-3247), in one kernel and

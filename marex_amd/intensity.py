@@ -135,10 +135,13 @@ class _Windows:
         import torch
 
         self.eng, self.np_dtype, self.is_ids = eng, np.dtype(np_dtype), is_ids
-        self.tdt = torch.int32 if is_ids else torch.float32
+        self.item = self.np_dtype.itemsize
+        self.tdt = torch.uint8 if self.np_dtype == np.uint8 else torch.int32 if is_ids else torch.float32
         t = _tensor_of(field)
         self.dev = self.host = None
         if t is not None:
+            if t.dtype == torch.bool and self.tdt == torch.uint8:
+                t = t.view(torch.uint8)  # the bytes of a bool tensor are 0 / 1: read in place
             if t.device != eng.device:
                 t = t.to(eng.device)
             self.dev = t.reshape(T, C) if t.is_contiguous() else t.contiguous().reshape(T, C)
@@ -148,8 +151,8 @@ class _Windows:
     @property
     def upload_bytes_per_step(self) -> int:
         if self.host is not None:
-            return 4 * self.host.shape[1]
-        return 0 if self.dev.dtype == self.tdt else 4 * self.dev.shape[1]
+            return self.item * self.host.shape[1]
+        return 0 if self.dev.dtype == self.tdt else self.item * self.dev.shape[1]
 
     def _range_check(self, lo: int, hi: int) -> None:
         if lo < 0 or hi > _I32_MAX:
@@ -170,22 +173,24 @@ class _Windows:
         h = self.host[a:b]
         if self.is_ids and h.dtype != np.int32 and h.size:
             self._range_check(int(h.min()), int(h.max()))
-        if h.shape[0] * h.shape[1] * 4 >= PINNED_ID_FIELD_BYTES:
+        if h.shape[0] * h.shape[1] * self.item >= PINNED_ID_FIELD_BYTES:
             from .detect import _pipe
 
             return _pipe(self.eng).upload(h, self.np_dtype)
         return torch.from_numpy(np.ascontiguousarray(h, dtype=self.np_dtype)).to(self.eng.device)
 
 
-def _plan_windows(eng, T: int, C: int, per_step: int, block_steps):
-    """Steps per window.  ``per_step``: bytes a window takes per timestep beyond what is resident already."""
+def _plan_windows(eng, T: int, C: int, per_step: int, block_steps, what: str = "event_intensity", details: Optional[str] = None):
+    """Steps per window.  ``per_step``: bytes a window takes per timestep beyond what is resident already.  ``what`` /
+    ``details`` word the error of a field that does not fit whole."""
     cap = max(1, _BLOCK_CELLS // C)  # the span kernels take blocks below 2^31 - 1 cells
     if block_steps is None:
         free = _free_bytes(eng)
         if T * per_step > free:
-            raise TrackingError(f"event_intensity: needs {T * per_step / 1e9:.3f} GB of device memory, {free / 1e9:.3f} GB are free",
-                                details=f"the ID field and the anomalies of {T} timesteps of {C} cells, 4 bytes per cell each, "
-                                        "as far as they are not on the device already",
+            raise TrackingError(f"{what}: needs {T * per_step / 1e9:.3f} GB of device memory, {free / 1e9:.3f} GB are free",
+                                details=details or
+                                f"the ID field and the anomalies of {T} timesteps of {C} cells, 4 bytes per cell each, "
+                                "as far as they are not on the device already",
                                 suggestions=["Pass block_steps='auto'", "Pass block_steps=<timesteps per window>"])
         return min(T, cap)
     if block_steps == "auto":

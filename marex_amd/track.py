@@ -929,6 +929,18 @@ class tracker(_MeshStages):  # noqa: N801 -- the reference's public name (marEx.
         ds.attrs.update(events_ds.attrs)
         return ds
 
+    def event_occurrence(self, events_ds, **kw):
+        """Occurrence statistics of the events of :meth:`run` (:func:`marex_amd.occurrence.event_occurrence` has the
+        arguments and the variables) from ``events_ds["ID_field"]``, on this tracker's device.  On a mesh ``lat`` defaults
+        to the tracker's own latitudes (degrees), so that ``zonal=True`` needs ``lat_bins`` only."""
+        from .occurrence import event_occurrence
+
+        kw.setdefault("device", self.device)
+        if self.unstructured_grid and kw.get("zonal") and kw.get("lat") is None:
+            lat = getattr(self, "lat", None)
+            kw["lat"] = np.asarray(lat if lat is not None else _host(self.lat_init))
+        return event_occurrence(events_ds["ID_field"], **kw)
+
     def _latlon_coords(self) -> dict:
         """The input's lat / lon as coordinate entries ``name -> (dims, host values)``."""
         ydim = self.xdim if self.unstructured_grid else self.ydim  # on a mesh lat runs over the cells too
