@@ -645,6 +645,51 @@ int marex_occurrence_i32(marex_ctx* ctx, const int32_t* x, int64_t t0, int64_t T
                          int G, const int32_t* sgrp, int G2, const int32_t* cls, int R, uint32_t* run_state,
                          uint32_t* cell_cnt, uint64_t* sec_cnt, uint64_t* status);
 
+/* Per-cell intensity of extremes and their severity categories, from one streaming pass over a presence field, the anomaly
+ * field and, optionally, the day-of-year thresholds (the reference leaves them to notebook code:
+ * dat_anomaly.where(extreme_events).groupby("time.year") sum / mean / max / idxmax; the categories of Hobday et al. 2018 as
+ * multiples of the threshold).
+ *
+ * marex_local_intensity_u8 / marex_local_intensity_i32: x uint8 / int32 [Tb][C] and anom float32 [Tb][C] are the rows
+ *   t0 .. t0 + Tb - 1 of the fields.  A cell is present when x > 0 (match == 0) or when x == match (match > 0); a negative
+ *   int32 cell is never present and adds one to status[0].  anom and thr are fetched only under present cells.
+ *   grp int32 [T] (indexed by the global step, must reach t0 + Tb; NULL with G == 1: every step is group 0) selects the
+ *   accumulators of a step, all [G][C]:
+ *     days uint32: present steps with a finite anomaly;  invalid uint32: present steps whose anomaly is NaN or +-inf (they
+ *     add nothing else);  sum float64: the sequential sum of (double)a over the steps counted in days, in ascending time;
+ *     vmax uint32: the largest key(a) (the key of marex_event_intensity_f32; 0: none);  tmax int32: the earliest global
+ *     step that attains it (replaced only by a strictly larger key; meaningless where vmax is 0).
+ *   Summation contract: within a call, when the first row or a change of the group label begins a stretch, the owning lane
+ *   loads sum[g][c], adds one term per step and stores it when the stretch ends; no partial sum is ever added to memory.
+ *   sum[g][c] is therefore one fixed sequence of float64 additions: bit-identical to a row-by-row loop, equal from run
+ *   to run and independent of how the rows are cut into calls, also for groups that are revisited (seasons, months).
+ *   thr float32 [n_doy][C] with doy int32 [T] (the row of thr of every global step) and cat_days uint32 [G][6][C], or all
+ *   three NULL: with h = thr[doy[t]][c] and the float32 products h2 = 2 h, h3 = 3 h, h4 = 4 h (one rounding each) a step
+ *   counted in days adds one to cat_days[g][k][c], k = 5 where h is NaN, +-inf or <= 0, else 0 for a < h (present below
+ *   the threshold: a gap-filled day of a tracked event), 1 for h <= a < h2, 2 for h2 <= a < h3, 3 for h3 <= a < h4, 4 for
+ *   a >= h4.
+ *   sec_cnt uint64 [G2][R][6] with sgrp int32 [T] and cls int32 [C], or all three NULL (they need thr):
+ *   sec_cnt[sgrp[t]][cls[c]][k] += 1 per step classified k.  A cell whose class lies outside 0 .. R - 1 is counted nowhere.
+ *   A step whose grp or doy label lies outside 0 .. G - 1 / 0 .. n_doy - 1 addresses nothing: its present cells add to
+ *   status[1] and to nothing else; under a label of sgrp outside 0 .. G2 - 1 the classified cells with a class add to
+ *   status[1] instead of sec_cnt.  status uint64 [2].
+ *   The functions only continue the accumulators: the caller zeroes all of them before the first window.  Everything but
+ *   sum is an integer or a maximum: exact and independent of any order.  No atomic touches a per-cell output.
+ *   The uint8 function without thr reads four cells per lane through 32-bit loads when C % 4 == 0 and x is 4-byte aligned,
+ *   one cell per lane otherwise and with thr: same results.
+ *   -1: null x, anom, days, invalid, sum, vmax, tmax or status, empty shape, t0 < 0, match < 0, G <= 0, NULL grp with
+ *   G != 1, thr / doy / cat_days given in part or with n_doy <= 0, sec_cnt / sgrp / cls given in part, with G2 <= 0 or
+ *   R <= 0, or without thr; -4: C or t0 + Tb of 2^31 - 1 or more (the fields themselves may hold any number of cells: they
+ *   are addressed with 64-bit offsets).  Asynchronous on the context's stream. */
+int marex_local_intensity_u8(marex_ctx* ctx, const uint8_t* x, const float* anom, int64_t t0, int64_t Tb, int64_t C, int match,
+                             const int32_t* grp, int G, const float* thr, const int32_t* doy, int n_doy, const int32_t* sgrp,
+                             int G2, const int32_t* cls, int R, uint32_t* days, uint32_t* invalid, double* sum, uint32_t* vmax,
+                             int32_t* tmax, uint32_t* cat_days, uint64_t* sec_cnt, uint64_t* status);
+int marex_local_intensity_i32(marex_ctx* ctx, const int32_t* x, const float* anom, int64_t t0, int64_t Tb, int64_t C, int match,
+                              const int32_t* grp, int G, const float* thr, const int32_t* doy, int n_doy, const int32_t* sgrp,
+                              int G2, const int32_t* cls, int R, uint32_t* days, uint32_t* invalid, double* sum, uint32_t* vmax,
+                              int32_t* tmax, uint32_t* cat_days, uint64_t* sec_cnt, uint64_t* status);
+
 /* The partition kernels of the split-and-merge stage on an unstructured mesh (tracker.split_and_merge_objects_parallel,
  * marEx/track.py:3804-4814, 5246-5419).  A slice is int32 [C], values <= 0 are background, C below 2^31 - 1.  u: float64
  * [3][C], the unit vectors of the cells; pv: float64 [3][n], the unit vectors of the parents' centroids.  "Nearest" is the

@@ -23,6 +23,7 @@ from .exceptions import (
 from .dask_adapter import preprocess_data_lazy
 from .intensity import event_intensity
 from .occurrence import event_occurrence
+from .local_intensity import local_intensity
 from .track import tracker
 from .xr_compat import DataArray, Dataset
 
@@ -30,6 +31,6 @@ __all__ = [
     "preprocess_data", "preprocess_data_lazy", "compute_normalised_anomaly", "identify_extremes", "rolling_climatology",
     "smoothed_rolling_climatology", "MarExError", "DataValidationError", "ConfigurationError",
     "ProcessingError", "DependencyError", "create_data_validation_error", "DataArray", "Dataset",
-    "tracker", "TrackingError", "event_intensity", "event_occurrence",
+    "tracker", "TrackingError", "event_intensity", "event_occurrence", "local_intensity",
 ]
 __version__ = "0.1.0"

@@ -1371,6 +1371,117 @@ class HotPath:
                    dur=host(acc["dur"], np.uint32) if ids else np.zeros((0, Cn), np.uint32))
         return out
 
+    def local_intensity(self, x: torch.Tensor, anom: torch.Tensor, t0: int = 0, grp=None, G: int = 1,
+                        thr: Optional[torch.Tensor] = None, doy=None, sgrp=None, G2: int = 0, cls=None, R: int = 0,
+                        acc: Optional[dict] = None, finish: bool = True, match: int = 0) -> Dict[str, object]:
+        """Per-cell intensity of the rows ``t0 .. t0 + Tb - 1`` (``marex_local_intensity_u8`` /
+        ``marex_local_intensity_i32``): ``x`` uint8, bool (read as uint8) or int32 ``[Tb, C]`` (present where ``x > 0``, or
+        where ``x == match``) and ``anom`` float32 ``[Tb, C]``.  ``grp`` (int ``[T]``, global steps, or None with
+        ``G == 1``) labels the steps.  ``thr`` (float32 ``[n_doy, C]`` on the device) with ``doy`` (int ``[T]``, the row of
+        ``thr`` of every global step) adds the category counts; ``sgrp`` (int ``[T]``) and ``cls`` (int ``[C]``; outside
+        ``0 .. R - 1``: counted nowhere) the section counts, which need ``thr``.  The first window allocates zeroed
+        accumulators and uploads the tables; a later window passes the ``"acc"`` entry of the previous result -- the window
+        lengths do not matter, not even to the last bit of ``sum``.  Returns ``acc`` and -- unless ``finish`` is False,
+        which defers them and the one host read -- ``days`` and ``invalid`` uint32 ``[G, C]``, ``sum`` float64 ``[G, C]``,
+        ``vmax`` float32 ``[G, C]`` (NaN: none), ``tmax`` int32 ``[G, C]`` (-1: none), ``cat_days`` uint32 ``[G, 6, C]``
+        and ``sec_cnt`` uint64 ``[G2, R, 6]`` (None without thresholds / sections).  A negative ID raises the trackers'
+        "Object IDs must be non-negative" error, a step label outside its range a :class:`ProcessingError`; both were
+        counted, nothing was written out of range."""
+        if x.dim() != 2 or not x.is_contiguous() or x.device != self.device or x.dtype not in (torch.uint8, torch.bool, torch.int32):
+            raise ProcessingError("local_intensity: the field must be a contiguous uint8, bool or int32 [T, C] tensor on the "
+                                  "engine's device", details=f"got {x.dtype} {tuple(x.shape)} on {x.device}")
+        if x.dtype == torch.bool:
+            x = x.view(torch.uint8)
+        Tb, Cn = (int(k) for k in x.shape)
+        if anom.dtype != torch.float32 or tuple(anom.shape) != (Tb, Cn) or not anom.is_contiguous() or anom.device != self.device:
+            raise ProcessingError(f"local_intensity: the anomalies must be a contiguous float32 [{Tb}, {Cn}] tensor on the "
+                                  f"engine's device", details=f"got {anom.dtype} {tuple(anom.shape)} on {anom.device}")
+        t0, G, G2, R, match = int(t0), int(G), int(G2), int(R), int(match)
+        cats = thr is not None or doy is not None
+        sect = sgrp is not None or cls is not None
+        if t0 < 0 or G <= 0 or (grp is None and G != 1) or match < 0 or match > 2**31 - 1:
+            raise ProcessingError("local_intensity: t0 and match must not be negative, G must be positive, and G > 1 needs labels",
+                                  details=f"t0 = {t0}, G = {G}, labels {'given' if grp is not None else 'missing'}, match = {match}")
+        if cats and (thr is None or doy is None or thr.dim() != 2 or thr.dtype != torch.float32 or int(thr.shape[1]) != Cn or
+                     int(thr.shape[0]) <= 0 or not thr.is_contiguous() or thr.device != self.device):
+            raise ProcessingError(f"local_intensity: the categories need thresholds, a contiguous float32 [n_doy, {Cn}] tensor on "
+                                  "the engine's device, and the row of every step",
+                                  details="one of thr / doy is missing" if thr is None or doy is None else
+                                  f"got {thr.dtype} {tuple(thr.shape)} on {thr.device}")
+        if sect and (sgrp is None or cls is None or G2 <= 0 or R <= 0 or not cats):
+            raise ProcessingError("local_intensity: the section counts need step labels, cell classes, G2 > 0, R > 0 and "
+                                  "thresholds together", details=f"G2 = {G2}, R = {R}, thresholds {'given' if cats else 'missing'}")
+        n_doy = int(thr.shape[0]) if cats else 0
+        plan = (G, Cn, n_doy, G2 if sect else 0, R if sect else 0, match)
+        if acc is None:
+            tabs = {}
+            for name, v, n in (("grp", grp, None), ("doy", doy if cats else None, None), ("sgrp", sgrp if sect else None, None),
+                               ("cls", cls if sect else None, Cn)):
+                if v is None:
+                    tabs[name] = None
+                    continue
+                h = np.asarray(v)
+                if h.ndim != 1 or h.dtype.kind not in "iu" or (n is not None and h.size != n) or \
+                        (h.size and (int(h.min()) < -2**31 or int(h.max()) > 2**31 - 1)):
+                    raise ProcessingError(f"local_intensity: {name} must be a vector of int32 values" + (f" of length {n}" if n else ""),
+                                          details=f"got {h.dtype} {h.shape}")
+                tabs[name] = h.astype(np.int32)
+            need = G * Cn * (24 + (24 if cats else 0)) + (48 * G2 * R if sect else 0) + 16 + \
+                sum(4 * v.size for v in tabs.values() if v is not None)
+            self._check_fits(need, "local intensity",
+                             f"{G} x {Cn} cells of {24 + (24 if cats else 0)} bytes (days, invalid, sum, maximum, its step"
+                             f"{', six category counts' if cats else ''}), {G2 if sect else 0} x {R if sect else 0} x 6 uint64 "
+                             f"section counts, and the label tables")
+            acc = {"days": self._buf(None, "li_days", (G, Cn), torch.int32, self.device).zero_(),
+                   "invalid": self._buf(None, "li_invalid", (G, Cn), torch.int32, self.device).zero_(),
+                   "sum": self._buf(None, "li_sum", (G, Cn), torch.float64, self.device).zero_(),
+                   "vmax": self._buf(None, "li_vmax", (G, Cn), torch.int32, self.device).zero_(),
+                   "tmax": self._buf(None, "li_tmax", (G, Cn), torch.int32, self.device).zero_(),
+                   "cat_days": self._buf(None, "li_cat", (G, 6, Cn), torch.int32, self.device).zero_() if cats else None,
+                   "sec_cnt": self._buf(None, "li_sec", (G2, R, 6), torch.int64, self.device).zero_() if sect else None,
+                   "status": self._buf(None, "li_status", (2,), torch.int64, self.device).zero_(),
+                   "len": {k: (None if v is None else int(v.size)) for k, v in tabs.items()},
+                   "tabs": {k: (None if v is None else self._dev(v)) for k, v in tabs.items()},
+                   "plan": plan}
+        elif acc["plan"] != plan:
+            raise ProcessingError("local_intensity: the accumulators were planned for another call",
+                                  details=f"{acc['plan']} there, {plan} here")
+        for name in ("grp", "doy", "sgrp"):
+            n = acc["len"][name]
+            if n is not None and n < t0 + Tb:
+                raise ProcessingError(f"local_intensity: {name} has {n} labels, the window ends at step {t0 + Tb}")
+        if Tb == 0 or Cn == 0:
+            raise ProcessingError(f"local_intensity: an empty window ({Tb} steps of {Cn} cells)")
+        fn = "marex_local_intensity_i32" if x.dtype == torch.int32 else "marex_local_intensity_u8"
+        tb = acc["tabs"]
+        self.call(fn, x, anom, t0, Tb, Cn, match, tb["grp"], G, thr if cats else None, tb["doy"], n_doy, tb["sgrp"],
+                  G2 if sect else 0, tb["cls"], R if sect else 0, acc["days"], acc["invalid"], acc["sum"], acc["vmax"],
+                  acc["tmax"], acc["cat_days"], acc["sec_cnt"], acc["status"])
+        out: Dict[str, object] = {"acc": acc}
+        if not finish:
+            return out
+        neg, lost = (int(v) for v in acc["status"].cpu().numpy())
+        if neg:
+            from .exceptions import create_data_validation_error
+
+            raise create_data_validation_error("Object IDs must be non-negative", details=f"{neg} negative cells; 0 is background",
+                                               data_info={"negative_cells": neg})
+        if lost:
+            raise ProcessingError(f"local_intensity: {lost} present cells lie under a step label outside its range",
+                                  details=f"grp must hold 0 .. {G - 1}, doy 0 .. {n_doy - 1}, sgrp 0 .. {G2 - 1}; the cells were "
+                                          "counted, nothing was written out of range")
+
+        def host(t, dt):
+            return None if t is None else t.cpu().numpy().view(dt)
+
+        key = host(acc["vmax"], np.uint32)
+        bits = np.where(key & np.uint32(0x80000000), key & np.uint32(0x7FFFFFFF), ~key).astype(np.uint32)
+        out.update(days=host(acc["days"], np.uint32), invalid=host(acc["invalid"], np.uint32), sum=host(acc["sum"], np.float64),
+                   vmax=np.where(key != 0, bits.view(np.float32), np.float32(np.nan)),  # key 0: none
+                   tmax=np.where(key != 0, host(acc["tmax"], np.int32), np.int32(-1)),
+                   cat_days=host(acc["cat_days"], np.uint32), sec_cnt=host(acc["sec_cnt"], np.uint64))
+        return out
+
     def event_rename(self, ids: torch.Tensor, ny: int, nx: int, lut, ev_tmin, ev_tmax,
                      weights: Optional[torch.Tensor] = None) -> Dict[str, np.ndarray]:
         """The device pass of cluster_rename_objects_and_props on a grid (track.py:2897-2976, 3140-3247), in one kernel and

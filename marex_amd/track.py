@@ -941,6 +941,23 @@ class tracker(_MeshStages):  # noqa: N801 -- the reference's public name (marEx.
             kw["lat"] = np.asarray(lat if lat is not None else _host(self.lat_init))
         return event_occurrence(events_ds["ID_field"], **kw)
 
+    def local_intensity(self, events_or_field, extremes_ds, **kw):
+        """Per-cell intensity and severity categories (:func:`marex_amd.local_intensity.local_intensity` has the arguments
+        and the variables) on this tracker's device: ``events_or_field`` is the events Dataset of :meth:`run` (its
+        ``ID_field`` is taken) or a presence field such as ``extremes_ds["extreme_events"]``; ``dat_anomaly`` and, unless
+        ``thresholds`` is passed, ``thresholds`` come from ``extremes_ds``, the Dataset of ``preprocess_data``.  On a mesh
+        ``lat`` defaults to the tracker's own latitudes (degrees), so that ``zonal=True`` needs ``lat_bins`` only."""
+        from .local_intensity import local_intensity
+
+        kw.setdefault("device", self.device)
+        if "thresholds" not in kw and "thresholds" in extremes_ds:
+            kw["thresholds"] = extremes_ds["thresholds"]
+        if self.unstructured_grid and kw.get("zonal") and kw.get("lat") is None:
+            lat = getattr(self, "lat", None)
+            kw["lat"] = np.asarray(lat if lat is not None else _host(self.lat_init))
+        field = events_or_field["ID_field"] if hasattr(events_or_field, "data_vars") else events_or_field
+        return local_intensity(field, extremes_ds["dat_anomaly"], **kw)
+
     def _latlon_coords(self) -> dict:
         """The input's lat / lon as coordinate entries ``name -> (dims, host values)``."""
         ydim = self.xdim if self.unstructured_grid else self.ydim  # on a mesh lat runs over the cells too

@@ -1,0 +1,418 @@
+"""Per-cell intensity on the host: the oracle against hand-computed values, the category rule on the exact multiples of the
+threshold, the validation errors (raised before any device work), the memory arithmetic and the public path -- labels,
+threshold layouts, windows, the carried accumulators, the host finish -- on a NumPy stand-in for the engine call.  No GPU
+needed."""
+import importlib
+import os
+import sys
+
+import numpy as np
+import pytest
+
+import marex_amd
+import marex_amd.intensity as mi
+from marex_amd import calendar
+from marex_amd.engine import HotPath
+from marex_amd.exceptions import ConfigurationError, DataValidationError
+from marex_amd.xr_compat import DataArray
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import local_intensity_oracle as lo  # noqa: E402
+import occurrence_oracle as oo  # noqa: E402
+from local_intensity_host_engine import HostEngine  # noqa: E402
+
+ml = importlib.import_module("marex_amd.local_intensity")  # the package attribute of that name is the function
+NAN, INF = np.nan, np.inf
+F = np.float32
+
+
+def test_oracle_on_a_hand_computed_field():
+    #            cell 0   1     2     3      4
+    x = np.array([[1,     1,    0,    2,     1],
+                  [1,     0,    0,    2,     1],
+                  [1,     1,    0,    3,     1],
+                  [1,     1,    0,    3,     0]], np.int32)
+    a = np.array([[1.0,   2.0,  9.0,  -1.0,  NAN],
+                  [3.0,   9.0,  9.0,  -0.5,  INF],
+                  [3.0,   0.5,  9.0,  -0.0,  -INF],
+                  [2.0,   2.0,  9.0,  0.0,   9.0]], F)
+    s = lo.finish(lo.accumulate(x, a))
+    assert s["days"].tolist() == [[4, 3, 0, 4, 0]] and s["invalid"].tolist() == [[0, 0, 0, 0, 3]]
+    assert s["sum"].tolist() == [[9.0, 4.5, 0.0, -1.5, 0.0]] and s["sum"].dtype == np.float64
+    assert np.array_equal(s["vmax"], [[3.0, 2.0, NAN, 0.0, NAN]], equal_nan=True) and s["vmax"].dtype == np.float32
+    assert s["tmax"].tolist() == [[1, 0, -1, 3, -1]]  # the earliest of two equal maxima; +0 lies above -0
+    assert s["status"] == [0, 0]
+    # groups 0, 1, 0, 1 and event 3 alone
+    g = lo.finish(lo.accumulate(x, a, grp=[0, 1, 0, 1], G=2))
+    assert g["sum"].tolist() == [[4.0, 2.5, 0.0, -1.0, 0.0], [5.0, 2.0, 0.0, -0.5, 0.0]] and g["tmax"].tolist()[1] == [1, 3, -1, 3, -1]
+    e = lo.finish(lo.accumulate(x, a, match=3))
+    assert e["days"].tolist() == [[0, 0, 0, 2, 0]] and e["tmax"].tolist() == [[-1, -1, -1, 3, -1]]
+    # any cut gives the state of the whole, bit for bit
+    for cut in (1, 2, 3):
+        st = lo.accumulate(x[:cut], a[:cut], 0, [0, 1, 0, 1], 2)
+        st = lo.finish(lo.accumulate(x[cut:], a[cut:], cut, [0, 1, 0, 1], 2, state=st))
+        assert all(st[k].tobytes() == g[k].tobytes() for k in ("days", "invalid", "sum", "vmax", "tmax"))
+    # a label outside its range: the present cells of the step are counted and nothing else
+    b = lo.accumulate(x, a, grp=[0, 5, 0, -1], G=2)
+    assert b["status"] == [0, 6] and b["days"].tolist() == [[2, 2, 0, 2, 0], [0] * 5]
+    assert lo.accumulate(np.array([[-1, 2], [0, -3]], np.int32), np.zeros((2, 2), F))["status"] == [2, 0]
+
+
+def test_the_sum_is_sequential():
+    rng = np.random.default_rng(0)
+    a = (np.array([1e8, 1e-3] * 8) * rng.uniform(1, 2, 16)).astype(F)[:, None]  # magnitudes 1e8 and 1e-3 alternating
+    s = lo.accumulate(np.ones((16, 1), np.uint8), a)["sum"][0, 0]
+    seq = 0.0
+    for v in a[:, 0]:
+        seq += float(v)
+    pair = float(a[::2].astype(np.float64).sum()) + float(a[1::2].astype(np.float64).sum())
+    assert s == seq and s != pair  # another association gives other bits
+
+
+def test_category_rule_on_the_exact_multiples():
+    # 0.1f: 3 h rounds (0.3 is no float32 multiple); one ulp to either side of every product
+    for h in (F(0.1), F(0.7), F(1.3), F(1.0)):
+        h2, h3, h4 = F(2) * h, F(3) * h, F(4) * h
+        for edge, k in ((h, 1), (h2, 2), (h3, 3), (h4, 4)):
+            lohi = [np.nextafter(edge, F(-INF)), edge, np.nextafter(edge, F(INF))]
+            assert lo.classes(np.array(lohi, F), np.full(3, h, F)).tolist() == [k - 1, k, k]
+    assert float(F(3) * F(0.1)) != 3 * float(F(0.1))  # the float32 product is rounded
+    assert lo.classes(np.full(6, 1.0, F), np.array([NAN, 0.0, -1.0, INF, -INF, -0.0], F)).tolist() == [5] * 6
+    assert lo.classes(np.array([-5.0, -0.0, 2.5e38], F), np.array([1.0, 1.0, 1e38], F)).tolist() == [0, 0, 2]  # 4 h overflows: never reached
+    x = np.ones((4, 2), np.uint8)
+    a = np.array([[0.5, 1.0], [2.0, 3.0], [4.0, NAN], [9.0, 1.0]], F)
+    thr = np.array([[1.0, 1.0], [1.0, NAN]], F)
+    s = lo.accumulate(x, a, thr=thr, doy=[0, 0, 0, 1], sgrp=[0, 0, 1, 1], G2=2, cls=[0, 0], R=1)
+    assert s["cat_days"][0].tolist() == [[1, 0], [0, 1], [1, 0], [0, 1], [2, 0], [0, 1]]
+    assert s["sec_cnt"].tolist() == [[[1, 1, 1, 1, 0, 0]], [[0, 0, 0, 0, 2, 1]]] and s["invalid"].tolist() == [[0, 1]]
+
+
+def _days(*dates):
+    return np.array(dates, dtype="datetime64[D]").astype("datetime64[ns]")
+
+
+def _no_gpu(monkeypatch):
+    import marex_amd.detect as det
+
+    def no_gpu(*a, **k):
+        raise AssertionError("the validation touched the GPU engine")
+
+    monkeypatch.setattr(det, "get_engine", no_gpu)
+
+
+def _da(a, tv=None, dims=("time", "lat", "lon")):
+    return DataArray(a, dims=dims, coords={dims[0]: (dims[0], np.arange(a.shape[0]) if tv is None else tv)})
+
+
+def test_validation_errors_come_before_the_device(monkeypatch):
+    _no_gpu(monkeypatch)
+    ids = np.zeros((3, 4, 5), np.int32)
+    an = np.zeros((3, 4, 5), F)
+    mesh, man = np.zeros((3, 20), np.int32), np.zeros((3, 20), F)
+    lat = np.linspace(-9, 9, 20)
+    tv = _days("2000-01-01", "2000-01-02", "2000-01-03")
+    thr = np.ones((4, 5), F)
+    V, Cf = DataValidationError, ConfigurationError
+    cases = [
+        (dict(field=ids[0, 0], dat_anomaly=an[0, 0]), V, r"field must be \(time, y, x\) or \(time, cells\)"),
+        (dict(dat_anomaly=an[:2]), V, "field and dat_anomaly differ in shape"),
+        (dict(dat_anomaly=man), V, "field and dat_anomaly differ in shape"),
+        (dict(field=_da(ids), dat_anomaly=_da(an, dims=("time", "y", "x"))), V,
+         "field and dat_anomaly differ in their dimensions"),
+        (dict(field=_da(ids), dat_anomaly=_da(an, np.arange(3) + 1)), V, "field and dat_anomaly differ in their time coordinate"),
+        (dict(field=ids.astype(np.float32)), V, "field must be a mask .* or an integer ID field"),
+        (dict(dat_anomaly=ids), V, "dat_anomaly must be a floating-point field"),
+        (dict(dat_anomaly=an > 0), V, "dat_anomaly must be a floating-point field"),
+        (dict(field=ids > 0, event_id=1), V, "event_id needs an ID field, not a boolean mask"),
+        (dict(event_id=0), V, "event_id must be a positive int32 ID"),
+        (dict(event_id=1.5), V, "event_id must be a positive int32 ID"),
+        (dict(event_id=2**31), V, "event_id must be a positive int32 ID"),
+        (dict(event_id=[1, 2]), V, "event_id must be a positive int32 ID"),
+        (dict(thresholds=np.ones((4, 5), np.int32)), V, "thresholds must be a floating-point field"),
+        (dict(thresholds=np.ones((5, 4), F)), V, "thresholds do not match the spatial shape of the field"),
+        (dict(thresholds=np.ones((4, 5, 365), F)), V, "thresholds do not match the spatial shape of the field"),
+        (dict(thresholds=np.ones((366, 5, 4), F)), V, "thresholds do not match the spatial shape of the field"),
+        (dict(field=_da(ids, tv), thresholds=DataArray(np.ones((5, 4), F), dims=("lon", "lat"))), V,
+         "field and thresholds differ in their dimensions"),
+        (dict(field=_da(ids, tv), thresholds=DataArray(np.ones((4, 366, 5), F), dims=("lat", "dayofyear", "lon"))), V,
+         "thresholds do not match the spatial shape of the field"),
+        (dict(thresholds=np.ones((4, 5, 366), F)), V, "thresholds by dayofyear needs a datetime time coordinate"),
+        (dict(field=_da(ids), thresholds=np.ones((366, 4, 5), F)), V, "thresholds by dayofyear needs a datetime time coordinate"),
+        (dict(zonal=True, zonal_by="step"), V, "zonal category counts need thresholds"),
+        (dict(by="week"), Cf, "by must be one of"),
+        (dict(by="season"), V, "by='season' needs a datetime time coordinate"),
+        (dict(by=np.zeros(4, np.int32)), V, "by labels must be one integer per timestep"),
+        (dict(by=np.array([0, -1, 0])), V, "by labels must not be negative"),
+        (dict(thresholds=thr, zonal=True, zonal_by="week"), Cf, "zonal_by must be one of"),
+        (dict(thresholds=thr, zonal=True), V, "zonal_by='month' needs a datetime time coordinate"),
+        (dict(thresholds=thr, zonal=True, zonal_by=np.array([0, 1, -2])), V, "zonal_by labels must not be negative"),
+        (dict(thresholds=thr, zonal=True, zonal_by="step", lat_bins=[0, 1]), V, "lat and lat_bins belong to a mesh"),
+        (dict(field=mesh, dat_anomaly=man, thresholds=np.ones(20, F), zonal=True, zonal_by="step"), V, "zonal presence on a mesh needs lat"),
+        (dict(field=mesh, dat_anomaly=man, thresholds=np.ones(20, F), zonal=True, zonal_by="step", lat=lat[:-1], lat_bins=[0, 1]), V,
+         "lat does not match the cells"),
+        (dict(field=mesh, dat_anomaly=man, thresholds=np.ones(20, F), zonal=True, zonal_by="step", lat=lat, lat_bins=[0, 2, 1]), V,
+         "lat_bins must be at least two finite, strictly"),
+    ]
+    cases += [(dict(block_steps=b), Cf, "block_steps must be a positive number of timesteps, 'auto' or None")
+              for b in (0, -2, 2.5, True, "all")]
+    for kw, cls, msg in cases:
+        args = dict(field=ids, dat_anomaly=an)
+        args.update(kw)
+        with pytest.raises(cls, match=msg):
+            marex_amd.local_intensity(**args)
+
+
+def test_local_intensity_is_public():
+    assert "local_intensity" in marex_amd.__all__ and marex_amd.local_intensity is ml.local_intensity
+    assert hasattr(marex_amd.tracker, "local_intensity") and hasattr(HotPath, "local_intensity")
+    from marex_amd import _lib
+
+    assert "marex_local_intensity_u8" in _lib.PROTOTYPES and "marex_local_intensity_i32" in _lib.PROTOTYPES
+    assert ml.CATEGORIES == ("below", "moderate", "strong", "severe", "extreme", "undefined")
+
+
+def test_memory_need_arithmetic(monkeypatch):
+    assert ml.accumulator_bytes(1, 10, False) == 240 and ml.accumulator_bytes(40, 1036800, True) == 40 * 1036800 * 48
+    assert ml.accumulator_bytes(3, 7, True) == 3 * 7 * (4 + 4 + 8 + 4 + 4 + 6 * 4)
+    eng = HostEngine()
+    M = 10**6
+    monkeypatch.setattr(mi, "_free_bytes", lambda e: 10_000 * M)
+    d = "the details"
+    # whole: fixed + T x per_step must fit
+    assert ml._window_steps(eng, 10, 100, 500 * M, 5_000 * M, None, d) == 10
+    with pytest.raises(marex_amd.TrackingError, match=r"local_intensity: needs 10\.001 GB of device memory, 10\.000 GB are free"):
+        ml._window_steps(eng, 10, 100, 500 * M, 5_001 * M, None, d)
+    # windows: fixed + one step must fit; "auto" takes what the accumulators leave of 15/16 of the free memory
+    assert ml._window_steps(eng, 10, 100, 500 * M, 9_500 * M, 4, d) == 4
+    with pytest.raises(marex_amd.TrackingError, match=r"local_intensity: needs 10\.001 GB"):
+        ml._window_steps(eng, 10, 100, 500 * M, 9_501 * M, 4, d)
+    assert ml._window_steps(eng, 10, 100, 500 * M, 5_000 * M, "auto", d) == (10_000 - 625 - 5_000) // 500 == 8
+    assert ml._window_steps(eng, 10, 100, 500 * M, 9_400 * M, "auto", d) == 1
+    assert ml._window_steps(eng, 10, 100, 0, 9_400 * M, "auto", d) == 10  # resident inputs: nothing to upload
+
+
+@pytest.fixture
+def host_engine(monkeypatch):
+    import marex_amd.detect as det
+
+    eng = HostEngine()
+    monkeypatch.setattr(det, "get_engine", lambda device=0: eng)
+    monkeypatch.setattr(mi, "_free_bytes", lambda e: 1 << 30)
+    return eng
+
+
+DTYPES = {"days": np.uint32, "invalid_steps": np.uint32, "intensity_cumulative": np.float64, "intensity_mean": np.float64,
+          "intensity_max": np.float32, "steps_by": np.int64, "category_days": np.uint32, "category_peak": np.uint8,
+          "category_cells": np.uint64, "category_share": np.float64, "class_cells": np.int64}
+NOT_SPATIAL = ("steps_by", "category_cells", "category_share", "class_cells")
+
+
+def assert_equals_oracle(ds, exp, space, grouped):
+    """Every variable the oracle has, and no other: dtype, shape (the oracle is flat in space and keeps the group axis)
+    and every value, the float64 sums bit for bit."""
+    assert sorted(ds.data_vars) == sorted(exp)
+    for k, want in exp.items():
+        got = np.asarray(ds[k].values)
+        if k != "time_of_max":
+            assert got.dtype == DTYPES[k], (k, got.dtype)
+        if k not in NOT_SPATIAL:
+            assert got.shape[got.ndim - len(space):] == tuple(space), (k, got.shape)
+            got = got.reshape(got.shape[:got.ndim - len(space)] + (-1,))
+            got = got if grouped else got[None]
+        assert got.shape == want.shape, (k, got.shape, want.shape)
+        assert got.dtype == want.dtype or k == "time_of_max", (k, got.dtype, want.dtype)
+        assert np.array_equal(got, want, equal_nan=got.dtype.kind in "fM"), k
+        if got.dtype.kind == "f":
+            assert got.tobytes() == np.asarray(want).tobytes(), k
+
+
+def same(a, b):
+    assert list(a.data_vars) == list(b.data_vars)
+    for k in a.data_vars:
+        assert np.asarray(a[k].values).tobytes() == np.asarray(b[k].values).tobytes(), k
+        assert tuple(a[k].dims) == tuple(b[k].dims), k
+
+
+def case_fields(T, C, seed=11):
+    """An ID field (events 1..6, a cell present throughout, one never) and anomalies whose sums depend on the order, with
+    NaN and infinities under present cells."""
+    rng = np.random.default_rng(seed)
+    on = rng.random((T, C)) < 0.5
+    on[:, 0] = True
+    on[:, 1] = False
+    ids = np.where(on, rng.integers(1, 7, (T, C)), 0).astype(np.int32)
+    ids[:, 3] = 4
+    an = (rng.normal(0, 2, (T, C)) * np.where(rng.random((T, C)) < 0.2, 1e7, 1.0)).astype(F)
+    an[rng.random((T, C)) < 0.05] = NAN
+    an[1, 0], an[2, 0] = INF, -INF
+    return ids, an
+
+
+TIMES = _days("2001-12-30", "2001-12-31", "2002-01-01", "2002-02-28", "2002-03-01", "2002-06-01", "2002-12-01", "2003-01-01",
+              "2003-07-04", "2004-02-29", "2004-12-31")
+YEAR = np.array([0, 0, 1, 1, 1, 1, 1, 2, 2, 3, 3], np.int32)
+SEASON = np.array([0, 0, 0, 0, 2, 1, 0, 0, 1, 0, 0], np.int32)
+MONTH = np.array([11, 11, 0, 1, 2, 5, 11, 0, 6, 1, 11], np.int32)
+DOY = np.array([364, 365, 1, 59, 60, 152, 335, 1, 185, 60, 366], np.int32)
+ZMONTH = (np.array([2001, 2001, 2002, 2002, 2002, 2002, 2002, 2003, 2003, 2004, 2004]) - 2001) * 12 + MONTH - 11
+
+
+def thresholds_for(rng, C):
+    thr = rng.uniform(0.3, 1.5, (calendar.N_DOY, C)).astype(F)
+    thr[:, 5] = NAN
+    thr[0, 6], thr[59, 7] = 0.0, -1.0
+    return thr
+
+
+@pytest.mark.parametrize("by", [None, "year", "season", "month", "dayofyear", "labels"])
+def test_every_grouping_on_the_host_engine(host_engine, by):
+    T, ny, nx = TIMES.size, 4, 6
+    C = ny * nx
+    ids, an = case_fields(T, C)
+    thr = thresholds_for(np.random.default_rng(1), C)
+    vals, dlab = np.unique(DOY, return_inverse=True)
+    lab, G = {None: (None, 1), "year": (YEAR, 4), "season": (SEASON, 4), "month": (MONTH, 12), "dayofyear": (dlab.astype(np.int32), vals.size),
+              "labels": (np.array([2, 0, 0, 2, 2, 0, 4, 4, 0, 2, 0], np.int32), 5)}[by]
+    cls = np.repeat(np.arange(ny, dtype=np.int32), nx)
+    exp = lo.local_intensity(ids, an, TIMES, lab, G, thr, DOY - 1, ZMONTH, int(ZMONTH.max()) + 1, cls, ny, np.full(ny, nx))
+    coords = {"time": ("time", TIMES), "lat": ("lat", np.linspace(-30, 30, ny)), "lon": ("lon", np.linspace(0, 50, nx))}
+    f = DataArray(ids.reshape(T, ny, nx), dims=("time", "lat", "lon"), coords=coords)
+    a = DataArray(an.reshape(T, ny, nx), dims=("time", "lat", "lon"), coords=coords)
+    h = DataArray(thr.reshape(-1, ny, nx), dims=("dayofyear", "lat", "lon"))
+    kw = dict(thresholds=h, by=lab if by == "labels" else by, zonal=True)
+    whole = marex_amd.local_intensity(f, a, **kw)
+    assert_equals_oracle(whole, exp, (ny, nx), by is not None)
+    assert host_engine.calls == [("local_intensity", "int32", 0, T, 366)]
+    gname = {None: None, "labels": "group"}.get(by, by)
+    lead = () if by is None else (gname,)
+    assert tuple(whole["days"].dims) == lead + ("lat", "lon") and tuple(whole["category_days"].dims) == lead + ("category", "lat", "lon")
+    assert tuple(whole["category_cells"].dims) == ("zonal_month", "lat", "category") and tuple(whole["steps_by"].dims) == lead
+    assert tuple(whole["category_share"].dims) == ("zonal_month", "category") and tuple(whole["class_cells"].dims) == ("lat",)
+    assert np.asarray(whole["category_days"].coords["category"].values).tolist() == list(ml.CATEGORIES)
+    assert np.asarray(whole["time_of_max"].values).dtype.kind == "M" and np.isnat(np.asarray(whole["time_of_max"].values)).any()
+    assert exp["invalid_steps"].sum() > 0 and exp["category_days"][:, 5].sum() > 0 and (exp["category_days"][:, 0].sum() > 0)
+    if by == "year":
+        assert np.asarray(whole["days"].coords["year"].values).tolist() == [2001, 2002, 2003, 2004]
+        assert np.asarray(whole["steps_by"].values).tolist() == [2, 5, 2, 2]
+    for b in (1, 3, "auto"):  # window plans: the same Dataset, the sums to the last bit
+        host_engine.calls.clear()
+        same(whole, marex_amd.local_intensity(f, a, block_steps=b, **kw))
+        if b == 3:
+            assert [c[2:4] for c in host_engine.calls] == [(s, min(3, T - s)) for s in range(0, T, 3)]
+
+
+@pytest.mark.parametrize("zonal_by", ["month", "dayofyear", "year", "step", "labels"])
+def test_every_zonal_grouping_on_a_mesh(host_engine, zonal_by):
+    import torch
+
+    T, C = TIMES.size, 31
+    ids, an = case_fields(T, C, seed=5)
+    mask = ids > 0
+    rng = np.random.default_rng(2)
+    thr = thresholds_for(rng, C)
+    lat = np.round(rng.uniform(-12, 12, C))
+    edges = np.arange(-10.0, 11.0, 4.0)
+    cls = oo.lat_bin(lat, edges)
+    R = edges.size - 1
+    assert (cls < 0).any()
+    vals, dlab = np.unique(DOY, return_inverse=True)
+    zlab, G2, zname = {"month": (ZMONTH, int(ZMONTH.max()) + 1, "zonal_month"), "dayofyear": (dlab, vals.size, "zonal_dayofyear"),
+                       "year": (YEAR, 4, "zonal_year"), "step": (np.arange(T), T, "zonal_step"),
+                       "labels": (np.array([1, 1, 0, 0, 3, 3, 3, 0, 1, 1, 0]), 4, "zonal_group")}[zonal_by]
+    exp = lo.local_intensity(mask, an, TIMES, None, 1, thr, DOY - 1, zlab, G2, cls, R, np.bincount(cls[cls >= 0], minlength=R))
+    zb = zlab if zonal_by == "labels" else zonal_by
+    # (*space, dayofyear), labelled; the mask as bool, uint8, a tensor, a labelled array: one byte per cell
+    h = DataArray(np.ascontiguousarray(thr.T), dims=("ncells", "dayofyear"))
+    a = DataArray(an, dims=("time", "ncells"), coords={"time": ("time", TIMES)})
+    for f in (mask, mask.astype(np.uint8), torch.from_numpy(mask), DataArray(mask, dims=("time", "ncells"))):
+        host_engine.calls.clear()
+        ds = marex_amd.local_intensity(f, a, thresholds=h, zonal=True, zonal_by=zb, lat=lat, lat_bins=edges, block_steps=4)
+        assert_equals_oracle(ds, exp, (C,), False)
+        assert [c[1] for c in host_engine.calls] == ["uint8"] * 3
+    assert tuple(ds["days"].dims) == ("ncells",) and tuple(ds["category_cells"].dims) == (zname, "lat_bins", "category")
+    assert np.array_equal(ds["category_cells"].coords["lat_bins"].values, 0.5 * (edges[:-1] + edges[1:]))
+    assert exp["category_cells"].sum() == exp["category_days"][:, :, cls >= 0].sum() > 0
+    share = exp["category_share"]
+    some = ~np.isnan(share[:, 0])
+    assert some.any() and np.allclose(share[some].sum(axis=1), 1.0)
+
+
+def test_threshold_layouts_plain_and_labelled(host_engine):
+    import torch
+
+    T, ny, nx = TIMES.size, 3, 5
+    C = ny * nx
+    ids, an = case_fields(T, C, seed=3)
+    thr = thresholds_for(np.random.default_rng(4), C)
+    exp = lo.local_intensity(ids, an, TIMES, None, 1, thr, DOY - 1)
+    for shape, sdims in (((ny, nx), ("lat", "lon")), ((C,), ("ncells",))):
+        f = DataArray(ids.reshape((T,) + shape), dims=("time",) + sdims, coords={"time": ("time", TIMES)})
+        a_plain = an.reshape((T,) + shape)
+        first, last = thr.reshape((-1,) + shape), np.ascontiguousarray(np.moveaxis(thr.reshape((-1,) + shape), 0, -1))
+        layouts = [first, last, torch.from_numpy(first), torch.from_numpy(last), first.astype(np.float64),
+                   DataArray(first, dims=("dayofyear",) + sdims), DataArray(last, dims=sdims + ("dayofyear",))]
+        for h in layouts:
+            host_engine.calls.clear()
+            assert_equals_oracle(marex_amd.local_intensity(f, a_plain, thresholds=h, block_steps=5), exp, shape, False)
+            assert host_engine.calls[0][4] == 366
+        # (*space) alone: one row, no calendar needed; a float64 threshold is rounded to float32
+        g64 = np.linspace(0.2, 1.4, C).reshape(shape)
+        g64.flat[2] = NAN
+        expg = lo.local_intensity(ids, an, None, None, 1, g64.astype(F).reshape(1, C), np.zeros(T, np.int32))
+        for h in (g64, g64.astype(F), DataArray(g64, dims=sdims)):
+            host_engine.calls.clear()
+            ds = marex_amd.local_intensity(ids.reshape((T,) + shape), a_plain, thresholds=h)
+            assert_equals_oracle(ds, expg, shape, False)
+            assert host_engine.calls == [("local_intensity", "int32", 0, T, 1)]
+        assert np.asarray(ds["time_of_max"].values).dtype.kind == "i" and (np.asarray(ds["time_of_max"].values) == -1).any()
+    # a 366-cell mesh with unlabelled (366, 366) thresholds is read as (dayofyear, cells): say so with dims where it is not
+    assert ml._threshold_layout(np.ones((366, 366), F), (366,), None) == "doy_last"
+    assert ml._threshold_layout(DataArray(np.ones((366, 366), F), dims=("dayofyear", "ncells")), (366,), ("ncells",)) == "doy_first"
+
+
+def test_event_id_empty_fields_and_refusals(host_engine):
+    T, C = 9, 20
+    ids, an = case_fields(T, C)
+    ds = marex_amd.local_intensity(ids, an, event_id=4)
+    assert_equals_oracle(ds, lo.local_intensity(ids, an, match=4), (C,), False)
+    assert np.asarray(ds["days"].values)[3] == T - np.asarray(ds["invalid_steps"].values)[3]
+    ds = marex_amd.local_intensity(ids.astype(np.int16), an.astype(np.float64), event_id=np.int64(4))  # converted per window
+    assert_equals_oracle(ds, lo.local_intensity(ids, an, match=4), (C,), False)
+    assert host_engine.calls[-1][1] == "int32"
+    with pytest.raises(DataValidationError, match="Object IDs must be non-negative"):
+        marex_amd.local_intensity(np.where(ids == 3, -1, ids).astype(np.int64), an)
+    with pytest.raises(DataValidationError, match="Object IDs must be non-negative"):
+        marex_amd.local_intensity(np.where(ids == 3, -1, ids), an, block_steps=2)
+    with pytest.raises(marex_amd.TrackingError, match=r"local_intensity: needs .* GB of device memory, .* GB are free"):
+        marex_amd.local_intensity(np.zeros((8, 1 << 27), bool), np.zeros((8, 1 << 27), F))
+    # the accumulators alone: 4000 groups x 2^14 cells x 48 bytes do not fit 1 GiB, whatever the windows
+    big = np.zeros((4000, 1 << 14), bool)
+    with pytest.raises(marex_amd.TrackingError, match=r"local_intensity: needs 3\.\d+ GB of device memory"):
+        marex_amd.local_intensity(big, np.zeros(big.shape, F), thresholds=np.ones(1 << 14, F), by=np.arange(4000), block_steps=1)
+    host_engine.calls.clear()
+    for shape in ((0, 5), (4, 0), (0, 2, 3)):
+        e = marex_amd.local_intensity(np.zeros(shape, np.int32), np.zeros(shape, F), thresholds=np.ones(shape[1:], F))
+        assert np.asarray(e["days"].values).shape == shape[1:] and not np.asarray(e["days"].values).any()
+        assert np.isnan(np.asarray(e["intensity_mean"].values)).all() and np.asarray(e["category_days"].values).shape == (6,) + shape[1:]
+        assert (np.asarray(e["time_of_max"].values) == -1).all() and int(e["steps_by"].values) == shape[0]
+    assert host_engine.calls == []
+
+
+def test_tracker_method_takes_the_fields_from_the_datasets(monkeypatch):
+    seen = {}
+    monkeypatch.setattr(ml, "local_intensity", lambda field, anom, **kw: seen.update(field=field, anom=anom, **kw) or "ds")
+
+    class T:  # the attributes the method reads
+        device, unstructured_grid, lat = 0, True, np.arange(5.0)
+
+    ev = marex_amd.Dataset({"ID_field": DataArray(np.zeros((2, 5), np.int32), dims=("time", "ncells"))})
+    ex = marex_amd.Dataset({"dat_anomaly": DataArray(np.zeros((2, 5), F), dims=("time", "ncells")),
+                            "extreme_events": DataArray(np.zeros((2, 5), bool), dims=("time", "ncells")),
+                            "thresholds": DataArray(np.ones(5, F), dims=("ncells",))})
+    assert marex_amd.tracker.local_intensity(T(), ev, ex, zonal=True, lat_bins=[0, 2, 4]) == "ds"
+    assert seen["field"] is ev["ID_field"] and seen["anom"] is ex["dat_anomaly"] and seen["thresholds"] is ex["thresholds"]
+    assert seen["lat"].tolist() == [0, 1, 2, 3, 4] and seen["device"] == 0
+    seen.clear()
+    T.unstructured_grid = False
+    marex_amd.tracker.local_intensity(T(), ex["extreme_events"], ex, thresholds=None, by="year", block_steps=3)
+    assert seen["field"] is ex["extreme_events"] and seen["thresholds"] is None and "lat" not in seen and seen["block_steps"] == 3
