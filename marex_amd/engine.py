@@ -1051,29 +1051,84 @@ class HotPath:
 
     def relabel(self, ids: torch.Tensor, vals: np.ndarray, keys: Optional[np.ndarray] = None) -> None:
         """In place: ``ids`` (contiguous int32 on the device) -> ``vals[j]`` where ``keys[j]`` equals the ID (``keys``
-        ascending; IDs without an entry stay), or with ``keys=None`` -> ``vals[id]`` for ``0 < id < len(vals)``."""
+        strictly ascending, one value per key; IDs without an entry stay), or with ``keys=None`` -> ``vals[id]`` for
+        ``0 < id < len(vals)``."""
         if ids.dtype != torch.int32 or not ids.is_contiguous() or ids.device != self.device:
             raise ProcessingError("relabel: ids must be a contiguous int32 tensor on the engine's device")
-        if ids.numel() == 0 or len(vals) == 0:
+        vals = self._i32_table("relabel", "vals", vals)
+        if keys is not None:
+            keys = self._i32_table("relabel", "keys", keys)
+            if keys.size != vals.size or np.any(np.diff(keys.astype(np.int64)) <= 0):
+                raise ProcessingError("relabel: keys must ascend strictly and have one value each",
+                                      details=f"{keys.size} keys, {vals.size} values")
+        if ids.numel() == 0 or vals.size == 0:
             return
         self.call("marex_relabel_i32", ids, ids.numel(), self._i32(keys) if keys is not None else None, self._i32(vals),
-                  len(vals))
+                  int(vals.size))
+
+    @staticmethod
+    def _i32_table(what: str, name: str, a) -> np.ndarray:
+        """A one-dimensional host table of integers that all fit int32 (a silent wrap would name another ID)."""
+        a = np.asarray(a)
+        if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
+            raise ProcessingError(f"{what}: {name} must be a one-dimensional table of integers",
+                                  details=f"got {a.dtype} {a.shape}")
+        a = a.astype(np.int64)
+        if a.size and (a.min() < -2 ** 31 or a.max() > 2 ** 31 - 1):
+            raise ProcessingError(f"{what}: {name} does not fit int32", details=f"range {a.min()} .. {a.max()}")
+        return a.astype(np.int32)
+
+    def _partition_check(self, what: str, slices, ny: int, nx: int, child_keys, off, lab, others) -> tuple:
+        """The tables of a grid partition, refused before any library call when a kernel would read past a slice or a
+        table, or search unsorted keys: ``slices`` are contiguous int32 ``ny * nx`` tensors on the device, ``child_keys``
+        ascend strictly, ``off`` runs from 0 to ``len(lab)`` with at least one entry per child, and every table of
+        ``others`` (name -> values) has one value per entry.  Returns ``(child_keys, off, lab)`` as int32 arrays."""
+        ny, nx = int(ny), int(nx)
+        for s in slices:
+            if (not isinstance(s, torch.Tensor) or s.dtype != torch.int32 or not s.is_contiguous() or s.device != self.device
+                    or ny <= 0 or nx <= 0 or s.numel() != ny * nx):
+                got = f"{s.dtype} {tuple(s.shape)} on {s.device}" if isinstance(s, torch.Tensor) else type(s).__name__
+                raise ProcessingError(f"{what}: a slice must be a contiguous int32 tensor of ny * nx = {ny} * {nx} cells on the "
+                                      f"engine's device", details=f"got {got}")
+        keys, off, lab = (self._i32_table(what, n, a) for n, a in (("child_keys", child_keys), ("off", off), ("lab", lab)))
+        n_ent = lab.size
+        if (keys.size == 0 or off.size != keys.size + 1 or np.any(np.diff(keys.astype(np.int64)) <= 0) or off[0] != 0
+                or off[-1] != n_ent or np.any(np.diff(off) <= 0)):
+            raise ProcessingError(f"{what}: child_keys must ascend strictly, off must run from 0 to len(lab) with at least one "
+                                  f"entry per child", details=f"{keys.size} children, off {off.tolist()}, {n_ent} labels")
+        for name, a in others.items():
+            if np.ndim(a) != 1 or len(a) != n_ent:
+                raise ProcessingError(f"{what}: {name} must have one value per entry of lab",
+                                      details=f"{np.shape(a)} for {n_ent} labels")
+        return keys, off, lab
 
     def partition_centroid(self, cur: torch.Tensor, ny: int, nx: int, child_keys, off, pcy, pcx, lab, wrap: bool) -> None:
-        """In place on the slice ``cur`` (int32 ``ny * nx``): every cell of child ``child_keys[k]`` takes ``lab[j]`` of the
-        nearest parent centroid ``(pcy[j], pcx[j])``, ``off[k] <= j < off[k + 1]`` (first minimum)."""
-        self.call("marex_partition_centroid_i32", cur, int(ny), int(nx), self._i32(child_keys), len(child_keys), self._i32(off),
-                  self._dev(np.asarray(pcy, np.float64)), self._dev(np.asarray(pcx, np.float64)), self._i32(lab),
-                  int(bool(wrap)))
+        """In place on the slice ``cur`` (int32 ``ny * nx``): every cell of child ``child_keys[k]`` (strictly ascending)
+        takes ``lab[j]`` of the nearest parent centroid ``(pcy[j], pcx[j])``, ``off[k] <= j < off[k + 1]`` (first
+        minimum); ``off`` runs from 0 to ``len(lab)``."""
+        pcy, pcx = np.array(pcy, np.float64), np.array(pcx, np.float64)
+        keys, off, lab = self._partition_check("partition_centroid", (cur,), ny, nx, child_keys, off, lab,
+                                               {"pcy": pcy, "pcx": pcx})
+        self.call("marex_partition_centroid_i32", cur, int(ny), int(nx), self._i32(keys), int(keys.size), self._i32(off),
+                  self._dev(pcy), self._dev(pcx), self._i32(lab), int(bool(wrap)))
 
     def partition_nn(self, cur: torch.Tensor, prev: torch.Tensor, ny: int, nx: int, child_keys, off, parents, pcy, pcx, lab,
                      maxd, wrap: bool) -> None:
         """In place on the slice ``cur``: every cell of child ``child_keys[k]`` takes ``lab[j]`` of the parent
         ``parents[j]`` (``off[k] <= j < off[k + 1]``) with the nearest cell in ``prev`` among its cells in the 3 x 3
-        buckets of size ``max(2, maxd[j] // 4)`` around the child cell's bucket and within ``maxd[j]``, else of the
-        nearest parent centroid (partition_nn_grid, track.py:4972-5113)."""
-        parents = np.asarray(parents, np.int64)
-        maxd = np.asarray(maxd, np.int64)
+        buckets of size ``max(2, maxd[j] // 4)`` around the child cell's bucket and within ``maxd[j]``
+        (``1 <= maxd[j] <= INT32_MAX``), else of the nearest parent centroid (partition_nn_grid, track.py:4972-5113).
+        The tables are checked as in :meth:`partition_centroid`."""
+        pcy, pcx = np.array(pcy, np.float64), np.array(pcx, np.float64)
+        parents, maxd = np.asarray(parents), np.asarray(maxd)
+        child_keys, off, lab = self._partition_check("partition_nn", (cur, prev), ny, nx, child_keys, off, lab,
+                                                     {"pcy": pcy, "pcx": pcx, "parents": parents, "maxd": maxd})
+        parents = self._i32_table("partition_nn", "parents", parents)
+        if maxd.dtype.kind not in "iu" or maxd.astype(np.int64).min() < 1 or maxd.astype(np.int64).max() > 2 ** 31 - 1:
+            raise ProcessingError("partition_nn: maxd must be integers from 1 to INT32_MAX",
+                                  details=f"got {maxd.dtype} {maxd.tolist()[:8]}")
+        parents, maxd = parents.astype(np.int64), maxd.astype(np.int64)
+        ny, nx = int(ny), int(nx)
         gs = np.maximum(2, maxd // 4)
         ngy, ngx = (ny + gs - 1) // gs, (nx + gs - 1) // gs
         nb = ngy * ngx
@@ -1085,7 +1140,7 @@ class HotPath:
         t = {k: self._i32(v) for k, v in (("par", par_keys), ("poff", poff), ("pent", order), ("gs", gs), ("ngy", ngy),
                                            ("ngx", ngx), ("maxd", maxd), ("ck", child_keys), ("off", off), ("lab", lab))}
         base_d = self._dev(base)
-        pcy_d, pcx_d = self._dev(np.asarray(pcy, np.float64)), self._dev(np.asarray(pcx, np.float64))
+        pcy_d, pcx_d = self._dev(pcy), self._dev(pcx)
         cnt = torch.empty(n_buckets, dtype=torch.int64, device=self.device)
         bstart = torch.empty(n_buckets + 1, dtype=torch.int64, device=self.device)
         self.call("marex_nn_bucket_count_i32", prev, int(ny), int(nx), t["par"], len(par_keys), t["poff"], t["pent"], t["gs"],
@@ -1095,7 +1150,7 @@ class HotPath:
             raise ProcessingError("partition_nn: the parents have no cells in the previous slice")
         cells = torch.empty(n_cells, dtype=torch.int32, device=self.device)
         self.call("marex_partition_nn_i32", cur, prev, int(ny), int(nx), t["par"], len(par_keys), t["poff"], t["pent"], t["ck"],
-                  len(child_keys), t["off"], pcy_d, pcx_d, t["lab"], t["gs"], t["ngy"], t["ngx"], t["maxd"], base_d, n_buckets,
+                  int(child_keys.size), t["off"], pcy_d, pcx_d, t["lab"], t["gs"], t["ngy"], t["ngx"], t["maxd"], base_d, n_buckets,
                   bstart, cnt, cells, n_cells, int(bool(wrap)))
 
     # ------------------------------------------------------------------ the partitions of the merge stage on a mesh (track.py:5246-5419)
