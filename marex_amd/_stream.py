@@ -1,0 +1,236 @@
+"""What the streaming statistics (``intensity``, ``occurrence``, ``local_intensity``) share in front of the engine: what a
+``[time, space]`` field says without a device, the windows it is walked in, and the way back to its spatial dimensions."""
+from __future__ import annotations
+
+from typing import Optional
+
+import numpy as np
+
+from .exceptions import ConfigurationError, TrackingError, create_data_validation_error
+from .track import _BLOCK_CELLS, PINNED_ID_FIELD_BYTES, _host, _tensor_of
+from .xr_compat import DataArray
+
+_I32_MAX = 2**31 - 1
+
+
+def _check_block_steps(block_steps):
+    b = block_steps
+    if b is not None and b != "auto" and (isinstance(b, (bool, str)) or not isinstance(b, (int, np.integer)) or b <= 0):
+        raise ConfigurationError("block_steps must be a positive number of timesteps, 'auto' or None", details=f"block_steps={b!r}")
+    return b if b is None or isinstance(b, str) else int(b)
+
+
+def _dtype_name(x) -> str:
+    t = _tensor_of(x)
+    if t is not None:
+        return str(t.dtype).replace("torch.", "")
+    return str(x.dtype if hasattr(x, "dtype") else np.asarray(x).dtype)
+
+
+def _kind(x) -> str:
+    """'i' for an integer field, 'f' for a float one, '?' for anything else (bool, complex, objects)."""
+    t = _tensor_of(x)
+    if t is not None:
+        if t.dtype.is_floating_point:
+            return "f"
+        return "?" if t.dtype.is_complex or "bool" in str(t.dtype) else "i"
+    k = np.dtype(_dtype_name(x)).kind
+    return "i" if k in "iu" else "f" if k == "f" else "?"
+
+
+def _field_kind(field) -> str:
+    """'m' for a mask (bool or uint8), 'i' for another integer field."""
+    t = _tensor_of(field)
+    name = _dtype_name(field) if t is None else str(t.dtype).replace("torch.", "")
+    if name in ("bool", "uint8"):
+        return "m"
+    try:
+        kind = np.dtype(name).kind
+    except TypeError:
+        kind = "?"
+    if kind not in "iu":
+        raise create_data_validation_error("field must be a mask (bool or uint8) or an integer ID field",
+                                           details=f"Found dtype {name}", data_info={"actual_dtype": name})
+    return "i"
+
+
+def _time_of(field, T: int):
+    """``(name, values or None)`` of the leading (time) dimension of a field."""
+    dims = tuple(getattr(field, "dims", ()) or ())
+    name = dims[0] if dims else "time"
+    coords = getattr(field, "coords", None)
+    if coords is None or not dims:
+        return name, None
+    c = coords[name] if name in coords else next((coords[k] for k in coords if tuple(getattr(coords[k], "dims", ())) == (name,)), None)
+    if c is None:
+        return name, None
+    v = np.asarray(_host(c))
+    return name, (v if v.shape == (T,) else None)
+
+
+def plan_field(field, what: str, partner=None) -> dict:
+    """What a presence field says without a device: ``shape``, ``T``, ``C``, ``kind`` ('m' mask, 'i' IDs), ``bool``, the
+    time axis (``tname``, ``tv``), the spatial dimensions ``sdims`` and their coordinates ``scoords``.  ``partner``: the
+    anomaly field, which must agree in shape, dimensions and time; its names and coordinates fill in what the field lacks."""
+    shape = tuple(int(k) for k in field.shape)
+    if len(shape) not in (2, 3):
+        raise create_data_validation_error("field must be (time, y, x) or (time, cells)", details=f"got shape {shape}")
+    dims = tuple(getattr(field, "dims", ()) or ())
+    d_a = ()
+    if partner is not None:
+        ashape = tuple(int(k) for k in partner.shape)
+        if ashape != shape:
+            raise create_data_validation_error("field and dat_anomaly differ in shape", details=f"field {shape}, dat_anomaly {ashape}")
+        d_a = tuple(getattr(partner, "dims", ()) or ())
+        if dims and d_a and dims != d_a:
+            raise create_data_validation_error("field and dat_anomaly differ in their dimensions",
+                                               details=f"field {dims}, dat_anomaly {d_a}; the order must agree too")
+    kind = _field_kind(field)
+    if partner is not None and _kind(partner) != "f":
+        raise create_data_validation_error("dat_anomaly must be a floating-point field",
+                                           details=f"Found dtype {_dtype_name(partner)}",
+                                           data_info={"actual_dtype": _dtype_name(partner)})
+    T, C = shape[0], int(np.prod(shape[1:]))
+    if C >= _I32_MAX or T >= _I32_MAX:
+        raise TrackingError(f"{what}: a timestep of {C} cells or a record of {T} steps reaches 2^31 - 1",
+                            details="the field may hold any number of cells, a single timestep and the time axis may not")
+    tname, tv = _time_of(field, T)
+    if partner is not None:
+        _, tv_a = _time_of(partner, T)
+        if tv is not None and tv_a is not None and not np.array_equal(tv, tv_a):
+            raise create_data_validation_error("field and dat_anomaly differ in their time coordinate",
+                                               details=f"the first difference is at step {int(np.argmax(tv != tv_a))}")
+        tv = tv if tv is not None else tv_a
+    labelled = dims or d_a
+    sdims = labelled[1:] if labelled else (("y", "x") if len(shape) == 3 else ("cells",))
+    coords = {}
+    for src in (partner, field):  # the field's coordinates win
+        for k, c in (getattr(src, "coords", None) or {}).items():
+            cd = tuple(getattr(c, "dims", ()) or ())
+            if cd and all(d in sdims for d in cd):
+                coords[k] = (cd, np.asarray(_host(c)))
+    return dict(kind=kind, bool=_dtype_name(field) == "bool", shape=shape, T=T, C=C, tname=tname, tv=tv, labelled=bool(labelled),
+                sdims=sdims, scoords=coords)
+
+
+def plan_sections(p: dict, zonal_by, lat, lat_bins):
+    """``p["sec"]`` of a zonal call: ``(step labels of zonal_labels, cls int32 [C], R, class dimension, class coordinate
+    or None, cells per class)`` -- the y rows of a grid, the latitude bins of a mesh."""
+    from .occurrence import lat_classes, zonal_labels  # occurrence imports this module
+
+    shape, sdims = p["shape"], p["sdims"]
+    lab = zonal_labels(zonal_by, p["tv"], p["T"])
+    if len(shape) == 3:
+        if lat is not None or lat_bins is not None:
+            raise create_data_validation_error("lat and lat_bins belong to a mesh: on a grid the classes are the y rows")
+        ny, nx = shape[1], shape[2]
+        cls = np.repeat(np.arange(ny, dtype=np.int32), nx)
+        yc = p["scoords"].get(sdims[0])
+        return (lab, cls, ny, sdims[0], None if yc is None else yc[1], np.full(ny, nx, np.int64))
+    cls, R, e = lat_classes(lat, lat_bins, p["C"])
+    return (lab, cls, R, "lat_bins", 0.5 * (e[:-1] + e[1:]), np.bincount(cls[cls >= 0], minlength=R).astype(np.int64))
+
+
+def space(p: dict, v, lead=(), extra=None):
+    """``v [*lead, C]`` over ``lead`` + the spatial dimensions of the field, with their coordinates and ``extra``."""
+    c = dict(p["scoords"])
+    c.update(extra or {})
+    return DataArray(v.reshape(v.shape[:len(lead)] + p["shape"][1:]), dims=tuple(lead) + tuple(p["sdims"]), coords=c)
+
+
+def section_coords(sec, extra=None):
+    """``(zonal dimension, class dimension, coordinates of both and of extra, class_cells DataArray)`` of ``p["sec"]``."""
+    (_, _, zname, zvals), _, _, cname, cvals, ccells = sec
+    zc = {zname: (zname, zvals), **(extra or {})}
+    if cvals is not None:
+        zc[cname] = (cname, cvals)
+    return zname, cname, zc, DataArray(ccells, dims=(cname,), coords={cname: zc[cname]} if cvals is not None else None)
+
+
+def _free_bytes(eng) -> int:
+    import torch
+
+    free, _ = torch.cuda.mem_get_info(eng.device)
+    return int(free + torch.cuda.memory_reserved(eng.device) - torch.cuda.memory_allocated(eng.device))
+
+
+class _Windows:
+    """The rows ``a .. b`` of a ``[T, C]`` field as a device tensor of one dtype: a view of a resident field (converted per
+    window when its type differs), an upload of a host one -- through the engine's pinned pipe where the window is large."""
+
+    def __init__(self, eng, field, T: int, C: int, np_dtype, is_ids: bool):
+        import torch
+
+        self.eng, self.np_dtype, self.is_ids = eng, np.dtype(np_dtype), is_ids
+        self.item = self.np_dtype.itemsize
+        self.tdt = torch.uint8 if self.np_dtype == np.uint8 else torch.int32 if is_ids else torch.float32
+        t = _tensor_of(field)
+        self.dev = self.host = None
+        if t is not None:
+            if t.dtype == torch.bool and self.tdt == torch.uint8:
+                t = t.view(torch.uint8)  # the bytes of a bool tensor are 0 / 1: read in place
+            if t.device != eng.device:
+                t = t.to(eng.device)
+            self.dev = t.reshape(T, C) if t.is_contiguous() else t.contiguous().reshape(T, C)
+        else:
+            self.host = np.asarray(field.values if hasattr(field, "values") else field).reshape(T, C)
+
+    @property
+    def upload_bytes_per_step(self) -> int:
+        if self.host is not None:
+            return self.item * self.host.shape[1]
+        return 0 if self.dev.dtype == self.tdt else self.item * self.dev.shape[1]
+
+    def _range_check(self, lo: int, hi: int) -> None:
+        if lo < 0 or hi > _I32_MAX:
+            from .track import tracker
+
+            raise tracker._id_range_error(lo, hi)
+
+    def get(self, a: int, b: int):
+        import torch
+
+        if self.dev is not None:
+            x = self.dev[a:b]
+            if x.dtype != self.tdt:
+                if self.is_ids and x.numel():
+                    self._range_check(int(x.min().item()), int(x.max().item()))
+                x = x.to(self.tdt)
+            return x
+        h = self.host[a:b]
+        if self.is_ids and h.dtype != np.int32 and h.size:
+            self._range_check(int(h.min()), int(h.max()))
+        if h.shape[0] * h.shape[1] * self.item >= PINNED_ID_FIELD_BYTES:
+            from .detect import _pipe
+
+            return _pipe(self.eng).upload(h, self.np_dtype)
+        return torch.from_numpy(np.ascontiguousarray(h, dtype=self.np_dtype)).to(self.eng.device)
+
+
+def _plan_windows(eng, T: int, C: int, per_step: int, block_steps, what: str = "event_intensity", details: Optional[str] = None):
+    """Steps per window.  ``per_step``: bytes a window takes per timestep beyond what is resident already.  ``what`` /
+    ``details`` word the error of a field that does not fit whole."""
+    cap = max(1, _BLOCK_CELLS // C)  # the span kernels take blocks below 2^31 - 1 cells
+    if block_steps is None:
+        free = _free_bytes(eng)
+        if T * per_step > free:
+            raise TrackingError(f"{what}: needs {T * per_step / 1e9:.3f} GB of device memory, {free / 1e9:.3f} GB are free",
+                                details=details or
+                                f"the ID field and the anomalies of {T} timesteps of {C} cells, 4 bytes per cell each, "
+                                "as far as they are not on the device already",
+                                suggestions=["Pass block_steps='auto'", "Pass block_steps=<timesteps per window>"])
+        return min(T, cap)
+    if block_steps == "auto":
+        free = _free_bytes(eng)
+        free -= free // 16  # the slots, the small tables and the allocator's rounding
+        return max(1, min(T, cap, free // per_step if per_step else T))
+    return min(int(block_steps), T, cap)
+
+
+def walk_windows(T: int, B: int, step):
+    """The last result of ``step(a, b, acc, finish)`` over the windows of ``B`` steps, each given the ``"acc"`` before it."""
+    acc = r = None
+    for a in range(0, T, B):
+        r = step(a, min(T, a + B), acc, a + B >= T)
+        acc = r["acc"]
+    return r

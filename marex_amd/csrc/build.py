@@ -13,7 +13,8 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 UNITS = ["marex_context", "marex_synth", "marex_shifting", "marex_thresholds", "marex_mask", "marex_anomalies",
          "marex_quantiles", "marex_morphology", "marex_objects", "marex_mesh_objects", "marex_merge", "marex_mesh_merge", "marex_intensity", "marex_occurrence", "marex_local_intensity", "marex_blosc", "marex_tails", "marex_zstd"]
 SRC = [os.path.join(HERE, u + ".hip") for u in UNITS]
-HEADERS = [os.path.join(HERE, "marex_common.hip.h"), os.path.join(HERE, "marex_tails.hip.h"), os.path.join(ROOT, "include", "marex_hip.h")]
+HEADERS = [os.path.join(HERE, "marex_common.hip.h"), os.path.join(HERE, "marex_tails.hip.h"),
+           os.path.join(HERE, "marex_cellwalk.hip.h"), os.path.join(ROOT, "include", "marex_hip.h")]
 OUT = os.path.join(HERE, "libmarex_hip.so")
 FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",

@@ -13,9 +13,7 @@
 // equal from run to run, independent of the windows, also for groups that are revisited.  No atomic touches a per-cell
 // output.  The section counts use occurrence's scheme: the wave's class partition is taken once, per row one ballot per
 // category, popcount(ballot & lane mask), one integer atomicAdd per (class, category) when the section label changes.
-#include "marex_common.hip.h"
-
-typedef unsigned long long u64;
+#include "marex_cellwalk.hip.h"
 
 // rows loaded together of the one-cell and of the four-cell layout
 #ifndef LI_U1
@@ -25,15 +23,6 @@ typedef unsigned long long u64;
 #define LI_U4 4
 #endif
 #define LI_NCAT 6  // below, moderate, strong, severe, extreme, undefined
-
-template <typename T, int V>
-struct li_word;
-template <>
-struct li_word<int, 1> { typedef int type; };
-template <>
-struct li_word<unsigned char, 1> { typedef unsigned char type; };
-template <>
-struct li_word<unsigned char, 4> { typedef unsigned type; };
 
 __device__ __forceinline__ bool li_finite(float v) { return (__float_as_uint(v) & 0x7F800000u) != 0x7F800000u; }
 
@@ -54,7 +43,7 @@ k_local_intensity(const T* __restrict__ x, const float* __restrict__ anom, long 
                   const int* __restrict__ grp, int G, const float* __restrict__ thr, const int* __restrict__ doy, int n_doy,
                   const int* __restrict__ sgrp, int G2, const int* __restrict__ cls, int R, unsigned* days, unsigned* invalid,
                   double* sum, unsigned* vmax, int* tmax, unsigned* cat_days, u64* sec_cnt, u64* status) {
-    typedef typename li_word<T, V>::type W;
+    typedef typename cell_word<T, V>::type W;
     constexpr bool SIGNED = std::is_same<T, int>::value;
     constexpr int U = V == 4 ? LI_U4 : LI_U1;
     constexpr int NC = CATS ? LI_NCAT : 1, NS = SECT ? LI_NCAT : 1;
@@ -76,16 +65,7 @@ k_local_intensity(const T* __restrict__ x, const float* __restrict__ anom, long 
         for (int q = 0; q < NS; ++q) scnt[j][q] = 0;
         if (SECT) {  // the wave's distinct classes among the sub-cells j: the k-th goes to lane k
             const int cj = active ? cls[c0 + j] : -1;
-            u64 todo = __ballot(cj >= 0 && cj < R);
-            for (int n = 0; todo; ++n) {  // at most 64 rounds: each takes at least one lane
-                const int cv = __shfl(cj, __ffsll((long long)todo) - 1, 64);
-                const u64 same = __ballot(cj == cv) & todo;
-                if (lane == n) {
-                    smask[j] = same;
-                    scls[j] = cv;
-                }
-                todo &= ~same;
-            }
+            wave_class_partition(cj, R, lane, smask[j], scls[j]);
         }
     }
     int cg = grp ? grp[t0] : 0;
@@ -158,8 +138,8 @@ k_local_intensity(const T* __restrict__ x, const float* __restrict__ anom, long 
             const bool dok = dk[k] >= 0 && dk[k] < n_doy;
 #pragma unroll
             for (int j = 0; j < V; ++j) {
-                const int v = V == 4 ? (int)(((unsigned)w[k] >> (8 * j)) & 255u) : (int)w[k];
-                const bool p = match ? v == match : v > 0;  // a row past Tb or a lane past C holds 0: never present
+                const int v = cell_value<V>(w[k], j);
+                const bool p = cell_present(v, match);  // a row past Tb or a lane past C holds 0: never present
                 av[k][j] = p ? anom[(size_t)(r + k) * (size_t)C + c0 + j] : 0.f;
                 hv[k][j] = (CATS && p && dok) ? thr[(size_t)dk[k] * (size_t)C + c0 + j] : 0.f;
             }
@@ -184,8 +164,8 @@ k_local_intensity(const T* __restrict__ x, const float* __restrict__ anom, long 
                 const bool row_ok = gok && (!CATS || (dk[k] >= 0 && dk[k] < n_doy));  // wave-uniform
 #pragma unroll
                 for (int j = 0; j < V; ++j) {
-                    const int v = V == 4 ? (int)(((unsigned)w[k] >> (8 * j)) & 255u) : (int)w[k];
-                    const bool p = match ? v == match : v > 0;
+                    const int v = cell_value<V>(w[k], j);
+                    const bool p = cell_present(v, match);
                     if (SIGNED) neg += v < 0;
                     if (!row_ok) {  // the step addresses nothing: its present cells are counted
                         lost += p;
@@ -226,8 +206,7 @@ template <typename T, int V>
 static void li_launch(marex_ctx* ctx, const T* x, const float* anom, long t0, long Tb, long C, int match, const int* grp, int G,
                       const float* thr, const int* doy, int n_doy, const int* sgrp, int G2, const int* cls, int R, unsigned* days,
                       unsigned* invalid, double* sum, unsigned* vmax, int* tmax, unsigned* cat_days, u64* sec_cnt, u64* status) {
-    const long lanes = (C + V - 1) / V;
-    const dim3 grid((unsigned)((lanes + 255) / 256)), block(256);
+    const dim3 grid = cell_grid<V>(C), block(256);
 #define LI_GO(CATS, SECT)                                                                                                    \
     hipLaunchKernelGGL((k_local_intensity<T, V, CATS, SECT>), grid, block, 0, ctx->stream, x, anom, t0, Tb, C, match, grp, G, \
                        thr, doy, n_doy, sgrp, G2, cls, R, days, invalid, sum, vmax, tmax, cat_days, sec_cnt, status)
@@ -257,8 +236,7 @@ static int li_entry(marex_ctx* ctx, const char* name, const T* x, const float* a
         (nsec == 3 && (G2 <= 0 || R <= 0 || ncat != 3)))
         return fail(ctx, -1, "%s: null pointer, empty shape, negative match, no group, category or section arguments given in "
                              "part, or sections without thresholds", name);
-    if (C >= 2147483647L || t0 >= 2147483647L || Tb >= 2147483647L || t0 + Tb >= 2147483647L)
-        return fail(ctx, -4, "%s: a row or the time axis has 2^31 - 1 or more entries", name);
+    if (const int rc = cell_stream_limits(ctx, name, t0, Tb, C)) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     LaunchTimer lt(ctx, MAREX_K_MORPH);
     // four cells per lane without categories; the category builds run one cell per lane (register budget: DESIGN.md section 4)
@@ -275,20 +253,13 @@ static int li_entry(marex_ctx* ctx, const char* name, const T* x, const float* a
     return 0;
 }
 
-extern "C" int marex_local_intensity_u8(marex_ctx* ctx, const uint8_t* x, const float* anom, int64_t t0, int64_t Tb, int64_t C,
-                                        int match, const int32_t* grp, int G, const float* thr, const int32_t* doy, int n_doy,
-                                        const int32_t* sgrp, int G2, const int32_t* cls, int R, uint32_t* days,
-                                        uint32_t* invalid, double* sum, uint32_t* vmax, int32_t* tmax, uint32_t* cat_days,
-                                        uint64_t* sec_cnt, uint64_t* status) {
-    return li_entry<unsigned char>(ctx, "marex_local_intensity_u8", (const unsigned char*)x, anom, t0, Tb, C, match, grp, G, thr,
-                                   doy, n_doy, sgrp, G2, cls, R, days, invalid, sum, vmax, tmax, cat_days, sec_cnt, status);
-}
-
-extern "C" int marex_local_intensity_i32(marex_ctx* ctx, const int32_t* x, const float* anom, int64_t t0, int64_t Tb, int64_t C,
-                                         int match, const int32_t* grp, int G, const float* thr, const int32_t* doy, int n_doy,
-                                         const int32_t* sgrp, int G2, const int32_t* cls, int R, uint32_t* days,
-                                         uint32_t* invalid, double* sum, uint32_t* vmax, int32_t* tmax, uint32_t* cat_days,
-                                         uint64_t* sec_cnt, uint64_t* status) {
-    return li_entry<int>(ctx, "marex_local_intensity_i32", (const int*)x, anom, t0, Tb, C, match, grp, G, thr, doy, n_doy, sgrp,
-                         G2, cls, R, days, invalid, sum, vmax, tmax, cat_days, sec_cnt, status);
-}
+#define LI_EXPORT(SFX, XT, T)  /* marex_local_intensity_u8, marex_local_intensity_i32 */                                           \
+    extern "C" int marex_local_intensity_##SFX(                                                                                    \
+        marex_ctx* ctx, const XT* x, const float* anom, int64_t t0, int64_t Tb, int64_t C, int match, const int32_t* grp, int G,   \
+        const float* thr, const int32_t* doy, int n_doy, const int32_t* sgrp, int G2, const int32_t* cls, int R, uint32_t* days,   \
+        uint32_t* invalid, double* sum, uint32_t* vmax, int32_t* tmax, uint32_t* cat_days, uint64_t* sec_cnt, uint64_t* status) {  \
+        return li_entry<T>(ctx, "marex_local_intensity_" #SFX, (const T*)x, anom, t0, Tb, C, match, grp, G, thr, doy, n_doy, sgrp, \
+                           G2, cls, R, days, invalid, sum, vmax, tmax, cat_days, sec_cnt, status);                                 \
+    }
+LI_EXPORT(u8, uint8_t, unsigned char)
+LI_EXPORT(i32, int32_t, int)

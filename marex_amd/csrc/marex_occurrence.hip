@@ -13,9 +13,7 @@
 // sub-cell of the four-cell layout), adds popcount(ballot(present) & mask) per row, and issues one integer atomicAdd per
 // class when the section label changes -- no per-lane atomic on a shared address inside the row loop.
 // All results are integers: exact, and independent of any order and of how the rows are cut into calls.
-#include "marex_common.hip.h"
-
-typedef unsigned long long u64;
+#include "marex_cellwalk.hip.h"
 
 // rows loaded together (loads in flight per lane) of the one-cell and of the four-cell layout
 #ifndef OCC_U1
@@ -25,15 +23,6 @@ typedef unsigned long long u64;
 #define OCC_U4 16
 #endif
 
-template <typename T, int V>
-struct occ_word;
-template <>
-struct occ_word<int, 1> { typedef int type; };
-template <>
-struct occ_word<unsigned char, 1> { typedef unsigned char type; };
-template <>
-struct occ_word<unsigned char, 4> { typedef unsigned type; };
-
 // Rows t0 .. t0 + Tb - 1 of the field: x [Tb][C].  T: int or unsigned char; V: cells per lane (4: C % 4 == 0 and x, cell_cnt
 // and run_state are aligned for the vector accesses -- the entry point checks); RUNS: run_state is given; SECT: sec_cnt,
 // sgrp and cls are given.  Lanes past the last cell stay in the loop (they take part in the ballots) with nothing present.
@@ -42,7 +31,7 @@ __global__ void __launch_bounds__(256)
 k_occurrence(const T* __restrict__ x, long t0, long Tb, long C, int match, const int* __restrict__ grp, int G,
              const int* __restrict__ sgrp, int G2, const int* __restrict__ cls, int R, unsigned* run_state, unsigned* cell_cnt,
              u64* sec_cnt, u64* status) {
-    typedef typename occ_word<T, V>::type W;
+    typedef typename cell_word<T, V>::type W;
     constexpr bool SIGNED = std::is_same<T, int>::value;
     constexpr int OCC_U = V == 4 ? OCC_U4 : OCC_U1;
     const int lane = threadIdx.x & 63;
@@ -64,16 +53,7 @@ k_occurrence(const T* __restrict__ x, long t0, long Tb, long C, int match, const
         }
         if (SECT) {  // the wave's distinct classes among the sub-cells j: the k-th goes to lane k
             const int cj = active ? cls[c0 + j] : -1;
-            u64 todo = __ballot(cj >= 0 && cj < R);
-            for (int n = 0; todo; ++n) {  // at most 64 rounds: each takes at least one lane
-                const int cv = __shfl(cj, __ffsll((long long)todo) - 1, 64);
-                const u64 same = __ballot(cj == cv) & todo;
-                if (lane == n) {
-                    smask[j] = same;
-                    scls[j] = cv;
-                }
-                todo &= ~same;
-            }
+            wave_class_partition(cj, R, lane, smask[j], scls[j]);
         }
     }
     int cg = grp ? grp[t0] : 0;
@@ -135,8 +115,8 @@ k_occurrence(const T* __restrict__ x, long t0, long Tb, long C, int match, const
                 }
 #pragma unroll
                 for (int j = 0; j < V; ++j) {
-                    const int v = V == 4 ? (int)(((unsigned)w[k] >> (8 * j)) & 255u) : (int)w[k];
-                    const bool p = match ? v == match : v > 0;
+                    const int v = cell_value<V>(w[k], j);
+                    const bool p = cell_present(v, match);
                     if (SIGNED) neg += v < 0;
                     gcnt[j] += p;
                     if (RUNS) {
@@ -165,8 +145,7 @@ k_occurrence(const T* __restrict__ x, long t0, long Tb, long C, int match, const
 template <typename T, int V>
 static void occ_launch(marex_ctx* ctx, const T* x, long t0, long Tb, long C, int match, const int* grp, int G, const int* sgrp,
                        int G2, const int* cls, int R, unsigned* rs, unsigned* cell_cnt, u64* sec_cnt, u64* status) {
-    const long lanes = (C + V - 1) / V;
-    const dim3 grid((unsigned)((lanes + 255) / 256)), block(256);
+    const dim3 grid = cell_grid<V>(C), block(256);
 #define OCC_GO(RUNS, SECT)                                                                                                  \
     hipLaunchKernelGGL((k_occurrence<T, V, RUNS, SECT>), grid, block, 0, ctx->stream, x, t0, Tb, C, match, grp, G, sgrp, G2, \
                        cls, R, rs, cell_cnt, sec_cnt, status)
@@ -190,8 +169,7 @@ static int occ_entry(marex_ctx* ctx, const char* name, const T* x, int64_t t0, i
     if (!x || !cell_cnt || !status || t0 < 0 || Tb <= 0 || C <= 0 || match < 0 || G <= 0 || (!grp && G != 1) ||
         (nsec != 0 && nsec != 3) || (nsec == 3 && (G2 <= 0 || R <= 0)))
         return fail(ctx, -1, "%s: null pointer, empty shape, negative match, no group, or section arguments given in part", name);
-    if (C >= 2147483647L || t0 >= 2147483647L || Tb >= 2147483647L || t0 + Tb >= 2147483647L)
-        return fail(ctx, -4, "%s: a row or the time axis has 2^31 - 1 or more entries", name);
+    if (const int rc = cell_stream_limits(ctx, name, t0, Tb, C)) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     LaunchTimer lt(ctx, MAREX_K_MORPH);
     const bool quad = sizeof(T) == 1 && C % 4 == 0 && ((uintptr_t)x & 3) == 0 && ((uintptr_t)cell_cnt & 15) == 0 &&
@@ -206,16 +184,12 @@ static int occ_entry(marex_ctx* ctx, const char* name, const T* x, int64_t t0, i
     return 0;
 }
 
-extern "C" int marex_occurrence_u8(marex_ctx* ctx, const uint8_t* x, int64_t t0, int64_t Tb, int64_t C, int match,
-                                   const int32_t* grp, int G, const int32_t* sgrp, int G2, const int32_t* cls, int R,
-                                   uint32_t* run_state, uint32_t* cell_cnt, uint64_t* sec_cnt, uint64_t* status) {
-    return occ_entry<unsigned char>(ctx, "marex_occurrence_u8", (const unsigned char*)x, t0, Tb, C, match, grp, G, sgrp, G2, cls, R,
-                                    run_state, cell_cnt, sec_cnt, status);
-}
-
-extern "C" int marex_occurrence_i32(marex_ctx* ctx, const int32_t* x, int64_t t0, int64_t Tb, int64_t C, int match,
-                                    const int32_t* grp, int G, const int32_t* sgrp, int G2, const int32_t* cls, int R,
-                                    uint32_t* run_state, uint32_t* cell_cnt, uint64_t* sec_cnt, uint64_t* status) {
-    return occ_entry<int>(ctx, "marex_occurrence_i32", (const int*)x, t0, Tb, C, match, grp, G, sgrp, G2, cls, R, run_state,
-                          cell_cnt, sec_cnt, status);
-}
+#define OCC_EXPORT(SFX, XT, T)  /* marex_occurrence_u8, marex_occurrence_i32 */                                                \
+    extern "C" int marex_occurrence_##SFX(marex_ctx* ctx, const XT* x, int64_t t0, int64_t Tb, int64_t C, int match,           \
+                                          const int32_t* grp, int G, const int32_t* sgrp, int G2, const int32_t* cls, int R,   \
+                                          uint32_t* run_state, uint32_t* cell_cnt, uint64_t* sec_cnt, uint64_t* status) {      \
+        return occ_entry<T>(ctx, "marex_occurrence_" #SFX, (const T*)x, t0, Tb, C, match, grp, G, sgrp, G2, cls, R, run_state, \
+                            cell_cnt, sec_cnt, status);                                                                        \
+    }
+OCC_EXPORT(u8, uint8_t, unsigned char)
+OCC_EXPORT(i32, int32_t, int)

@@ -16,9 +16,10 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._keys import key_float
 from .binning import BinTable
 from .calendar import N_DOY, CalendarPlan
-from .exceptions import ConfigurationError, ProcessingError, TrackingError
+from .exceptions import ConfigurationError, ProcessingError, TrackingError, create_data_validation_error
 from .track_mesh import mesh_moments_finish
 
 
@@ -69,8 +70,24 @@ def plan_time_blocks(T: int, C: int, max_block_cells: Optional[int] = None) -> L
 
 def _key_to_float(key: int) -> float:
     """Inverse of the order-preserving uint32 key used for the device-side min / max of thresholds."""
-    bits = (key & 0x7FFFFFFF) if (key & 0x80000000) else (~key & 0xFFFFFFFF)
-    return float(np.array([bits], dtype=np.uint32).view(np.float32)[0])
+    return float(key_float([key])[0])
+
+
+def label_tables(what: str, specs) -> Dict[str, Optional[np.ndarray]]:
+    """``{name: int32 vector or None}`` of the ``(name, values or None, length or None)`` in ``specs``; anything but an
+    integer vector of that length with values inside int32 is refused.  Needs no device."""
+    tabs = {}
+    for name, v, n in specs:
+        if v is None:
+            tabs[name] = None
+            continue
+        h = np.asarray(v)
+        if h.ndim != 1 or h.dtype.kind not in "iu" or (n is not None and h.size != n) or \
+                (h.size and (int(h.min()) < -2**31 or int(h.max()) > 2**31 - 1)):
+            raise ProcessingError(f"{what}: {name} must be a vector of int32 values" + (f" of length {n}" if n else ""),
+                                  details=f"got {h.dtype} {h.shape}")
+        tabs[name] = h.astype(np.int32)
+    return tabs
 
 
 def _linear_percentile(values: torch.Tensor, q: float) -> float:
@@ -773,8 +790,6 @@ class HotPath:
         self.call("marex_ids_minmax_i32", ids, ids.numel(), mm)
         lo, hi = (int(v) for v in mm.cpu().numpy())
         if lo < 0:
-            from .exceptions import create_data_validation_error
-
             raise create_data_validation_error("Object IDs must be non-negative", details=f"smallest ID {lo}; 0 is background",
                                                data_info={"min_id": lo, "max_id": hi})
         return lo, hi
@@ -1260,6 +1275,54 @@ class HotPath:
             out["wmom"] = wacc.cpu().numpy().reshape(T, n_ev, 4)
         return out
 
+    def _presence_window(self, what: str, x: torch.Tensor):
+        """``(x, Tb, Cn)`` of a presence window, a bool one viewed as uint8."""
+        if x.dim() != 2 or not x.is_contiguous() or x.device != self.device or x.dtype not in (torch.uint8, torch.bool, torch.int32):
+            raise ProcessingError(f"{what}: the field must be a contiguous uint8, bool or int32 [T, C] tensor on the engine's "
+                                  "device", details=f"got {x.dtype} {tuple(x.shape)} on {x.device}")
+        if x.dtype == torch.bool:
+            x = x.view(torch.uint8)
+        return x, int(x.shape[0]), int(x.shape[1])
+
+    def _anomaly_window_check(self, what: str, anom: torch.Tensor, Tb: int, Cn: int) -> None:
+        if anom.dtype != torch.float32 or tuple(anom.shape) != (Tb, Cn) or not anom.is_contiguous() or anom.device != self.device:
+            raise ProcessingError(f"{what}: the anomalies must be a contiguous float32 [{Tb}, {Cn}] tensor on the "
+                                  f"engine's device", details=f"got {anom.dtype} {tuple(anom.shape)} on {anom.device}")
+
+    def _upload_tables(self, tabs: dict) -> dict:
+        """The ``"len"`` and ``"tabs"`` entries of the accumulators: the tables of :func:`label_tables` on the device."""
+        return {"len": {k: (None if v is None else int(v.size)) for k, v in tabs.items()},
+                "tabs": {k: (None if v is None else self._dev(v)) for k, v in tabs.items()}}
+
+    @staticmethod
+    def _window_check(what: str, acc: dict, plan: tuple, step_tables, t0: int, Tb: int, Cn: int) -> None:
+        """The accumulators were planned for this call, every step table reaches the window's end, the window is not empty."""
+        if acc["plan"] != plan:
+            raise ProcessingError(f"{what}: the accumulators were planned for another call",
+                                  details=f"{acc['plan']} there, {plan} here")
+        for name in step_tables:
+            n = acc["len"][name]
+            if n is not None and n < t0 + Tb:
+                raise ProcessingError(f"{what}: {name} has {n} labels, the window ends at step {t0 + Tb}")
+        if Tb == 0 or Cn == 0:
+            raise ProcessingError(f"{what}: an empty window ({Tb} steps of {Cn} cells)")
+
+    @staticmethod
+    def _stream_status(what: str, acc: dict, passes: int, ranges: str) -> None:
+        """The host read of ``status``: negative cells, counted in each of the ``passes`` over a window, and lost ones."""
+        neg, lost = (int(v) for v in acc["status"].cpu().numpy())
+        if neg:
+            raise create_data_validation_error("Object IDs must be non-negative",
+                                               details=f"{neg // passes} negative cells; 0 is background",
+                                               data_info={"negative_cells": neg // passes})
+        if lost:
+            raise ProcessingError(f"{what}: {lost} present cells lie under a step label outside its range",
+                                  details=f"{ranges}; the cells were counted, nothing was written out of range")
+
+    @staticmethod
+    def _host(t: Optional[torch.Tensor], dt):
+        return None if t is None else t.cpu().numpy().view(dt)
+
     @staticmethod
     def event_slot_plan(ev_tmin, ev_tmax, T: Optional[int] = None) -> np.ndarray:
         """The compact (timestep, event) slots of :meth:`event_rename` and :meth:`event_intensity`: ``off`` int64
@@ -1289,9 +1352,7 @@ class HotPath:
         cell).  A cell of an event outside its declared span raises :class:`ProcessingError` (it was counted, nothing was
         written out of range)."""
         Tb, Cn = self._ids_check(ids)
-        if anom.dtype != torch.float32 or tuple(anom.shape) != (Tb, Cn) or not anom.is_contiguous() or anom.device != self.device:
-            raise ProcessingError(f"event_intensity: the anomalies must be a contiguous float32 [{Tb}, {Cn}] tensor on the "
-                                  f"engine's device", details=f"got {anom.dtype} {tuple(anom.shape)} on {anom.device}")
+        self._anomaly_window_check("event_intensity", anom, Tb, Cn)
         if weights is not None and (weights.dtype != torch.float32 or tuple(weights.shape) != (Cn,) or not weights.is_contiguous()
                                     or weights.device != self.device):
             raise ProcessingError(f"event_intensity: the weights must be a contiguous float32 [{Cn}] tensor on the engine's "
@@ -1326,10 +1387,8 @@ class HotPath:
         if bad:
             raise ProcessingError(f"event_intensity: {bad} cells belong to an event outside its declared span of timesteps",
                                   details="ev_tmin / ev_tmax do not cover the field; the cells were counted, not accumulated")
-        key = acc["vmax"][:n_slots].cpu().numpy().view(np.uint32)
-        bits = np.where(key & np.uint32(0x80000000), key & np.uint32(0x7FFFFFFF), ~key)  # key 0 -> all ones: a NaN
         out.update(cnt=acc["cnt"][:n_slots].cpu().numpy(), sums=acc["sums"][:n_slots].cpu().numpy(),
-                   vmax=bits.astype(np.uint32).view(np.float32))
+                   vmax=key_float(acc["vmax"][:n_slots].cpu().numpy().view(np.uint32)))  # key 0: a NaN
         return out
 
     def occurrence(self, x: torch.Tensor, t0: int = 0, grp=None, G: int = 1, sgrp=None, G2: int = 0, cls=None, R: int = 0,
@@ -1346,12 +1405,7 @@ class HotPath:
         ``runs``), ``sec_cnt`` uint64 ``[G2, R]`` (None without sections) and ``dur`` uint32 ``[K, C]``.  A negative ID
         raises the trackers' "Object IDs must be non-negative" error, a step label outside its range a
         :class:`ProcessingError`; both were counted, nothing was written out of range."""
-        if x.dim() != 2 or not x.is_contiguous() or x.device != self.device or x.dtype not in (torch.uint8, torch.bool, torch.int32):
-            raise ProcessingError("occurrence: the field must be a contiguous uint8, bool or int32 [T, C] tensor on the engine's "
-                                  "device", details=f"got {x.dtype} {tuple(x.shape)} on {x.device}")
-        if x.dtype == torch.bool:
-            x = x.view(torch.uint8)
-        Tb, Cn = (int(k) for k in x.shape)
+        x, Tb, Cn = self._presence_window("occurrence", x)
         t0, G, G2, R = int(t0), int(G), int(G2), int(R)
         ids = [int(k) for k in event_ids]
         sect = sgrp is not None or cls is not None
@@ -1361,18 +1415,10 @@ class HotPath:
         if sect and (sgrp is None or cls is None or G2 <= 0 or R <= 0):
             raise ProcessingError("occurrence: the section counts need step labels, cell classes, G2 > 0 and R > 0 together",
                                   details=f"G2 = {G2}, R = {R}")
+        plan = (G, Cn, G2 if sect else 0, R if sect else 0, bool(runs), tuple(ids))
         if acc is None:
-            tabs = {}
-            for name, v, n in (("grp", grp, None), ("sgrp", sgrp if sect else None, None), ("cls", cls if sect else None, Cn)):
-                if v is None:
-                    tabs[name] = None
-                    continue
-                h = np.asarray(v)
-                if h.ndim != 1 or h.dtype.kind not in "iu" or (n is not None and h.size != n) or \
-                        (h.size and (int(h.min()) < -2**31 or int(h.max()) > 2**31 - 1)):
-                    raise ProcessingError(f"occurrence: {name} must be a vector of int32 values" + (f" of length {n}" if n else ""),
-                                          details=f"got {h.dtype} {h.shape}")
-                tabs[name] = h.astype(np.int32)
+            tabs = label_tables("occurrence", (("grp", grp, None), ("sgrp", sgrp if sect else None, None),
+                                               ("cls", cls if sect else None, Cn)))
             K = len(ids)
             need = 4 * G * Cn + (12 * Cn if runs else 0) + (8 * G2 * R if sect else 0) + 4 * K * Cn + 16 + \
                 sum(4 * v.size for v in tabs.values() if v is not None)
@@ -1385,18 +1431,8 @@ class HotPath:
                    "sec_cnt": self._buf(None, "occ_sec", (G2, R), torch.int64, self.device).zero_() if sect else None,
                    "dur": self._buf(None, "occ_dur", (K, Cn), torch.int32, self.device).zero_() if K else None,
                    "status": self._buf(None, "occ_status", (2,), torch.int64, self.device).zero_(),
-                   "len": {k: (None if v is None else int(v.size)) for k, v in tabs.items()},
-                   "tabs": {k: (None if v is None else self._dev(v)) for k, v in tabs.items()},
-                   "plan": (G, Cn, G2 if sect else 0, R if sect else 0, bool(runs), tuple(ids))}
-        elif acc["plan"] != (G, Cn, G2 if sect else 0, R if sect else 0, bool(runs), tuple(ids)):
-            raise ProcessingError("occurrence: the accumulators were planned for another call",
-                                  details=f"{acc['plan']} there, {(G, Cn, G2 if sect else 0, R if sect else 0, bool(runs), tuple(ids))} here")
-        for name in ("grp", "sgrp"):
-            n = acc["len"][name]
-            if n is not None and n < t0 + Tb:
-                raise ProcessingError(f"occurrence: {name} has {n} labels, the window ends at step {t0 + Tb}")
-        if Tb == 0 or Cn == 0:
-            raise ProcessingError(f"occurrence: an empty window ({Tb} steps of {Cn} cells)")
+                   "plan": plan, **self._upload_tables(tabs)}
+        self._window_check("occurrence", acc, plan, ("grp", "sgrp"), t0, Tb, Cn)
         fn = "marex_occurrence_i32" if x.dtype == torch.int32 else "marex_occurrence_u8"
         tb = acc["tabs"]
         self.call(fn, x, t0, Tb, Cn, 0, tb["grp"], G, tb["sgrp"], G2 if sect else 0, tb["cls"], R if sect else 0, acc["runs"],
@@ -1406,21 +1442,8 @@ class HotPath:
         out: Dict[str, object] = {"acc": acc}
         if not finish:
             return out
-        neg, lost = (int(v) for v in acc["status"].cpu().numpy())
-        if neg:
-            from .exceptions import create_data_validation_error
-
-            raise create_data_validation_error("Object IDs must be non-negative",
-                                               details=f"{neg // (1 + len(ids))} negative cells; 0 is background",
-                                               data_info={"negative_cells": neg // (1 + len(ids))})
-        if lost:
-            raise ProcessingError(f"occurrence: {lost} present cells lie under a step label outside its range",
-                                  details=f"grp must hold 0 .. {G - 1}, sgrp 0 .. {G2 - 1}; the cells were counted, nothing was "
-                                          "written out of range")
-
-        def host(t, dt):
-            return None if t is None else t.cpu().numpy().view(dt)
-
+        self._stream_status("occurrence", acc, 1 + len(ids), f"grp must hold 0 .. {G - 1}, sgrp 0 .. {G2 - 1}")
+        host = self._host
         out.update(cell_cnt=host(acc["cell_cnt"], np.uint32), runs=host(acc["runs"], np.uint32),
                    sec_cnt=host(acc["sec_cnt"], np.uint64),
                    dur=host(acc["dur"], np.uint32) if ids else np.zeros((0, Cn), np.uint32))
@@ -1442,15 +1465,8 @@ class HotPath:
         and ``sec_cnt`` uint64 ``[G2, R, 6]`` (None without thresholds / sections).  A negative ID raises the trackers'
         "Object IDs must be non-negative" error, a step label outside its range a :class:`ProcessingError`; both were
         counted, nothing was written out of range."""
-        if x.dim() != 2 or not x.is_contiguous() or x.device != self.device or x.dtype not in (torch.uint8, torch.bool, torch.int32):
-            raise ProcessingError("local_intensity: the field must be a contiguous uint8, bool or int32 [T, C] tensor on the "
-                                  "engine's device", details=f"got {x.dtype} {tuple(x.shape)} on {x.device}")
-        if x.dtype == torch.bool:
-            x = x.view(torch.uint8)
-        Tb, Cn = (int(k) for k in x.shape)
-        if anom.dtype != torch.float32 or tuple(anom.shape) != (Tb, Cn) or not anom.is_contiguous() or anom.device != self.device:
-            raise ProcessingError(f"local_intensity: the anomalies must be a contiguous float32 [{Tb}, {Cn}] tensor on the "
-                                  f"engine's device", details=f"got {anom.dtype} {tuple(anom.shape)} on {anom.device}")
+        x, Tb, Cn = self._presence_window("local_intensity", x)
+        self._anomaly_window_check("local_intensity", anom, Tb, Cn)
         t0, G, G2, R, match = int(t0), int(G), int(G2), int(R), int(match)
         cats = thr is not None or doy is not None
         sect = sgrp is not None or cls is not None
@@ -1469,18 +1485,8 @@ class HotPath:
         n_doy = int(thr.shape[0]) if cats else 0
         plan = (G, Cn, n_doy, G2 if sect else 0, R if sect else 0, match)
         if acc is None:
-            tabs = {}
-            for name, v, n in (("grp", grp, None), ("doy", doy if cats else None, None), ("sgrp", sgrp if sect else None, None),
-                               ("cls", cls if sect else None, Cn)):
-                if v is None:
-                    tabs[name] = None
-                    continue
-                h = np.asarray(v)
-                if h.ndim != 1 or h.dtype.kind not in "iu" or (n is not None and h.size != n) or \
-                        (h.size and (int(h.min()) < -2**31 or int(h.max()) > 2**31 - 1)):
-                    raise ProcessingError(f"local_intensity: {name} must be a vector of int32 values" + (f" of length {n}" if n else ""),
-                                          details=f"got {h.dtype} {h.shape}")
-                tabs[name] = h.astype(np.int32)
+            tabs = label_tables("local_intensity", (("grp", grp, None), ("doy", doy if cats else None, None),
+                                                    ("sgrp", sgrp if sect else None, None), ("cls", cls if sect else None, Cn)))
             need = G * Cn * (24 + (24 if cats else 0)) + (48 * G2 * R if sect else 0) + 16 + \
                 sum(4 * v.size for v in tabs.values() if v is not None)
             self._check_fits(need, "local intensity",
@@ -1495,18 +1501,8 @@ class HotPath:
                    "cat_days": self._buf(None, "li_cat", (G, 6, Cn), torch.int32, self.device).zero_() if cats else None,
                    "sec_cnt": self._buf(None, "li_sec", (G2, R, 6), torch.int64, self.device).zero_() if sect else None,
                    "status": self._buf(None, "li_status", (2,), torch.int64, self.device).zero_(),
-                   "len": {k: (None if v is None else int(v.size)) for k, v in tabs.items()},
-                   "tabs": {k: (None if v is None else self._dev(v)) for k, v in tabs.items()},
-                   "plan": plan}
-        elif acc["plan"] != plan:
-            raise ProcessingError("local_intensity: the accumulators were planned for another call",
-                                  details=f"{acc['plan']} there, {plan} here")
-        for name in ("grp", "doy", "sgrp"):
-            n = acc["len"][name]
-            if n is not None and n < t0 + Tb:
-                raise ProcessingError(f"local_intensity: {name} has {n} labels, the window ends at step {t0 + Tb}")
-        if Tb == 0 or Cn == 0:
-            raise ProcessingError(f"local_intensity: an empty window ({Tb} steps of {Cn} cells)")
+                   "plan": plan, **self._upload_tables(tabs)}
+        self._window_check("local_intensity", acc, plan, ("grp", "doy", "sgrp"), t0, Tb, Cn)
         fn = "marex_local_intensity_i32" if x.dtype == torch.int32 else "marex_local_intensity_u8"
         tb = acc["tabs"]
         self.call(fn, x, anom, t0, Tb, Cn, match, tb["grp"], G, thr if cats else None, tb["doy"], n_doy, tb["sgrp"],
@@ -1515,24 +1511,11 @@ class HotPath:
         out: Dict[str, object] = {"acc": acc}
         if not finish:
             return out
-        neg, lost = (int(v) for v in acc["status"].cpu().numpy())
-        if neg:
-            from .exceptions import create_data_validation_error
-
-            raise create_data_validation_error("Object IDs must be non-negative", details=f"{neg} negative cells; 0 is background",
-                                               data_info={"negative_cells": neg})
-        if lost:
-            raise ProcessingError(f"local_intensity: {lost} present cells lie under a step label outside its range",
-                                  details=f"grp must hold 0 .. {G - 1}, doy 0 .. {n_doy - 1}, sgrp 0 .. {G2 - 1}; the cells were "
-                                          "counted, nothing was written out of range")
-
-        def host(t, dt):
-            return None if t is None else t.cpu().numpy().view(dt)
-
+        self._stream_status("local_intensity", acc, 1, f"grp must hold 0 .. {G - 1}, doy 0 .. {n_doy - 1}, sgrp 0 .. {G2 - 1}")
+        host = self._host
         key = host(acc["vmax"], np.uint32)
-        bits = np.where(key & np.uint32(0x80000000), key & np.uint32(0x7FFFFFFF), ~key).astype(np.uint32)
         out.update(days=host(acc["days"], np.uint32), invalid=host(acc["invalid"], np.uint32), sum=host(acc["sum"], np.float64),
-                   vmax=np.where(key != 0, bits.view(np.float32), np.float32(np.nan)),  # key 0: none
+                   vmax=np.where(key != 0, key_float(key), np.float32(np.nan)),  # key 0: none
                    tmax=np.where(key != 0, host(acc["tmax"], np.int32), np.int32(-1)),
                    cat_days=host(acc["cat_days"], np.uint32), sec_cnt=host(acc["sec_cnt"], np.uint64))
         return out

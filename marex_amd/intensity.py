@@ -12,63 +12,10 @@ from typing import Optional
 
 import numpy as np
 
-from .exceptions import ConfigurationError, ProcessingError, TrackingError, create_data_validation_error
-from .track import _BLOCK_CELLS, PINNED_ID_FIELD_BYTES, _host, _tensor_of
-
-_I32_MAX = 2**31 - 1
-
-
-def float_key(a) -> np.ndarray:
-    """The order-preserving uint32 key of float32 values that the device maximum works on: ``bits | 2^31`` for a clear
-    sign bit, ``~bits`` otherwise.  Strictly monotone from -inf to +inf (-0 below +0); no finite value and neither infinity
-    maps to 0, which the kernel keeps for "no finite cell"."""
-    b = np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-    return np.where(b & np.uint32(0x80000000), ~b, b | np.uint32(0x80000000)).astype(np.uint32)
-
-
-def key_float(k) -> np.ndarray:
-    """Inverse of :func:`float_key`; key 0 gives a NaN."""
-    k = np.ascontiguousarray(k, dtype=np.uint32)
-    return np.where(k & np.uint32(0x80000000), k & np.uint32(0x7FFFFFFF), ~k).astype(np.uint32).view(np.float32)
-
-
-def _check_block_steps(block_steps):
-    b = block_steps
-    if b is not None and b != "auto" and (isinstance(b, (bool, str)) or not isinstance(b, (int, np.integer)) or b <= 0):
-        raise ConfigurationError("block_steps must be a positive number of timesteps, 'auto' or None", details=f"block_steps={b!r}")
-    return b if b is None or isinstance(b, str) else int(b)
-
-
-def _dtype_name(x) -> str:
-    t = _tensor_of(x)
-    if t is not None:
-        return str(t.dtype).replace("torch.", "")
-    return str(x.dtype if hasattr(x, "dtype") else np.asarray(x).dtype)
-
-
-def _kind(x) -> str:
-    """'i' for an integer field, 'f' for a float one, '?' for anything else (bool, complex, objects)."""
-    t = _tensor_of(x)
-    if t is not None:
-        if t.dtype.is_floating_point:
-            return "f"
-        return "?" if t.dtype.is_complex or "bool" in str(t.dtype) else "i"
-    k = np.dtype(_dtype_name(x)).kind
-    return "i" if k in "iu" else "f" if k == "f" else "?"
-
-
-def _time_of(field, T: int):
-    """``(name, values or None)`` of the leading (time) dimension of a field."""
-    dims = tuple(getattr(field, "dims", ()) or ())
-    name = dims[0] if dims else "time"
-    coords = getattr(field, "coords", None)
-    if coords is None or not dims:
-        return name, None
-    c = coords[name] if name in coords else next((coords[k] for k in coords if tuple(getattr(coords[k], "dims", ())) == (name,)), None)
-    if c is None:
-        return name, None
-    v = np.asarray(_host(c))
-    return name, (v if v.shape == (T,) else None)
+from ._keys import float_key, key_float  # noqa: F401 -- public here
+from ._stream import _I32_MAX, _Windows, _check_block_steps, _dtype_name, _kind, _plan_windows, _time_of
+from .exceptions import ProcessingError, TrackingError, create_data_validation_error
+from .track import _host
 
 
 def _validate(ID_field, dat_anomaly, cell_areas):
@@ -118,86 +65,6 @@ def _validate(ID_field, dat_anomaly, cell_areas):
                                                details=f"{int((~np.isfinite(a)).sum())} non-finite, {int((a < 0).sum())} negative")
         w = np.ascontiguousarray(a, dtype=np.float32)
     return shape, tname, tv, w
-
-
-def _free_bytes(eng) -> int:
-    import torch
-
-    free, _ = torch.cuda.mem_get_info(eng.device)
-    return int(free + torch.cuda.memory_reserved(eng.device) - torch.cuda.memory_allocated(eng.device))
-
-
-class _Windows:
-    """The rows ``a .. b`` of a ``[T, C]`` field as a device tensor of one dtype: a view of a resident field (converted per
-    window when its type differs), an upload of a host one -- through the engine's pinned pipe where the window is large."""
-
-    def __init__(self, eng, field, T: int, C: int, np_dtype, is_ids: bool):
-        import torch
-
-        self.eng, self.np_dtype, self.is_ids = eng, np.dtype(np_dtype), is_ids
-        self.item = self.np_dtype.itemsize
-        self.tdt = torch.uint8 if self.np_dtype == np.uint8 else torch.int32 if is_ids else torch.float32
-        t = _tensor_of(field)
-        self.dev = self.host = None
-        if t is not None:
-            if t.dtype == torch.bool and self.tdt == torch.uint8:
-                t = t.view(torch.uint8)  # the bytes of a bool tensor are 0 / 1: read in place
-            if t.device != eng.device:
-                t = t.to(eng.device)
-            self.dev = t.reshape(T, C) if t.is_contiguous() else t.contiguous().reshape(T, C)
-        else:
-            self.host = np.asarray(field.values if hasattr(field, "values") else field).reshape(T, C)
-
-    @property
-    def upload_bytes_per_step(self) -> int:
-        if self.host is not None:
-            return self.item * self.host.shape[1]
-        return 0 if self.dev.dtype == self.tdt else self.item * self.dev.shape[1]
-
-    def _range_check(self, lo: int, hi: int) -> None:
-        if lo < 0 or hi > _I32_MAX:
-            from .track import tracker
-
-            raise tracker._id_range_error(lo, hi)
-
-    def get(self, a: int, b: int):
-        import torch
-
-        if self.dev is not None:
-            x = self.dev[a:b]
-            if x.dtype != self.tdt:
-                if self.is_ids and x.numel():
-                    self._range_check(int(x.min().item()), int(x.max().item()))
-                x = x.to(self.tdt)
-            return x
-        h = self.host[a:b]
-        if self.is_ids and h.dtype != np.int32 and h.size:
-            self._range_check(int(h.min()), int(h.max()))
-        if h.shape[0] * h.shape[1] * self.item >= PINNED_ID_FIELD_BYTES:
-            from .detect import _pipe
-
-            return _pipe(self.eng).upload(h, self.np_dtype)
-        return torch.from_numpy(np.ascontiguousarray(h, dtype=self.np_dtype)).to(self.eng.device)
-
-
-def _plan_windows(eng, T: int, C: int, per_step: int, block_steps, what: str = "event_intensity", details: Optional[str] = None):
-    """Steps per window.  ``per_step``: bytes a window takes per timestep beyond what is resident already.  ``what`` /
-    ``details`` word the error of a field that does not fit whole."""
-    cap = max(1, _BLOCK_CELLS // C)  # the span kernels take blocks below 2^31 - 1 cells
-    if block_steps is None:
-        free = _free_bytes(eng)
-        if T * per_step > free:
-            raise TrackingError(f"{what}: needs {T * per_step / 1e9:.3f} GB of device memory, {free / 1e9:.3f} GB are free",
-                                details=details or
-                                f"the ID field and the anomalies of {T} timesteps of {C} cells, 4 bytes per cell each, "
-                                "as far as they are not on the device already",
-                                suggestions=["Pass block_steps='auto'", "Pass block_steps=<timesteps per window>"])
-        return min(T, cap)
-    if block_steps == "auto":
-        free = _free_bytes(eng)
-        free -= free // 16  # the slots, the small tables and the allocator's rounding
-        return max(1, min(T, cap, free // per_step if per_step else T))
-    return min(int(block_steps), T, cap)
 
 
 def _device_slots(eng, ID_field, dat_anomaly, w, T: int, C: int, block_steps):

@@ -15,12 +15,10 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import calendar
-from . import intensity as _mi
+from . import _stream, calendar, occurrence as mo
+from ._stream import _I32_MAX, _Windows, _check_block_steps, _dtype_name, _kind, _plan_windows
 from .exceptions import TrackingError, create_data_validation_error
-from .intensity import _I32_MAX, _Windows, _check_block_steps, _dtype_name, _kind, _plan_windows, _time_of
-from .occurrence import _calendar, _field_kind, group_labels, lat_classes, zonal_labels
-from .track import _host, _tensor_of
+from .track import _tensor_of
 
 CATEGORIES = ("below", "moderate", "strong", "severe", "extreme", "undefined")
 
@@ -69,44 +67,8 @@ def _threshold_layout(thresholds, sp, sdims):
 
 def _plan(field, dat_anomaly, thresholds, by, zonal, zonal_by, lat, lat_bins, event_id, block_steps):
     """Everything that can be refused or derived without a device."""
-    p = {"block_steps": _check_block_steps(block_steps)}
-    shape = tuple(int(k) for k in field.shape)
-    if len(shape) not in (2, 3):
-        raise create_data_validation_error("field must be (time, y, x) or (time, cells)", details=f"got shape {shape}")
-    ashape = tuple(int(k) for k in dat_anomaly.shape)
-    if ashape != shape:
-        raise create_data_validation_error("field and dat_anomaly differ in shape", details=f"field {shape}, dat_anomaly {ashape}")
-    dims, d_a = tuple(getattr(field, "dims", ()) or ()), tuple(getattr(dat_anomaly, "dims", ()) or ())
-    if dims and d_a and dims != d_a:
-        raise create_data_validation_error("field and dat_anomaly differ in their dimensions",
-                                           details=f"field {dims}, dat_anomaly {d_a}; the order must agree too")
-    p["kind"] = _field_kind(field)
-    p["bool"] = _dtype_name(field) == "bool"
-    if _kind(dat_anomaly) != "f":
-        raise create_data_validation_error("dat_anomaly must be a floating-point field",
-                                           details=f"Found dtype {_dtype_name(dat_anomaly)}",
-                                           data_info={"actual_dtype": _dtype_name(dat_anomaly)})
-    T, C = shape[0], int(np.prod(shape[1:]))
-    p.update(shape=shape, T=T, C=C)
-    if C >= _I32_MAX or T >= _I32_MAX:
-        raise TrackingError(f"local_intensity: a timestep of {C} cells or a record of {T} steps reaches 2^31 - 1",
-                            details="the field may hold any number of cells, a single timestep and the time axis may not")
-    tname, tv = _time_of(field, T)
-    _, tv_a = _time_of(dat_anomaly, T)
-    if tv is not None and tv_a is not None and not np.array_equal(tv, tv_a):
-        raise create_data_validation_error("field and dat_anomaly differ in their time coordinate",
-                                           details=f"the first difference is at step {int(np.argmax(tv != tv_a))}")
-    tv = tv if tv is not None else tv_a
-    p.update(tname=tname, tv=tv)
-    labelled = dims or d_a
-    sdims = labelled[1:] if labelled else (("y", "x") if len(shape) == 3 else ("cells",))
-    coords = {}
-    for src in (dat_anomaly, field):
-        for k, c in (getattr(src, "coords", None) or {}).items():
-            cd = tuple(getattr(c, "dims", ()) or ())
-            if cd and all(d in sdims for d in cd):
-                coords[k] = (cd, np.asarray(_host(c)))
-    p.update(sdims=sdims, scoords=coords)
+    p = {"block_steps": _check_block_steps(block_steps), **_stream.plan_field(field, "local_intensity", dat_anomaly)}
+    shape, T, tv = p["shape"], p["T"], p["tv"]
     p["match"] = 0
     if event_id is not None:
         if p["bool"]:
@@ -117,29 +79,19 @@ def _plan(field, dat_anomaly, thresholds, by, zonal, zonal_by, lat, lat_bins, ev
         p["match"] = int(k)
     p["thr"] = None
     if thresholds is not None:
-        kind = _threshold_layout(thresholds, shape[1:], labelled[1:] if labelled else None)
+        kind = _threshold_layout(thresholds, shape[1:], p["sdims"] if p["labelled"] else None)
         doy = np.zeros(T, np.int32)
         if kind != "none":
-            _calendar(tv, "thresholds by dayofyear")
+            mo._calendar(tv, "thresholds by dayofyear")
             doy = (calendar._to_year_doy(tv)[1].astype(np.int32) - 1) if T else doy  # the row preprocess_data compares with
         p["thr"] = (kind, doy, 1 if kind == "none" else calendar.N_DOY)
     elif zonal:
         raise create_data_validation_error("zonal category counts need thresholds",
                                            details="zonal=True counts the cells of every category per latitude class")
-    p["grp"] = None if by is None else group_labels(by, tv, T)
+    p["grp"] = None if by is None else mo.group_labels(by, tv, T)
     p["sec"] = None
     if zonal:
-        lab = zonal_labels(zonal_by, tv, T)
-        if len(shape) == 3:
-            if lat is not None or lat_bins is not None:
-                raise create_data_validation_error("lat and lat_bins belong to a mesh: on a grid the classes are the y rows")
-            ny, nx = shape[1], shape[2]
-            cls = np.repeat(np.arange(ny, dtype=np.int32), nx)
-            yc = coords.get(sdims[0])
-            p["sec"] = (lab, cls, ny, sdims[0], None if yc is None else yc[1], np.full(ny, nx, np.int64))
-        else:
-            cls, R, e = lat_classes(lat, lat_bins, C)
-            p["sec"] = (lab, cls, R, "lat_bins", 0.5 * (e[:-1] + e[1:]), np.bincount(cls[cls >= 0], minlength=R).astype(np.int64))
+        p["sec"] = _stream.plan_sections(p, zonal_by, lat, lat_bins)
     return p
 
 
@@ -159,7 +111,7 @@ def _device_thresholds(eng, thresholds, kind: str, n_doy: int, C: int):
 
 def _window_steps(eng, T: int, C: int, per_step: int, fixed: int, block_steps, details: str) -> int:
     """Steps per window; ``fixed``: the bytes that stay for the whole call (accumulators, thresholds)."""
-    free = _mi._free_bytes(eng)
+    free = _stream._free_bytes(eng)
     need = fixed + per_step * (T if block_steps is None else 1)
     if need > free:
         raise TrackingError(f"local_intensity: needs {need / 1e9:.3f} GB of device memory, {free / 1e9:.3f} GB are free",
@@ -204,12 +156,11 @@ def _device_pass(p, field, dat_anomaly, thresholds, device):
         kw.update(thr=_device_thresholds(eng, thresholds, p["thr"][0], n_doy, C), doy=p["thr"][1])
     if sec is not None:
         kw.update(sgrp=sec[0][0], G2=sec[0][1], cls=sec[1], R=sec[2])
-    acc, r = None, None
-    for a in range(0, T, B):
-        b = min(T, a + B)
-        r = eng.local_intensity(x_w.get(a, b), a_w.get(a, b), t0=a, acc=acc, finish=b == T, **kw)
-        acc = r["acc"]
-    return r
+
+    def step(a, b, acc, finish):
+        return eng.local_intensity(x_w.get(a, b), a_w.get(a, b), t0=a, acc=acc, finish=finish, **kw)
+
+    return _stream.walk_windows(T, B, step)
 
 
 def _time_of_max(tv, T: int, tmax, has):
@@ -223,24 +174,18 @@ def _time_of_max(tv, T: int, tmax, has):
 
 
 def _local_intensity(field, dat_anomaly, thresholds, by, zonal, zonal_by, lat, lat_bins, event_id, block_steps, device):
-    from .occurrence import _ratio
     from .xr_compat import DataArray, Dataset
 
     p = _plan(field, dat_anomaly, thresholds, by, zonal, zonal_by, lat, lat_bins, event_id, block_steps)
     r = _device_pass(p, field, dat_anomaly, thresholds, device)
-    T, sp, sdims, scoords = p["T"], p["shape"][1:], p["sdims"], p["scoords"]
+    T, _ratio = p["T"], mo._ratio
     grouped = p["grp"] is not None
     gname, gvals = (p["grp"][2], p["grp"][3]) if grouped else (None, None)
     gc = {gname: (gname, gvals)} if grouped else {}
 
     def space(v, mid=(), extra=None):
         """``v [G, *mid, C]`` over (group,) + mid + the spatial dims; the group axis is dropped without ``by``."""
-        v = v if grouped else v[0]
-        lead = ((gname,) if grouped else ()) + tuple(mid)
-        c = dict(scoords)
-        c.update(gc)
-        c.update(extra or {})
-        return DataArray(v.reshape(v.shape[:len(lead)] + sp), dims=lead + tuple(sdims), coords=c)
+        return _stream.space(p, v if grouped else v[0], ((gname,) if grouped else ()) + tuple(mid), {**gc, **(extra or {})})
 
     days = r["days"]
     has = ~np.isnan(r["vmax"])
@@ -260,16 +205,13 @@ def _local_intensity(field, dat_anomaly, thresholds, by, zonal, zonal_by, lat, l
             peak[cat[:, k] > 0] = k
         data["category_peak"] = space(peak)
     if p["sec"] is not None:
-        (_, _, zname, zvals), _, R, cname, cvals, ccells = p["sec"]
-        zc = {zname: (zname, zvals), "category": ("category", np.array(CATEGORIES))}
-        if cvals is not None:
-            zc[cname] = (cname, cvals)
+        zname, cname, zc, class_cells = _stream.section_coords(p["sec"], {"category": ("category", np.array(CATEGORIES))})
         sec = r["sec_cnt"]
         per_cat = sec.sum(axis=1, dtype=np.uint64)
         data["category_cells"] = DataArray(sec, dims=(zname, cname, "category"), coords=zc)
         data["category_share"] = DataArray(_ratio(per_cat, per_cat.sum(axis=1, dtype=np.uint64)[:, None]), dims=(zname, "category"),
                                            coords={k: zc[k] for k in (zname, "category")})
-        data["class_cells"] = DataArray(ccells, dims=(cname,), coords={cname: zc[cname]} if cvals is not None else None)
+        data["class_cells"] = class_cells
     return Dataset(data)
 
 

@@ -12,11 +12,14 @@ are derived on the host from the time coordinate.
 """
 from __future__ import annotations
 
+from functools import partial
+
 import numpy as np
 
-from .exceptions import ConfigurationError, TrackingError, create_data_validation_error
-from .intensity import _I32_MAX, _Windows, _check_block_steps, _dtype_name, _plan_windows, _time_of
-from .track import _host, _tensor_of
+from . import _stream
+from ._stream import _I32_MAX, _Windows, _check_block_steps, _plan_windows
+from .exceptions import ConfigurationError, create_data_validation_error
+from .track import _host
 
 SEASONS = ("DJF", "JJA", "MAM", "SON")  # xarray's (alphabetical) order of the groups of "time.season"
 _SEASON_OF_MONTH = np.array([0, 0, 2, 2, 2, 1, 1, 1, 3, 3, 3, 0], np.int32)  # January .. December
@@ -114,45 +117,10 @@ def lat_classes(lat, lat_bins, C: int):
     return r.astype(np.int32), R, e
 
 
-def _field_kind(field) -> str:
-    """'m' for a mask (bool or uint8), 'i' for another integer field."""
-    t = _tensor_of(field)
-    name = _dtype_name(field) if t is None else str(t.dtype).replace("torch.", "")
-    if name in ("bool", "uint8"):
-        return "m"
-    try:
-        kind = np.dtype(name).kind
-    except TypeError:
-        kind = "?"
-    if kind not in "iu":
-        raise create_data_validation_error("field must be a mask (bool or uint8) or an integer ID field",
-                                           details=f"Found dtype {name}", data_info={"actual_dtype": name})
-    return "i"
-
-
 def _plan(field, by, zonal, zonal_by, lat, lat_bins, event_ids, block_steps):
     """Everything that can be refused or derived without a device."""
-    p = {"block_steps": _check_block_steps(block_steps)}
-    shape = tuple(int(k) for k in field.shape)
-    if len(shape) not in (2, 3):
-        raise create_data_validation_error("field must be (time, y, x) or (time, cells)", details=f"got shape {shape}")
-    p["kind"] = _field_kind(field)
-    p["bool"] = _dtype_name(field) == "bool"
-    T, C = shape[0], int(np.prod(shape[1:]))
-    p.update(shape=shape, T=T, C=C)
-    if C >= _I32_MAX or T >= _I32_MAX:
-        raise TrackingError(f"event_occurrence: a timestep of {C} cells or a record of {T} steps reaches 2^31 - 1",
-                            details="the field may hold any number of cells, a single timestep and the time axis may not")
-    dims = tuple(getattr(field, "dims", ()) or ())
-    p["tname"], tv = _time_of(field, T)
-    p["tv"] = tv
-    sdims = dims[1:] if dims else (("y", "x") if len(shape) == 3 else ("cells",))
-    coords = {}
-    for k, c in (getattr(field, "coords", None) or {}).items():
-        cd = tuple(getattr(c, "dims", ()) or ())
-        if cd and all(d in sdims for d in cd):
-            coords[k] = (cd, np.asarray(_host(c)))
-    p.update(sdims=sdims, scoords=coords)
+    p = {"block_steps": _check_block_steps(block_steps), **_stream.plan_field(field, "event_occurrence")}
+    T, tv = p["T"], p["tv"]
     ids = []
     if event_ids is not None:
         ids = [k for k in np.asarray(event_ids).reshape(-1).tolist()]
@@ -164,18 +132,7 @@ def _plan(field, by, zonal, zonal_by, lat, lat_bins, event_ids, block_steps):
     p["grp"] = None if by is None else group_labels(by, tv, T)
     p["sec"] = None
     if zonal:
-        lab = zonal_labels(zonal_by, tv, T)
-        if len(shape) == 3:
-            if lat is not None or lat_bins is not None:
-                raise create_data_validation_error("lat and lat_bins belong to a mesh: on a grid the classes are the y rows")
-            ny, nx = shape[1], shape[2]
-            cls = np.repeat(np.arange(ny, dtype=np.int32), nx)
-            yc = coords.get(sdims[0])
-            p["sec"] = (lab, cls, ny, sdims[0], None if yc is None else yc[1], np.full(ny, nx, np.int64))
-        else:
-            cls, R, e = lat_classes(lat, lat_bins, C)
-            p["sec"] = (lab, cls, R, "lat_bins", 0.5 * (e[:-1] + e[1:]), np.bincount(cls[cls >= 0], minlength=R).astype(np.int64))
-            p["edges"] = e
+        p["sec"] = _stream.plan_sections(p, zonal_by, lat, lat_bins)
     return p
 
 
@@ -199,11 +156,11 @@ def _counts(p, field, device):
         kw.update(grp=p["grp"][0], G=G)
     if p["sec"] is not None:
         kw.update(sgrp=p["sec"][0][0], G2=p["sec"][0][1], cls=p["sec"][1], R=p["sec"][2])
-    acc, r = None, None
-    for a in range(0, T, B):
-        b = min(T, a + B)
-        r = eng.occurrence(wins.get(a, b), t0=a, event_ids=p["ids"], acc=acc, finish=b == T, **kw)
-        acc = r["acc"]
+
+    def step(a, b, acc, finish):
+        return eng.occurrence(wins.get(a, b), t0=a, event_ids=p["ids"], acc=acc, finish=finish, **kw)
+
+    r = _stream.walk_windows(T, B, step)
     return r["cell_cnt"], r["runs"], r["sec_cnt"], r["dur"]
 
 
@@ -217,13 +174,7 @@ def _event_occurrence(field, by, zonal, zonal_by, lat, lat_bins, event_ids, bloc
 
     p = _plan(field, by, zonal, zonal_by, lat, lat_bins, event_ids, block_steps)
     cell_cnt, runs, sec_cnt, dur = _counts(p, field, device)
-    T, sp, sdims, scoords = p["T"], p["shape"][1:], p["sdims"], p["scoords"]
-
-    def space(v, lead=(), extra=None):
-        c = dict(scoords)
-        c.update(extra or {})
-        return DataArray(v.reshape(v.shape[:len(lead)] + sp), dims=tuple(lead) + tuple(sdims), coords=c)
-
+    T, space = p["T"], partial(_stream.space, p)
     occ = cell_cnt.sum(axis=0, dtype=np.uint32) if cell_cnt.shape[0] != 1 else cell_cnt[0]
     data = {"occurrence": space(occ), "frequency": space(_ratio(occ, np.int64(T))), "n_runs": space(runs[1]),
             "longest_run": space(runs[2]), "mean_run": space(_ratio(occ, runs[1]))}
@@ -235,14 +186,12 @@ def _event_occurrence(field, by, zonal, zonal_by, lat, lat_bins, event_ids, bloc
         data["steps_by"] = DataArray(steps, dims=(gname,), coords=gc)
         data["frequency_by"] = space(_ratio(cell_cnt, steps[:, None]), (gname,), gc)
     if p["sec"] is not None:
-        (lab, G2, zname, zvals), _, R, cname, cvals, ccells = p["sec"]
+        (lab, G2, *_), *_, ccells = p["sec"]
         steps = np.bincount(lab, minlength=G2).astype(np.int64)
-        zc = {zname: (zname, zvals)}
-        if cvals is not None:
-            zc[cname] = (cname, cvals)
+        zname, cname, zc, class_cells = _stream.section_coords(p["sec"])
         data["presence_cells"] = DataArray(sec_cnt, dims=(zname, cname), coords=zc)
         data["presence"] = DataArray(_ratio(sec_cnt, steps[:, None] * ccells[None, :]), dims=(zname, cname), coords=zc)
-        data["class_cells"] = DataArray(ccells, dims=(cname,), coords={cname: zc[cname]} if cvals is not None else None)
+        data["class_cells"] = class_cells
     if event_ids is not None:
         ec = {"event": ("event", np.asarray(p["ids"], np.int32))}
         data["local_duration"] = space(dur, ("event",), ec)

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import marex_amd
+import marex_amd._stream as ms
 import marex_amd.intensity as mi
 from marex_amd.engine import HotPath, _key_to_float
 from marex_amd.exceptions import ConfigurationError, DataValidationError
@@ -157,7 +158,7 @@ def host_engine(monkeypatch):
 
     eng = HostEngine()
     monkeypatch.setattr(det, "get_engine", lambda device=0: eng)
-    monkeypatch.setattr(mi, "_free_bytes", lambda e: 1 << 30)
+    monkeypatch.setattr(ms, "_free_bytes", lambda e: 1 << 30)
     return eng
 
 

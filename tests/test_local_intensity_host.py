@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 import marex_amd
-import marex_amd.intensity as mi
+import marex_amd._stream as mi
 from marex_amd import calendar
 from marex_amd.engine import HotPath
 from marex_amd.exceptions import ConfigurationError, DataValidationError
