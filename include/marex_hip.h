@@ -690,6 +690,46 @@ int marex_local_intensity_i32(marex_ctx* ctx, const int32_t* x, const float* ano
                               int G2, const int32_t* cls, int R, uint32_t* days, uint32_t* invalid, double* sum, uint32_t* vmax,
                               int32_t* tmax, uint32_t* cat_days, uint64_t* sec_cnt, uint64_t* status);
 
+/* Per-cell events under the duration and gap rule of Hobday et al. (2016), from one streaming pass over an event mask and,
+ * optionally, the anomaly field.  Per cell a run of at least min_duration consecutive present steps qualifies (a shorter
+ * run is ignored and bridges nothing); walking the qualifying runs in time order, a run that starts at most max_gap steps
+ * after the end of the current event extends it, any other run starts a new one.  An event spans start .. end inclusive,
+ * gaps included; a run at either end of the record counts by its observed length.
+ *
+ * marex_cell_events_u8: x uint8 [Tb][C] (present where x > 0) and anom float32 [Tb][C] (or NULL) are the rows
+ *   t0 .. t0 + Tb - 1 of the fields.  The state of every cell is carried between calls in state_i32 int32 [4][C] (without
+ *   anom) or [10][C] (run length, start + 1 of the open event, its last qualifying step, records written; the event's
+ *   maximum key, its step and invalid steps; the same three of the tail) and state_f64 float64 [2][C] (the event's and the
+ *   tail's sum; NULL without anom): one plane per variable, zeroed by the caller before the first window.  finish != 0 on
+ *   the last window closes the open events at their last qualifying step.
+ *   An event that closes adds to the accumulators of the group of its START step, grp[start] (grp int32 [T], global steps,
+ *   must reach t0 + Tb; NULL with G == 1), all [G][C] and all NULL or all given: events uint32 += 1, event_days uint32 +=
+ *   end - start + 1, duration_max uint32 = max, and with anom sum float64 += the event's sum, vmax uint32 = max of the
+ *   event's maximum as an ordered key (0: none), invalid uint32 += the event's non-finite steps.  The intensity of an event
+ *   is taken over all steps start .. end.  Its sum has one fixed order: the steps of a run up to the one that qualifies it,
+ *   and the steps since the event's last qualifying step before them when the run joins an open event, are summed in
+ *   ascending time on their own (the tail) and join the event's sum as one term; every later step of the run is added to
+ *   the event's sum directly.  No window boundary changes a bit of it.  anom is fetched only under present steps and
+ *   under absent steps of an open event.  A start label outside 0 .. G - 1 addresses nothing: status[0] += 1.
+ *   mask uint8 (or NULL) is the base of the WHOLE [T][C] output, addressed with the global step: row t gets 1 where the
+ *   cell is in a qualified run, and when a run qualifies the steps of its event not marked yet -- from the run's start, or
+ *   from the step after the event's previous end -- are set to 1, also in rows of earlier windows.
+ *   rec_off int64 [C + 1] with rec_start and rec_end int32 [n] (and with anom rec_vmax uint32, rec_tmax int32, rec_sum
+ *   float64, rec_invalid uint32 [n]), or all NULL: the k-th event that closes in cell c is written at rec_off[c] + k, k
+ *   carried in the state; an event past rec_off[c + 1] is not written: status[1] += 1.  status uint64 [2].
+ *   Without anom four cells per lane through 32-bit accesses when C % 4 == 0 and x and mask are 4-byte aligned; one cell
+ *   per lane otherwise and with anom: same results.  No atomic touches a per-cell output.  Tb == 0 does nothing.
+ *   -1: null x, state_i32 or status, anom without state_f64, C <= 0, t0 < 0, Tb < 0, min_duration < 1, max_gap < 0, G <= 0,
+ *   NULL grp with G != 1, accumulators or records given in part or their anomaly members without anom, a pointer not
+ *   aligned to its element; -4: C or t0 + Tb of 2^31 - 1 or more.  Nothing is launched then.  Asynchronous on the context's
+ *   stream. */
+int marex_cell_events_u8(marex_ctx* ctx, const uint8_t* x, const float* anom, int64_t t0, int64_t Tb, int64_t C,
+                         int min_duration, int max_gap, int finish, const int32_t* grp, int G, int32_t* state_i32,
+                         double* state_f64, uint32_t* events, uint32_t* event_days, uint32_t* duration_max, double* sum,
+                         uint32_t* vmax, uint32_t* invalid, uint8_t* mask, const int64_t* rec_off, int32_t* rec_start,
+                         int32_t* rec_end, uint32_t* rec_vmax, int32_t* rec_tmax, double* rec_sum, uint32_t* rec_invalid,
+                         uint64_t* status);
+
 /* The partition kernels of the split-and-merge stage on an unstructured mesh (tracker.split_and_merge_objects_parallel,
  * marEx/track.py:3804-4814, 5246-5419).  A slice is int32 [C], values <= 0 are background, C below 2^31 - 1.  u: float64
  * [3][C], the unit vectors of the cells; pv: float64 [3][n], the unit vectors of the parents' centroids.  "Nearest" is the

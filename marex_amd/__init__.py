@@ -24,6 +24,7 @@ from .dask_adapter import preprocess_data_lazy
 from .intensity import event_intensity
 from .occurrence import event_occurrence
 from .local_intensity import local_intensity
+from .cell_events import cell_events
 from .track import tracker
 from .xr_compat import DataArray, Dataset
 
@@ -32,5 +33,6 @@ __all__ = [
     "smoothed_rolling_climatology", "MarExError", "DataValidationError", "ConfigurationError",
     "ProcessingError", "DependencyError", "create_data_validation_error", "DataArray", "Dataset",
     "tracker", "TrackingError", "event_intensity", "event_occurrence", "local_intensity",
+    "cell_events",
 ]
 __version__ = "0.1.0"

@@ -1,5 +1,5 @@
 #pragma once
-// marex_cellwalk.hip.h -- what the per-cell streaming kernels (marex_occurrence.hip, marex_local_intensity.hip) share: a
+// marex_cellwalk.hip.h -- what the per-cell streaming kernels (marex_occurrence.hip, marex_local_intensity.hip, marex_cell_events.hip) share: a
 // lane owns one cell, or four consecutive uint8 cells through one 32-bit load, for the whole call and walks the rows.
 // The kernels, their unroll depths and what they keep per cell stay in their units (the register
 // budgets differ).

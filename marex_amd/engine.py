@@ -1520,6 +1520,120 @@ class HotPath:
                    cat_days=host(acc["cat_days"], np.uint32), sec_cnt=host(acc["sec_cnt"], np.uint64))
         return out
 
+    def cell_event_records(self, acc: dict) -> Dict[str, object]:
+        """The record buffers of a second pass of :meth:`cell_events`, from the accumulators of a finished summary pass:
+        ``off`` int64 ``[C + 1]`` (the exclusive scan of the events per cell, summed over the groups, on the device), ``n``
+        and one array per record field, ``[n]`` on the device.  :class:`ProcessingError` with the figures when they do not
+        fit."""
+        G, Cn, anomalies = acc["plan"][0], acc["plan"][1], acc["plan"][2]
+        off = torch.zeros(Cn + 1, dtype=torch.int64, device=self.device)
+        torch.cumsum(acc["events"].sum(dim=0, dtype=torch.int64), 0, out=off[1:])
+        n = int(off[-1].item())
+        per = 8 + (20 if anomalies else 0)
+        self._check_fits(per * n, "cell events", f"{n} event records of {per} bytes (start, end"
+                         f"{', maximum, its step, float64 sum, invalid steps' if anomalies else ''}) for the second pass")
+        alloc = max(n, 1)
+        rec = {"off": off, "n": n, "start": self._buf(None, "ce_rstart", (alloc,), torch.int32, self.device),
+               "end": self._buf(None, "ce_rend", (alloc,), torch.int32, self.device)}
+        if anomalies:
+            rec.update(vmax=self._buf(None, "ce_rvmax", (alloc,), torch.int32, self.device),
+                       tmax=self._buf(None, "ce_rtmax", (alloc,), torch.int32, self.device),
+                       sum=self._buf(None, "ce_rsum", (alloc,), torch.float64, self.device),
+                       invalid=self._buf(None, "ce_rinv", (alloc,), torch.int32, self.device))
+        return rec
+
+    def cell_events(self, x: torch.Tensor, anom: Optional[torch.Tensor] = None, t0: int = 0, min_duration: int = 5,
+                    max_gap: int = 2, grp=None, G: int = 1, mask: Optional[torch.Tensor] = None, records: Optional[dict] = None,
+                    acc: Optional[dict] = None, finish: bool = True) -> Dict[str, object]:
+        """Per-cell events under the duration and gap rule of the rows ``t0 .. t0 + Tb - 1`` (``marex_cell_events_u8``):
+        ``x`` uint8 or bool ``[Tb, C]`` and, optionally, ``anom`` float32 ``[Tb, C]``.  ``grp`` (int ``[T]``, global steps, or
+        None with ``G == 1``) labels the steps; an event belongs to the group of its start.  ``mask``: the WHOLE uint8
+        ``[T, C]`` output (rows of earlier windows are completed when a run qualifies), or None.  The first window allocates
+        the zeroed state and accumulators and uploads the labels; a later window passes the ``"acc"`` entry of the previous
+        result -- the window lengths do not matter, not even to the last bit of ``sum``; ``finish`` on the last window
+        closes the open events.  Returns ``acc`` and, with ``finish``, ``events``, ``event_days`` and ``duration_max`` uint32
+        ``[G, C]`` and with ``anom`` ``sum`` float64, ``vmax`` float32 (NaN: none) and ``invalid`` uint32 ``[G, C]``.
+        ``records``: the buffers of :meth:`cell_event_records` make the call the SECOND pass (a fresh ``acc``, no
+        accumulators, no mask): the events are written at ``off[c] + k`` and ``finish`` returns ``rec``, the host arrays
+        ``off``, ``start``, ``end`` (and ``vmax``, ``tmax``, ``sum``, ``invalid``), beside ``records``, the device buffers.
+        An event whose start label lies outside ``0 .. G - 1`` raises :class:`ProcessingError`; it was counted, nothing was
+        written out of range."""
+        x, Tb, Cn = self._presence_window("cell_events", x)
+        if x.dtype != torch.uint8:
+            raise ProcessingError("cell_events: the field must be a uint8 or bool mask", details=f"got {x.dtype}")
+        if anom is not None:
+            self._anomaly_window_check("cell_events", anom, Tb, Cn)
+        t0, G, D, gap = int(t0), int(G), int(min_duration), int(max_gap)
+        if t0 < 0 or G <= 0 or (grp is None and G != 1) or not 1 <= D <= 2**31 - 1 or not 0 <= gap <= 2**31 - 1:
+            raise ProcessingError("cell_events: t0 and max_gap must not be negative, G and min_duration must be positive, and "
+                                  "G > 1 needs labels", details=f"t0 = {t0}, G = {G}, labels {'given' if grp is not None else 'missing'}, "
+                                                                f"min_duration = {D}, max_gap = {gap}")
+        if mask is not None and (records is not None or mask.dtype != torch.uint8 or mask.dim() != 2 or int(mask.shape[1]) != Cn or
+                                 int(mask.shape[0]) < t0 + Tb or not mask.is_contiguous() or mask.device != self.device):
+            raise ProcessingError(f"cell_events: the mask must be the whole contiguous uint8 [T, {Cn}] output on the engine's "
+                                  f"device, T >= {t0 + Tb}, and belongs to the summary pass",
+                                  details=f"got {mask.dtype} {tuple(mask.shape)} on {mask.device}")
+        anomalies, second = anom is not None, records is not None
+        plan = (G, Cn, anomalies, D, gap, second)
+        if acc is None:
+            tabs = label_tables("cell_events", (("grp", grp, None),))
+            planes = 10 if anomalies else 4
+            per_acc = 0 if second else 12 + (16 if anomalies else 0)
+            need = Cn * (4 * planes + (16 if anomalies else 0)) + G * Cn * per_acc + 16 + \
+                sum(4 * v.size for v in tabs.values() if v is not None)
+            self._check_fits(need, "cell events",
+                             f"{Cn} cells of carried state, {4 * planes + (16 if anomalies else 0)} bytes each, {G} x {Cn} cells "
+                             f"of accumulators, {per_acc} bytes each, and the label table")
+            dev = self.device
+            acc = {"state_i32": self._buf(None, "ce_sti", (planes, Cn), torch.int32, dev).zero_(),
+                   "state_f64": self._buf(None, "ce_stf", (2, Cn), torch.float64, dev).zero_() if anomalies else None,
+                   "status": self._buf(None, "ce_status", (2,), torch.int64, dev).zero_(), "plan": plan,
+                   **{k: None for k in ("events", "event_days", "duration_max", "sum", "vmax", "invalid")},
+                   **self._upload_tables(tabs)}
+            if not second:
+                for k in ("events", "event_days", "duration_max") + (("vmax", "invalid") if anomalies else ()):
+                    acc[k] = self._buf(None, "ce_" + k, (G, Cn), torch.int32, dev).zero_()
+                if anomalies:
+                    acc["sum"] = self._buf(None, "ce_sum", (G, Cn), torch.float64, dev).zero_()
+        self._window_check("cell_events", acc, plan, ("grp",), t0, Tb, Cn)
+        if second and (int(records["off"].numel()) != Cn + 1 or ("sum" in records) != anomalies):
+            raise ProcessingError("cell_events: the record buffers were planned for another call",
+                                  details=f"{int(records['off'].numel()) - 1} cells there, {Cn} here")
+        rec = records or {}
+        self.call("marex_cell_events_u8", x, anom, t0, Tb, Cn, D, gap, int(bool(finish)), acc["tabs"]["grp"], G,
+                  acc["state_i32"], acc["state_f64"], acc["events"], acc["event_days"], acc["duration_max"], acc["sum"],
+                  acc["vmax"], acc["invalid"], mask, rec.get("off"), rec.get("start"), rec.get("end"), rec.get("vmax"),
+                  rec.get("tmax"), rec.get("sum"), rec.get("invalid"), acc["status"])
+        out: Dict[str, object] = {"acc": acc}
+        if not finish:
+            return out
+        bad, over = (int(v) for v in acc["status"].cpu().numpy())
+        if bad:
+            raise ProcessingError(f"cell_events: {bad} events start under a step label outside its range",
+                                  details=f"grp must hold 0 .. {G - 1}; the events were counted, nothing was written out of range")
+        if over:
+            raise ProcessingError(f"cell_events: {over} events found no room in the records of their cell",
+                                  details="the record offsets do not belong to this field; nothing was written out of range")
+        host = self._host
+        if second:
+            n = records["n"]
+            r = {"off": records["off"].cpu().numpy(), "start": host(records["start"][:n], np.int32),
+                 "end": host(records["end"][:n], np.int32)}
+            if anomalies:
+                key = host(records["vmax"][:n], np.uint32)
+                r.update(vmax=np.where(key != 0, key_float(key), np.float32(np.nan)),
+                         tmax=np.where(key != 0, host(records["tmax"][:n], np.int32), np.int32(-1)),
+                         sum=host(records["sum"][:n], np.float64), invalid=host(records["invalid"][:n], np.uint32))
+            out.update(rec=r, records=records)
+            return out
+        out.update(events=host(acc["events"], np.uint32), event_days=host(acc["event_days"], np.uint32),
+                   duration_max=host(acc["duration_max"], np.uint32))
+        if anomalies:
+            key = host(acc["vmax"], np.uint32)
+            out.update(sum=host(acc["sum"], np.float64), vmax=np.where(key != 0, key_float(key), np.float32(np.nan)),
+                       invalid=host(acc["invalid"], np.uint32))
+        return out
+
     def event_rename(self, ids: torch.Tensor, ny: int, nx: int, lut, ev_tmin, ev_tmax,
                      weights: Optional[torch.Tensor] = None) -> Dict[str, np.ndarray]:
         """The device pass of cluster_rename_objects_and_props on a grid (track.py:2897-2976, 3140-3247), in one kernel and
