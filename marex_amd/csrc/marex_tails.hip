@@ -325,6 +325,52 @@ __device__ __forceinline__ void tl_bump_chunk(const uint4& ch, int n, int B0, in
 #undef MAREX_BUMP_LO
 #undef MAREX_BUMP_HI
 
+// The lean instance's form of the same loop: no count in front of it.  A key is inside the band <=> its bin + 1 > B0, and the bin
+// has to be extracted for the level anyway, so the loop compares the bin itself, counts the keys it takes (n += 1 per key: the
+// caller needs the sum for level 0) and hands back the lanes whose eighth key was still inside (the next chunk is theirs).
+// The counted form spends a dozen vector instructions per chunk before its first key and 9 per key; this one spends 11 per key
+// and nothing in front -- and on the headline field a wave takes fewer than two keys per list (LDS instruction counter).
+// pm: the lanes that may take keys at all (lanes with samples; for a deeper chunk the full lanes of the chunk before).
+#define MAREX_SCAN_KEY(ext)                                                                                           \
+    ext "\n\tv_cmpx_lt_u32_e32 vcc, %[b0], %[t]\n\ts_cbranch_execz 1f\n\t"
+#define MAREX_SCAN_ADD(one)                                                                                           \
+    "v_subrev_u32_e32 %[t], %[b0], %[t]\n\tv_min_i32_e32 %[t], %[hi], %[t]\n\tv_and_b32_e32 %[a], -2, %[t]\n\t"         \
+    "v_and_b32_e32 %[t], 1, %[t]\n\tv_lshl_add_u32 %[a], %[a], 1, %[col]\n\tv_mad_i32_i24 %[t], %[t], %[mul], " one "\n\t" \
+    "ds_add_u32 %[a], %[t]\n\tv_add_u32_e32 %[n], 1, %[n]\n\t"
+#define MAREX_SCAN_LO(w) "v_bfe_u32 %[t], %[" #w "], 7, 9"
+#define MAREX_SCAN_HI(w) "v_lshrrev_b32_e32 %[t], 23, %[" #w "]"
+template <int SGN>
+__device__ __forceinline__ unsigned long long tl_scan_chunk(const uint4& ch, unsigned long long pm, int& n, int B0, int BWp1,
+                                                            unsigned col_lds) {
+    unsigned t, a;
+    unsigned long long sv, full;
+    const int mul = SGN > 0 ? 65535 : -65535;
+#define MAREX_SCAN_ALL(one)                                                                                           \
+    "s_mov_b64 %[sv], exec\n\ts_mov_b64 %[full], 0\n\ts_and_b64 exec, exec, %[pm]\n\ts_cbranch_execz 1f\n\t"          \
+    MAREX_SCAN_KEY(MAREX_SCAN_LO(x)) MAREX_SCAN_ADD(one) MAREX_SCAN_KEY(MAREX_SCAN_HI(x)) MAREX_SCAN_ADD(one)         \
+    MAREX_SCAN_KEY(MAREX_SCAN_LO(y)) MAREX_SCAN_ADD(one) MAREX_SCAN_KEY(MAREX_SCAN_HI(y)) MAREX_SCAN_ADD(one)         \
+    MAREX_SCAN_KEY(MAREX_SCAN_LO(z)) MAREX_SCAN_ADD(one) MAREX_SCAN_KEY(MAREX_SCAN_HI(z)) MAREX_SCAN_ADD(one)         \
+    MAREX_SCAN_KEY(MAREX_SCAN_LO(w)) MAREX_SCAN_ADD(one) MAREX_SCAN_KEY(MAREX_SCAN_HI(w))                             \
+    "s_mov_b64 %[full], exec\n\t" MAREX_SCAN_ADD(one)                                                                \
+    "1:\n\ts_mov_b64 exec, %[sv]"
+    if (SGN > 0)
+        asm volatile(MAREX_SCAN_ALL("1")
+                     : [t] "=&v"(t), [a] "=&v"(a), [sv] "=&s"(sv), [full] "=&s"(full), [n] "+v"(n)
+                     : [pm] "s"(pm), [x] "v"(ch.x), [y] "v"(ch.y), [z] "v"(ch.z), [w] "v"(ch.w), [b0] "s"(B0), [hi] "s"(BWp1), [col] "v"(col_lds), [mul] "s"(mul)
+                     : "vcc", "memory");
+    else
+        asm volatile(MAREX_SCAN_ALL("-1")
+                     : [t] "=&v"(t), [a] "=&v"(a), [sv] "=&s"(sv), [full] "=&s"(full), [n] "+v"(n)
+                     : [pm] "s"(pm), [x] "v"(ch.x), [y] "v"(ch.y), [z] "v"(ch.z), [w] "v"(ch.w), [b0] "s"(B0), [hi] "s"(BWp1), [col] "v"(col_lds), [mul] "s"(mul)
+                     : "vcc", "memory");
+#undef MAREX_SCAN_ALL
+    return full;
+}
+#undef MAREX_SCAN_KEY
+#undef MAREX_SCAN_ADD
+#undef MAREX_SCAN_LO
+#undef MAREX_SCAN_HI
+
 #define TT_LS 34       // dwords per lane column (68 uint16 levels; stride 34 keeps 8-byte alignment, conflict-free b64)
 #ifndef TT_BW
 #define TT_BW 64       // bins per band (experiments: -DTT_BW=48 -DTT_STEP=40; must stay <= 64: the column has 68 levels)
@@ -341,17 +387,25 @@ struct TailBucket {
     uint4 c0[NPERT < TT_NPF ? NPERT : TT_NPF];
     unsigned aux;  // count | overflow flag
     int d;         // dayofyear index 0..365
+    const uint4* base;  // lean instance: the bucket's first chunk row (wave-uniform: SGPRs), carried instead of d
 };
 
-template <int P, int TC, int NT, int NPERT, int TR_ = NT / TC>
+// LN, LC > 0: the LEAN instance for lists of exactly LN x LC chunks per bucket (option THR_LEAN, the launcher below) -- the same
+// walk and the same arithmetic with the list geometry as compile-time constants, running bases for the entering and the leaving
+// bucket instead of a modulo and a 64-bit product per use, and the key loop that needs no count in front of it (tl_scan_chunk).
+// LN = 0: list geometry from the arguments.
+template <int P, int TC, int NT, int NPERT, int TR_ = NT / TC, int LN = 0, int LC = 0>
 __global__ void __launch_bounds__(NT, NT == 256 ? 4 : (NT == 512 ? 2 : 1))
-k_thr_tails(const uint4* __restrict__ lists, const unsigned* __restrict__ aux, int NPER, int nch, const float* __restrict__ anom,
+k_thr_tails(const uint4* __restrict__ lists, const unsigned* __restrict__ aux, int NPER_rt, int nch_rt, const float* __restrict__ anom,
             long C, int ny, int nx, int row0, int row1, int tiles_x, int Dd, const float* __restrict__ centres, int nb, double q,
             int wd, float lower_bound, float upper_bound, float* __restrict__ thr, marex_thr_stats* __restrict__ stats,
             unsigned long long* __restrict__ dbg, int pass_limit) {
     constexpr int TR = TR_;
     constexpr int NCELL = TR * TC;
     constexpr int NPF = NPERT < TT_NPF ? NPERT : TT_NPF;
+    constexpr bool LEAN = LN > 0;
+    static_assert(!LEAN || (LN >= NPF && LN <= 2 * NPERT && LC >= 2 && LC <= 4), "lean list geometry");
+    const int NPER = LEAN ? LN : NPER_rt, nch = LEAN ? LC : nch_rt;
     static_assert(NCELL <= NT && NT - NCELL < 64, "tile does not match the thread count");
     constexpr int OR = TR - 2 * P, OC = TC - 2 * P;
     __shared__ unsigned lev[NT * TT_LS];
@@ -416,6 +470,18 @@ k_thr_tails(const uint4* __restrict__ lists, const unsigned* __restrict__ aux, i
         for (int p = 0; p < NPF; ++p)
             b.c0[p] = (p < NPER) ? tl_load_chunk(r, voff, (unsigned)(nch * p) * chunk_row) : make_uint4(0, 0, 0, 0);
         b.aux = aux[(size_t)d0 * C + cell];
+        b.base = lists + (size_t)d0 * day_stride;
+        return b;
+    };
+    // the same from running bases (lean walk): no modulo, no product
+    auto load_bucket_at = [&](const uint4* lbase, const unsigned* abase) {
+        TailBucket<NPERT> b;
+        b.d = 0;
+        b.base = lbase;
+        const tl_rsrc_t r = tl_make_rsrc(lbase);
+#pragma unroll
+        for (int p = 0; p < NPF; ++p) b.c0[p] = tl_load_chunk(r, voff, (unsigned)(nch * p) * chunk_row);
+        b.aux = abase[cell];
         return b;
     };
     // +-1 on level k >= 1 of the lane's packed column
@@ -449,7 +515,7 @@ k_thr_tails(const uint4* __restrict__ lists, const unsigned* __restrict__ aux, i
         // in the band <=> bin >= B0 <=> key >= (B0 + 1) << 7 <=> key > lim
         const unsigned lim = ((unsigned)(B0 + 1) << TAIL_POS_BITS) - 1u;
         const unsigned lim_rep = lim | (lim << 16);
-        const tl_rsrc_t r = tl_make_rsrc(lists + (size_t)b.d * day_stride);
+        const tl_rsrc_t r = tl_make_rsrc(LEAN ? b.base : lists + (size_t)b.d * day_stride);
         int n_in = 0;
         // one list: count the keys of its first chunk that lie inside the band, bump them, go on to the next chunk while
         // a whole chunk was inside
@@ -470,19 +536,33 @@ k_thr_tails(const uint4* __restrict__ lists, const unsigned* __restrict__ aux, i
                 full = nj == 8;
             }
         };
+        // lean: the scanning loop (tl_scan_chunk) finds the keys inside the band itself; lanes without samples take none
+        const unsigned long long live = LEAN ? __builtin_amdgcn_ballot_w64(cnt > 0) : 0ull;
+        auto scan_list = [&](const uint4& ch, int p) {
+            unsigned long long f = sgn > 0 ? tl_scan_chunk<1>(ch, live, n_in, B0, BW + 1, col_lds) : tl_scan_chunk<-1>(ch, live, n_in, B0, BW + 1, col_lds);
+#pragma unroll
+            for (int jj = 1; jj < LC; ++jj) {
+                if (f == 0) break;
+                const uint4 cj = tl_load_chunk(r, voff, (unsigned)(nch * p + jj) * chunk_row);
+                f = sgn > 0 ? tl_scan_chunk<1>(cj, f, n_in, B0, BW + 1, col_lds) : tl_scan_chunk<-1>(cj, f, n_in, B0, BW + 1, col_lds);
+            }
+        };
+        auto a_list = [&](const uint4& ch, int p) {
+            if (LEAN) scan_list(ch, p); else one_list(ch, p);
+        };
 #pragma unroll
         for (int p = 0; p < NPF; ++p)
-            if (p < NPER) one_list(b.c0[p], p);
+            if (p < NPER) a_list(b.c0[p], p);
         // the lists that were not prefetched: two first chunks in flight at a time
 #pragma nounroll
         for (int p = NPF; p < NPER; p += 2) {  // uniform trip count
             const uint4 e0 = tl_load_chunk(r, voff, (unsigned)(nch * p) * chunk_row);
             const uint4 e1 = p + 1 < NPER ? tl_load_chunk(r, voff, (unsigned)(nch * (p + 1)) * chunk_row) : make_uint4(0, 0, 0, 0);
-            one_list(e0, p);
-            if (p + 1 < NPER) one_list(e1, p + 1);
+            a_list(e0, p);
+            if (p + 1 < NPER) a_list(e1, p + 1);
         }
         const int below = cnt - n_in;  // everything under the band
-        if (below > 0) __hip_atomic_fetch_add((lds_u32*)(size_t)col_lds, (unsigned)(sgn > 0 ? below : -below), __ATOMIC_RELAXED,
+        if (LEAN || below > 0) __hip_atomic_fetch_add((lds_u32*)(size_t)col_lds, (unsigned)(sgn > 0 ? below : -below), __ATOMIC_RELAXED,
                                               __HIP_MEMORY_SCOPE_WORKGROUP);
         mytot += sgn > 0 ? cnt : -cnt;
     };
@@ -676,6 +756,13 @@ k_thr_tails(const uint4* __restrict__ lists, const unsigned* __restrict__ aux, i
     TailBucket<NPERT> pin, pout;
     pin.d = pout.d = 0;
     pin.aux = pout.aux = 0;
+    pin.base = pout.base = lists;
+    // lean walk: dayofyear and bases of the bucket that entered / left last (day d_begin: d_begin + pd entered, d_begin - pd - 1 left)
+    int in_d = wrap(d_begin + pd), out_d = wrap(d_begin - pd - 1);
+    const uint4* in_l = lists + (size_t)in_d * day_stride;
+    const uint4* out_l = lists + (size_t)out_d * day_stride;
+    const unsigned* in_a = aux + (size_t)in_d * C;
+    const unsigned* out_a = aux + (size_t)out_d * C;
 #pragma unroll
     for (int p = 0; p < NPF; ++p) pin.c0[p] = pout.c0[p] = make_uint4(0, 0, 0, 0);
 #ifdef MAREX_STAMPS
@@ -700,7 +787,19 @@ k_thr_tails(const uint4* __restrict__ lists, const unsigned* __restrict__ aux, i
             apply_bucket(pout, -1);
         }
         tot_s[ci] = prefix();
-        if (dd + 1 < ndays) {
+        if (LEAN) {
+            // the entering and the leaving bucket of the next day: one step of two running bases, one compare each for the year's end
+            in_d = in_d + 1 == NDOY ? 0 : in_d + 1;
+            in_l = in_d == 0 ? lists : in_l + day_stride;
+            in_a = in_d == 0 ? aux : in_a + C;
+            out_d = out_d + 1 == NDOY ? 0 : out_d + 1;
+            out_l = out_d == 0 ? lists : out_l + day_stride;
+            out_a = out_d == 0 ? aux : out_a + C;
+            if (dd + 1 < ndays) {
+                pin = load_bucket_at(in_l, in_a);
+                pout = load_bucket_at(out_l, out_a);
+            }
+        } else if (dd + 1 < ndays) {
             pin = load_bucket(wrap(d + 1 + pd));
             pout = load_bucket(wrap(d - pd));
         }
@@ -1156,9 +1255,17 @@ extern "C" int marex_hobday_thresholds_tails_f32(marex_ctx* ctx, const void* lis
         else /* two lists prefetched across the barrier, the others loaded at use */                                                 \
             hipLaunchKernelGGL((k_thr_tails<PP, TCC, NTT, 3, ##__VA_ARGS__>), grid, dim3(NTT), lds_pad, ctx->stream, MAREX_TT_ARGS); \
     } while (0)
+    // the lean instance (k_thr_tails, LN x LC): 6 lists of 2 chunks -- the lists the anomaly kernel emits for buckets of 76..90
+    // samples, a century of days -- on the 1024-thread tiles of a 5 x 5 pooling window; THR_LEAN=0 keeps the general body, which
+    // also takes every other geometry
+    const bool lean = NPER == 6 && nch == 2 && big && p == 2 && ctx_opt(ctx, "THR_LEAN", 1) != 0;
     {
         LaunchTimer lt(ctx, MAREX_K_THRESHOLDS);
-        if (TR == 1)
+        if (lean && tall)
+            hipLaunchKernelGGL((k_thr_tails<2, 30, 1024, 3, 34, 6, 2>), grid, dim3(1024), lds_pad, ctx->stream, MAREX_TT_ARGS);
+        else if (lean)
+            hipLaunchKernelGGL((k_thr_tails<2, 32, 1024, 3, 32, 6, 2>), grid, dim3(1024), lds_pad, ctx->stream, MAREX_TT_ARGS);
+        else if (TR == 1)
             MAREX_TT_LAUNCH(0, 256, 256);
         else if (half)
             MAREX_TT_LAUNCH(2, 32, 512, 16);

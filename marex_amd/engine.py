@@ -411,6 +411,8 @@ class HotPath:
 
     def hobday_thresholds_tails(self, tl: dict, anom: torch.Tensor, dcal: DeviceCalendar, bins: BinTable, q: float, wd: int,
                                 ws: int, ny: int, nx: int, rows: Optional[tuple] = None, wsp: Optional[dict] = None):
+        """Day-of-year thresholds from the key lists.  Option THR_LEAN (default 1): lists of 6 x 2 chunks on 1024-thread tiles
+        take the lean instance of the kernel, 0 = the general body for every geometry (same bits)."""
         T_out, Cn = anom.shape
         row0, row1 = rows if rows is not None else (0, max(ny, 1))
         thr, stats = self._threshold_buffers(wsp, Cn)
