@@ -99,8 +99,10 @@ int marex_sync(marex_ctx* ctx);
  * these calls change it -- nothing reads the environment at launch time.  name == NULL clears every option. */
 int marex_set_option(marex_ctx* ctx, const char* name, int value);
 int marex_clear_option(marex_ctx* ctx, const char* name);
-/* Event counters of the tail kernels (host uint64[8], synchronises the stream): [0] column rebuilds, [1] unused, [2] extra passes for stragglers, [3] days walked (per tile and block),
+/* Event counters of the tail kernels (host uint64[8], synchronises the stream): [0] column rebuilds, [1] probes the per-cell and pooled threshold kernels recounted from every chunk,
+ * [2] extra passes for stragglers, [3] days walked (per tile and block),
  * [4] (4-cell, dayofyear) groups the mask kernel decided on the anomalies, [5..7] phase timers of -DMAREX_STAMPS builds.
+ * The pooled threshold kernel adds per workgroup: [0] one when its first chunks waited in LDS, [2] one, [3] its days.
  * reset != 0 zeroes them afterwards. */
 int marex_debug_counters(marex_ctx* ctx, uint64_t* out8, int reset);
 
@@ -226,6 +228,20 @@ int marex_hobday_thresholds_tails_f32(marex_ctx* ctx, const void* lists, const u
                                       int64_t T_out, int64_t C, int ny, int nx, int max_bucket, const float* centres, int nb,
                                       double q, int wd, int ws, float lower_bound, float upper_bound, int row0, int row1,
                                       float* thr_doy_major, marex_thr_stats* stats);
+
+/* Day-of-year thresholds from tails, pooled over mesh neighbour rings (no reference counterpart: the reference does not pool
+ * on unstructured meshes).  The histogram of cell c is the sum of the histograms of pool[0..K)[c]: `pool` is int32 [K][C] on the
+ * device, member-major, row 0 = the cell itself, -1 = empty slot, no duplicates, K <= 13 (two rings of at most three neighbours).
+ * Everything after the sum is marex_hobday_thresholds_tails_f32 with ws = 1: count-interpolated quantile, NaN where the cell's OWN
+ * first kept anomaly is NaN, clamp, statistics.  Thresholds are written for the cells [c0, c1) only; members may lie anywhere in
+ * [0, C).  The entries of the rows c0..c1 are range-checked on the host before the launch (one device-to-host copy of the table):
+ * -1 for an index outside -1..C-1 or a row 0 that is not the cell.  -4: nb > 511, max_bucket > 128, max_bucket*wd*K > 65535 or
+ * C > 2^24.  Options: THR_POOL_RING = 1 / 0 (the first chunks of the window's lists wait in LDS / are read from global memory at
+ * every probe; default: in LDS whenever the ring fits), THR_POOL_BLOCKS = day blocks per 64 cells.  Same bits on either path. */
+int marex_hobday_thresholds_pool_f32(marex_ctx* ctx, const void* lists, const uint32_t* aux, int list_rows, const float* anom,
+                                     int64_t T_out, int64_t C, int max_bucket, const int32_t* pool, int K, int64_t c0, int64_t c1,
+                                     const float* centres, int nb, double q, int wd, float lower_bound, float upper_bound,
+                                     float* thr_doy_major, marex_thr_stats* stats);
 
 /* The extreme mask from tails: same result as marex_mask_ge_doy_f32 (detect.py:2003-2004, 833-835) without reading the
  * anomalies, except for samples in the threshold's own bin and for buckets holding more than two values beyond the edge table

@@ -3,6 +3,10 @@
 Public names mirror the reference's re-exports for this path (marEx/__init__.py:36-42, 45-58).
 Importing the package never touches the GPU; the HIP extension is loaded on the first compute call and
 its absence is an error (no CPU fallback).
+
+Beyond the reference: ``preprocess_data`` and ``identify_extremes`` take ``neighbour_rings_hobday=1 | 2`` with ``neighbours``
+on unstructured meshes -- day-of-year thresholds pooled over the cell and one or two rings of its listed neighbours, the mesh
+counterpart of ``window_spatial_hobday``.
 """
 from .detect import (
     compute_normalised_anomaly,

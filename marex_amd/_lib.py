@@ -84,6 +84,9 @@ PROTOTYPES = {
         _i32,
         [_p, _p, _p, _i32, _p, _i64, _i64, _i32, _i32, _i32, _p, _i32, _f64, _i32, _i32, _f32, _f32, _i32, _i32, _p, _p],
     ),
+    "marex_hobday_thresholds_pool_f32": (
+        _i32, [_p, _p, _p, _i32, _p, _i64, _i64, _i32, _p, _i32, _i64, _i64, _p, _i32, _f64, _i32, _f32, _f32, _p, _p],
+    ),
     "marex_mask_ge_doy_tails_f32": (_i32, [_p, _p, _p, _i32, _i32, _p, _p, _i32, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _p]),
     "marex_blosc_decompress_h": (_i32, [_p, _i64, _p, _i64, _p]),
     "marex_zstd_decompress_h": (_i32, [_p, _i64, _p, _i64, _p]),

@@ -1291,6 +1291,315 @@ extern "C" int marex_hobday_thresholds_tails_f32(marex_ctx* ctx, const void* lis
 }
 
 // ------------------------------------------------------------------------------------------------
+// K_T pooled over mesh neighbour rings: the histogram of a cell is the sum of the histograms of the members of its pool (the
+// cell itself, its listed neighbours, their listed neighbours: at most 13 cells), pool[m][c] = member m of cell c or -1.
+// The scheme is k_thr_cells': a lane owns one cell and walks a block of days, the quantile bin of a day is found by bisection on
+// the bin index, a probe counts the keys at or above its first key in the FIRST chunks of the window's lists (a lower bound).  The
+// bound is the exact count unless some list's last kept key is such a key too ("saturated"); a probe the bound does not decide is
+// completed exactly from every chunk of the saturated lists alone -- with hundreds of lists in a window some list is saturated at
+// most probes near the quantile, so a recount of the whole window (k_thr_cells) would run every day.  The window holds wd * K * NPER lists instead of
+// wd * NPER and every member's lists are gathered through its index; totals slide with the window from the members' aux counts.
+//   RING = true:  the first chunks wait in a per-wave LDS ring, 16 bytes per list and lane (1 KiB per list and wave)
+//   RING = false: no ring, every probe reads the first chunks from global memory (any window, whatever its size)
+// (A ring of the 4 largest keys per list -- half the LDS, twice the waves -- measured slower on every window tried: lists are
+// saturated from their 4th key on, and completing the counts costs more than the occupancy gives.)
+// The member indices of a lane sit in LDS too (K ints per lane): a lane beyond c1 or on land gets -1 everywhere, and a member of
+// -1 is skipped before any address is made from it.  Same bits on every path.
+// ------------------------------------------------------------------------------------------------
+template <bool RING>
+__global__ void __launch_bounds__(64)
+k_thr_pool(const uint4* __restrict__ lists, const unsigned* __restrict__ aux, int NPER, int nch, const float* __restrict__ anom,
+           long C, long c0, long c1, int nblk, const int* __restrict__ pool, int K, const float* __restrict__ centres, int nb,
+           double q, int wd, float lower_bound, float upper_bound, float* __restrict__ thr, marex_thr_stats* __restrict__ stats,
+           unsigned long long* __restrict__ dbg) {
+    extern __shared__ uint4 pool_smem[];  // [K][64] member indices, then the ring [wd][K][NPER][64] of first chunks (RING)
+    const int lane = (int)threadIdx.x;
+    const long cell = c0 + (long)blockIdx.x * 64 + lane;
+    const bool valid = cell < c1;
+    const int d_begin = (int)blockIdx.y * NDOY / nblk, d_end = ((int)blockIdx.y + 1) * NDOY / nblk;
+    const bool land = valid ? !(anom[cell] == anom[cell]) : true;  // first kept anomaly row (detect.py:2704)
+    if (__builtin_amdgcn_ballot_w64(!land) == 0) {
+        if (valid)
+            for (int d = d_begin; d < d_end; ++d) thr[(size_t)d * C + cell] = nan_f();
+        return;
+    }
+    int* mem = reinterpret_cast<int*>(pool_smem) + lane;  // + m * 64
+    for (int m = 0; m < K; ++m) mem[m * 64] = land ? -1 : pool[(size_t)m * C + cell];
+    uint4* ring = pool_smem + K * 16 + lane;  // + slot * 64
+    const int pd = wd / 2, per_day = K * NPER, nslot = (wd * per_day + 3) & ~3;  // the ring is padded to whole groups of four slots
+    if (RING)
+        for (int k = wd * per_day; k < nslot; ++k) ring[k * 64] = make_uint4(0, 0, 0, 0);
+    const unsigned chunk_row = (unsigned)C * 16u;
+    const size_t day_stride = (size_t)NPER * nch * (size_t)C;
+    auto wrap = [](int d) { return d < 0 ? d + NDOY : (d >= NDOY ? d - NDOY : d); };
+    auto cnt_of = [&](int day) {  // samples of the members' buckets of `day`
+        int n = 0;
+        for (int m = 0; m < K; ++m) {
+            const int j = mem[m * 64];
+            if (j >= 0) n += (int)(aux[(size_t)day * C + j] & 0x3FFu);
+        }
+        return n;
+    };
+    auto global_first = [&](int day, int j, int p) {  // first chunk of list p of bucket (day, member j); j >= 0
+        return tl_load_chunk(tl_make_rsrc(lists + (size_t)day * day_stride), (unsigned)j * 16u, (unsigned)(nch * p) * chunk_row);
+    };
+    auto load_day = [&](int day, int k) {  // bucket `day` of every member into ring position k % wd
+        if (!RING) return;
+        for (int m = 0; m < K; ++m) {
+            const int j = mem[m * 64];
+            for (int p = 0; p < NPER; ++p) {
+                const uint4 ch = j >= 0 ? global_first(day, j, p) : make_uint4(0, 0, 0, 0);
+                ring[((k % wd) * per_day + m * NPER + p) * 64] = ch;
+            }
+        }
+    };
+    // first chunk of list (m, p) of the i-th bucket of the window of day d; the order of the buckets does not matter to a
+    // count, so the ring is read by position
+    auto first_chunk = [&](int d, int i, int m, int p) {
+        if (RING) return ring[(i * per_day + m * NPER + p) * 64];
+        const int j = mem[m * 64];
+        return j >= 0 ? global_first(wrap(d - pd + i), j, p) : make_uint4(0, 0, 0, 0);
+    };
+    int tot = 0;
+    for (int o = 0; o < wd; ++o) {
+        const int day = wrap(d_begin - pd + o);
+        load_day(day, o);
+        tot += cnt_of(day);
+    }
+    // lower bound of #(keys >= first key of bin b) from the first chunks; sat = the lists whose LAST kept key is such a key too:
+    // only they can hold more of them behind what is kept (a list is sorted), so sat == 0 makes the bound the exact count
+    auto count_first = [&](int d, int b, int& sat) {
+        const unsigned lim = ((unsigned)(b + 1) << TAIL_POS_BITS) - 1u, lim_rep = lim | (lim << 16);
+        unsigned acc0 = 0, acc1 = 0, accl = 0;  // accl: the register that ends with the last kept key
+        if (RING) {
+            for (int k = 0; k < nslot; k += 4) {  // four lists in flight per trip
+                const uint4 c[4] = {ring[k * 64], ring[(k + 1) * 64], ring[(k + 2) * 64], ring[(k + 3) * 64]};
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    acc0 += pk_min1_u16(pk_sub_sat_u16(c[u].x, lim_rep)) + pk_min1_u16(pk_sub_sat_u16(c[u].z, lim_rep));
+                    acc1 += pk_min1_u16(pk_sub_sat_u16(c[u].y, lim_rep));
+                    accl += pk_min1_u16(pk_sub_sat_u16(c[u].w, lim_rep));
+                }
+            }
+        } else
+        for (int i = 0; i < wd; ++i)
+            for (int m = 0; m < K; ++m)
+                for (int p = 0; p < NPER; ++p) {
+                    const uint4 c = first_chunk(d, i, m, p);
+                    acc0 += pk_min1_u16(pk_sub_sat_u16(c.x, lim_rep)) + pk_min1_u16(pk_sub_sat_u16(c.z, lim_rep));
+                    acc1 += pk_min1_u16(pk_sub_sat_u16(c.y, lim_rep));
+                    accl += pk_min1_u16(pk_sub_sat_u16(c.w, lim_rep));
+                }
+        sat = (int)(accl >> 16);
+        const unsigned acc = acc0 + acc1 + accl;  // the halves together count at most the window's samples: max_bucket * wd * K <= 65535
+        return (int)((acc & 0xFFFFu) + (acc >> 16));
+    };
+    // what count_first misses: the keys >= first key of bin b that the saturated lists hold behind their kept keys, counted from
+    // every chunk of those lists (lanes with `want` only; the others walk along)
+    auto count_behind = [&](int d, int b, bool want) {
+        const unsigned lim = ((unsigned)(b + 1) << TAIL_POS_BITS) - 1u, lim_rep = lim | (lim << 16);
+        const int s0 = (d - d_begin) % wd;  // ring position of the first bucket of the window
+        int n = 0;
+        for (int i = 0; i < wd; ++i) {
+            const int o = RING ? (i - s0 + wd) % wd : i;  // ring position i holds the o-th bucket of the window
+            const tl_rsrc_t r = tl_make_rsrc(lists + (size_t)wrap(d - pd + o) * day_stride);
+            for (int m = 0; m < K; ++m) {
+                const int j = mem[m * 64];
+                if (j < 0 || !want) continue;
+                for (int p = 0; p < NPER; ++p) {
+                    const uint4 c = first_chunk(d, i, m, p);
+                    if ((c.w >> 16) <= lim) continue;  // its 8th key is no such key: nothing behind the first chunk
+                    for (int jj = 1; jj < nch; ++jj) n += tl_count_above(tl_load_chunk(r, (unsigned)j * 16u, (unsigned)(nch * p + jj) * chunk_row), lim_rep);
+                }
+            }
+        }
+        return n;
+    };
+    unsigned kmin = 0xFFFFFFFFu, kmax = 0u, nlow = 0u, nhigh = 0u;
+    unsigned long long n_exact = 0;
+    for (int d = d_begin; d < d_end; ++d) {
+        if (d > d_begin) {  // the window moves on: bucket d + pd takes the ring position of bucket d - pd - 1
+            const int din = wrap(d + pd), dout = wrap(d - pd - 1);
+            load_day(din, d - d_begin - 1);
+            tot += cnt_of(din) - cnt_of(dout);
+        }
+        // khead = largest key of the window; ktail = smallest largest-key of a non-empty list (k_thr_cells)
+        unsigned khead = 0, ktail = 0xFFFFu;
+        int nlists = 0;
+        auto see_head = [&](unsigned first_pair) {
+            const unsigned head = first_pair & 0xFFFFu;
+            khead = head > khead ? head : khead;
+            ktail = (head != 0u && head < ktail) ? head : ktail;
+            nlists += head != 0u ? 1 : 0;
+        };
+        if (RING) {
+            for (int k = 0; k < nslot; k += 4) {
+                const unsigned h[4] = {ring[k * 64].x, ring[(k + 1) * 64].x, ring[(k + 2) * 64].x, ring[(k + 3) * 64].x};
+#pragma unroll
+                for (int u = 0; u < 4; ++u) see_head(h[u]);
+            }
+        } else
+        for (int i = 0; i < wd; ++i)
+            for (int m = 0; m < K; ++m)
+                for (int p = 0; p < NPER; ++p) see_head(first_chunk(d, i, m, p).x);
+        float t32 = nan_f();
+        if (tot > 0) {
+            const double qpos = q * (double)tot;
+            // f(b) = cs[b] <= qpos is true below iu and false from iu on; answer in (lo, hi] (k_thr_cells)
+            int lo = -1, hi = nb - 1, n_lo = tot, n_hi = 0;
+            if (khead != 0u && (double)tot > qpos) {
+                const int bh = (int)(khead >> TAIL_POS_BITS) - 1;
+                hi = bh < hi ? bh : hi;
+            }
+            bool lo_exact = true;
+            if (nlists > 0 && (double)(tot - nlists) <= qpos) {
+                const int bt = (int)(ktail >> TAIL_POS_BITS) - 2;
+                if (bt > lo && bt < hi) {
+                    lo = bt;
+                    n_lo = nlists;
+                    lo_exact = false;
+                }
+            }
+            while (__builtin_amdgcn_ballot_w64(hi - lo > 1) != 0) {
+                const bool go = hi - lo > 1;
+                const int mid = go ? (lo + hi) >> 1 : hi;
+                int sat;
+                int n = count_first(d, mid + 1, sat);
+                bool exact = sat == 0;
+                bool f = (double)(tot - n) <= qpos;
+                const bool undecided = go && !f && !exact;  // the bound does not decide: count behind the saturated lists
+                if (__builtin_amdgcn_ballot_w64(undecided) != 0) {
+                    const int more = count_behind(d, mid + 1, undecided);
+                    if (undecided) {
+                        n += more;
+                        exact = true;
+                        f = (double)(tot - n) <= qpos;
+                        ++n_exact;
+                    }
+                }
+                if (go) {
+                    if (f) {
+                        lo = mid;
+                        n_lo = n;
+                        lo_exact = exact;
+                    } else {
+                        hi = mid;
+                        n_hi = n;
+                    }
+                }
+            }
+            const int iu = hi;
+            const bool redo = iu > 0 && !lo_exact;
+            if (__builtin_amdgcn_ballot_w64(redo) != 0) {
+                int sat;
+                const int ne = count_first(d, iu, sat) + count_behind(d, iu, redo);
+                if (redo) {
+                    n_lo = ne;
+                    ++n_exact;
+                }
+            }
+            const int il = iu > 0 ? iu - 1 : 0;
+            const int cs_iu = tot - n_hi, cs_il = iu > 0 ? tot - n_lo : cs_iu;
+            const int diff = cs_iu - cs_il;
+            const double frac = diff > 0 ? (qpos - (double)cs_il) / (double)diff : 0.5;
+            const float dc = centres[iu] - centres[il];
+            const double prod = frac * (double)dc;
+            t32 = (float)((double)centres[il] + prod);
+            if (iu == 0) t32 = centres[0];
+            if (!land) {
+                const unsigned key = ordered_key(t32);
+                kmin = key < kmin ? key : kmin;
+                kmax = key > kmax ? key : kmax;
+                if (t32 > upper_bound) ++nhigh;
+                if (t32 < lower_bound) ++nlow;
+            }
+            if (t32 < lower_bound) t32 = lower_bound;
+        }
+        if (valid) thr[(size_t)d * C + cell] = land ? nan_f() : t32;
+    }
+    for (int sft = 32; sft > 0; sft >>= 1) {
+        const unsigned a = __shfl_down(kmin, sft, 64), b = __shfl_down(kmax, sft, 64);
+        kmin = a < kmin ? a : kmin;
+        kmax = b > kmax ? b : kmax;
+        nlow += __shfl_down(nlow, sft, 64);
+        nhigh += __shfl_down(nhigh, sft, 64);
+        n_exact += __shfl_down(n_exact, sft, 64);
+    }
+    if (lane == 0) {
+        if (kmin != 0xFFFFFFFFu) atomicMin(&stats->min_key, kmin);
+        if (kmax != 0u) atomicMax(&stats->max_key, kmax);
+        if (nlow) atomicAdd(&stats->n_too_low, nlow);
+        if (nhigh) atomicAdd(&stats->n_too_high, nhigh);
+        if (dbg) {
+            if (n_exact) atomicAdd(&dbg[1], n_exact);
+            atomicAdd(&dbg[0], RING ? 1ull : 0ull);      // workgroups with the first chunks in LDS
+            atomicAdd(&dbg[2], 1ull);                    // workgroups that walked days
+            atomicAdd(&dbg[3], (unsigned long long)(d_end - d_begin));
+        }
+    }
+}
+
+extern "C" int marex_hobday_thresholds_pool_f32(marex_ctx* ctx, const void* lists, const uint32_t* aux, int list_rows,
+                                                const float* anom, int64_t T_out, int64_t C, int max_bucket, const int32_t* pool,
+                                                int K, int64_t c0, int64_t c1, const float* centres, int nb, double q, int wd,
+                                                float lower_bound, float upper_bound, float* thr_doy_major, marex_thr_stats* stats) {
+    if (!ctx) return -1;
+    if (!lists || !aux || !anom || !pool || !centres || !thr_doy_major || !stats || T_out <= 0 || C <= 0)
+        return fail(ctx, -1, "marex_hobday_thresholds_pool_f32: null pointer or empty shape");
+    if (wd < 3 || wd > 365 || (wd & 1) == 0)
+        return fail(ctx, -1, "marex_hobday_thresholds_pool_f32: window_days_hobday must be odd and in 3..365");
+    if (!(q > 0.0 && q <= 1.0)) return fail(ctx, -1, "marex_hobday_thresholds_pool_f32: q must be in (0, 1]");
+    if (K < 1 || K > 13) return fail(ctx, -1, "marex_hobday_thresholds_pool_f32: a pool has 1..13 members (two neighbour rings), not %d", K);
+    if (c0 < 0 || c0 >= c1 || c1 > C) return fail(ctx, -1, "marex_hobday_thresholds_pool_f32: need 0 <= c0 < c1 <= C");
+    if (nb < 4 || nb > TAIL_MAX_NB || max_bucket < 1 || max_bucket > TAIL_MAX_BUCKET || (int64_t)max_bucket * wd * K > 65535 ||
+        C > (1 << 24))
+        return fail(ctx, -4, "marex_hobday_thresholds_pool_f32: shape outside the tail kernel (nb <= %d, buckets <= %d rows, "
+                             "pooled window <= 65535 samples)", TAIL_MAX_NB, TAIL_MAX_BUCKET);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int NPER, nch;
+    if (!tails_geometry(max_bucket, list_rows, NPER, nch))
+        return fail(ctx, -4, "marex_hobday_thresholds_pool_f32: %d rows per bucket in lists of %d", max_bucket, list_rows);
+    {  // every index the kernel will read is checked here, on the host: a bad table is an error, never a device fault
+        std::vector<int32_t> h((size_t)K * (size_t)C);
+        HIP_TRY(ctx, hipMemcpyAsync(h.data(), pool, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        for (int64_t c = c0; c < c1; ++c)
+            if (h[(size_t)c] != (int32_t)c)
+                return fail(ctx, -1, "marex_hobday_thresholds_pool_f32: row 0 of the pool table must be the cell itself (cell %lld lists %d)",
+                            (long long)c, (int)h[(size_t)c]);
+        for (int m = 1; m < K; ++m)
+            for (int64_t c = c0; c < c1; ++c) {
+                const int32_t j = h[(size_t)m * (size_t)C + (size_t)c];
+                if (j < -1 || j >= C)
+                    return fail(ctx, -1, "marex_hobday_thresholds_pool_f32: pool member %d of cell %lld is %d, outside -1..%lld", m,
+                                (long long)c, (int)j, (long long)C - 1);
+            }
+    }
+    // Where the first chunks wait: in a per-wave LDS ring while it fits (1 KiB per list; measured on 0.5 M cells, 11 days of
+    // single-list buckets: 4 members 77 ms against 383 from global memory, 11 members -- one wave per CU -- 575 against 1161),
+    // else nowhere: probes read global memory, whatever the window.  THR_POOL_RING = 1 / 0 forces a path (a ring that does not
+    // fit is never taken).
+    const int nlist = (wd * K * NPER + 3) & ~3;  // the kernel pads its ring to whole groups of four slots
+    const size_t lds_mem = (size_t)K * 64 * sizeof(int), lds_max = 128 * 1024;
+    const size_t lds_ring = lds_mem + (size_t)nlist * 64 * sizeof(uint4);
+    const bool use_ring = lds_ring <= lds_max && ctx_opt(ctx, "THR_POOL_RING", 1) != 0;
+    const size_t lds = use_ring ? lds_ring : lds_mem;
+    const long ncg = (long)((c1 - c0 + 63) / 64);
+    int nblk = (int)((32L * 4 * device_cus(ctx) + ncg - 1) / ncg);  // several rounds of waves; every block re-reads wd - 1 buckets
+    nblk = nblk < 1 ? 1 : (nblk > 12 ? 12 : nblk);
+    nblk = ctx_opt(ctx, "THR_POOL_BLOCKS", nblk);
+    nblk = nblk < 1 ? 1 : (nblk > NDOY ? NDOY : nblk);
+    auto kern = use_ring ? k_thr_pool<true> : k_thr_pool<false>;
+    if (lds > 64 * 1024) HIP_TRY(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    LaunchTimer lt(ctx, MAREX_K_THRESHOLDS);
+    hipLaunchKernelGGL(kern, dim3((unsigned)ncg, (unsigned)nblk), dim3(64), lds, ctx->stream, reinterpret_cast<const uint4*>(lists),
+                       aux, NPER, nch, anom, (long)C, (long)c0, (long)c1, nblk, pool, K, centres, nb, q, wd, lower_bound, upper_bound,
+                       thr_doy_major, stats, ctx_debug_counters(ctx));
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
 // K_M from tails: extreme[t, c] = anom[t, c] >= thr[doy(t), c]  (detect.py:2003-2004) without reading the anomalies.
 // Every sample at or above the threshold sits at the top of one of its bucket's lists: the keys at or above the
 // threshold's bin are counted with packed arithmetic (they are a prefix of the sorted chunk); those above it are extremes,

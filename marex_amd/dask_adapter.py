@@ -32,7 +32,7 @@ import numpy as np
 
 from .detect import _infer_dims_coords, _raise_if_invalid, _validate_extreme_options, preprocess_data, warn_threshold_stats
 from .dist import Shard, plan_shards
-from .exceptions import DependencyError, create_data_validation_error
+from .exceptions import ConfigurationError, DependencyError, create_data_validation_error
 from .xr_compat import DataArray, Dataset, coord_values
 
 #: output variables of one block and where their spatial axes sit: "t" = (time', *space), "s" = (*space), "sd" = (*space, dayofyear),
@@ -113,7 +113,17 @@ def preprocess_data_lazy(da, *, block_rows: Optional[int] = None, block_cells: O
     :func:`marex_amd.preprocess_data`.  Returns a Dataset whose variables are Dask arrays, chunked
     ``{time: dask_chunks["time"] (default 25), space: -1}``; ``ds.encoding["marex_validation"]`` is the lazy whole-field verdict
     (:func:`validation_summary`), raised as the reference's ``DataValidationError`` when computed through
-    :func:`raise_if_invalid` -- ``check_valid=True`` does that before returning."""
+    :func:`raise_if_invalid` -- ``check_valid=True`` does that before returning.  ``neighbour_rings_hobday`` is refused here
+    (``ConfigurationError``): the blocks of the graph carry no halo cells."""
+    if kwargs.get("neighbour_rings_hobday"):
+        # a block of the lazy graph is a plain cell range: it has no halo of pool members (preprocess_data cuts its own blocks)
+        raise ConfigurationError(
+            "neighbour_rings_hobday is not supported by preprocess_data_lazy",
+            details="Pooling over mesh neighbour rings needs the pool members of a block's cells in the block.",
+            suggestions=["Use preprocess_data (it cuts the mesh into blocks with halo cells itself)",
+                         "Remove the neighbour_rings_hobday parameter"],
+            context={"neighbour_rings_hobday": kwargs.get("neighbour_rings_hobday")},
+        )
     try:
         import dask
         import dask.array as dsa

@@ -103,8 +103,10 @@ def _get_preprocessing_steps(
     window_days_hobday: int,
     window_spatial_hobday: Optional[int],
     reference_period: Optional[Tuple[int, int]] = None,
+    neighbour_rings_hobday: Optional[int] = None,
 ) -> List[str]:
-    """Provenance strings stored in ``attrs['preprocessing_steps']`` (detect.py:844-888; golden-pinned)."""
+    """Provenance strings stored in ``attrs['preprocessing_steps']`` (detect.py:844-888; golden-pinned).
+    ``neighbour_rings_hobday`` (extension) adds its words only when it is set."""
     steps: List[str] = []
     ref = f"{reference_period[0]}-{reference_period[1]}" if reference_period is not None else None
     if method_anomaly == "detrend_harmonic":
@@ -126,6 +128,8 @@ def _get_preprocessing_steps(
         txt = f"Day-of-year thresholds with {window_days_hobday} day window"
         if window_spatial_hobday is not None:
             txt += f" & {window_spatial_hobday} spatial neighbours"
+        if neighbour_rings_hobday:
+            txt += f" & {neighbour_rings_hobday} neighbour rings"
         steps.append(txt)
     return steps
 
@@ -233,12 +237,14 @@ class _FieldBlock:
         return _pipe(eng).upload(f.x[:, self.c0:self.c1], np.float32)
 
 
-def plan_blocks(field: _Field, eng, halo: int, per_cell_bytes: int, min_blocks: int = 1, engines=None):
+def plan_blocks(field: _Field, eng, halo: int, per_cell_bytes: int, min_blocks: int = 1, engines=None, pool_tab=None):
     """Spatial blocks that fit the free HBM -- the device-side counterpart of the reference's Dask layout for this path
     (space chunked, ``time: -1``; detect.py:2617-2620, 785-792): latitude bands with ``halo`` overlap rows per interior
     side on grids, cell ranges on meshes.  ``MAREX_BLOCKS=n`` forces the number of blocks (tests; tuning).
     ``engines``: every engine that will hold a block at the same time; the budget of a block is then the smallest share any
-    of them gets -- 80 % of the free memory of its card divided by the number of engines listed on that card."""
+    of them gets -- 80 % of the free memory of its card divided by the number of engines listed on that card.
+    ``pool_tab`` (meshes with ``neighbour_rings_hobday``): the blocks carry the halo cells their pools reach
+    (``plan_pool_blocks``) and a block is budgeted by its owned and halo cells together."""
     import os
 
     import torch
@@ -246,12 +252,17 @@ def plan_blocks(field: _Field, eng, halo: int, per_cell_bytes: int, min_blocks: 
     from .dist import plan_shards
 
     ny, nx = (field.ny, field.nx) if field.gridded else (0, field.nx)
+
+    def cut(ny, nx, n, halo):  # with pooling on a mesh: the same cell ranges, with halo cells and local pool tables
+        shards = plan_shards(ny, nx, n, halo)
+        return shards if pool_tab is None else plan_pool_blocks(shards, pool_tab)
+
     forced = int(os.environ.get("MAREX_BLOCKS", "0"))
     if forced > 0:
         n = min(max(forced, int(min_blocks)), ny if field.gridded else max(nx, 1))
-        return plan_shards(ny, nx, max(n, 1), halo)
+        return cut(ny, nx, max(n, 1), halo)
     if eng.device.type != "cuda":
-        return plan_shards(ny, nx, 1, halo)
+        return cut(ny, nx, 1, halo)
     torch.cuda.empty_cache()
     per_card: Dict[int, int] = {}
     for e in (engines or [eng]):
@@ -259,7 +270,7 @@ def plan_blocks(field: _Field, eng, halo: int, per_cell_bytes: int, min_blocks: 
     budget = min(int(torch.cuda.mem_get_info(torch.device("cuda", card))[0] * 0.8) // k for card, k in per_card.items())
     n = max(1, min(int(min_blocks), ny if field.gridded else nx))
     while True:
-        shards = plan_shards(ny, nx, n, halo)
+        shards = cut(ny, nx, n, halo)
         if max(sh.cells_in for sh in shards) * per_cell_bytes <= budget:
             return shards
         if n >= (ny if field.gridded else nx):
@@ -437,6 +448,163 @@ def _validate_extreme_options(
 
 
 # ======================================================================================
+# neighbour_rings_hobday: thresholds pooled over mesh neighbour rings (extension; the reference does not pool on meshes)
+# ======================================================================================
+def _validate_pool_options(gridded: bool, rings, neighbours, n_cells: int, cells_dim: str, method_extreme, method_percentile):
+    """Option checks of ``neighbour_rings_hobday`` (texts in the manner of ``_validate_extreme_options``).  Returns the
+    neighbour table as int64 ``[nv, cells]`` (1-based, 0 = none), or None for 0 rings (no pooling)."""
+    if isinstance(rings, bool) or not isinstance(rings, (int, np.integer)) or int(rings) not in (0, 1, 2):
+        raise ConfigurationError(
+            "neighbour_rings_hobday must be 0, 1 or 2",
+            details=f"neighbour_rings_hobday={rings!r}: a pool is the cell with one or two rings of its listed neighbours.",
+            suggestions=["Use neighbour_rings_hobday=1 or 2", "Remove the neighbour_rings_hobday parameter (no pooling)"],
+            context={"neighbour_rings_hobday": rings},
+        )
+    if int(rings) == 0:
+        return None
+    if gridded:
+        raise ConfigurationError(
+            "neighbour_rings_hobday is not supported for structured grids",
+            details="Pooling over neighbour rings follows the neighbours table of an unstructured mesh.",
+            suggestions=["On structured grids use window_spatial_hobday", "Remove the neighbour_rings_hobday parameter"],
+            context={"grid_type": "structured", "neighbour_rings_hobday": rings},
+        )
+    if method_extreme != "hobday_extreme":
+        raise ConfigurationError(
+            "neighbour_rings_hobday can only be used with method_extreme='hobday_extreme'",
+            details="The neighbour_rings_hobday parameter is only implemented for the Hobday extreme method.",
+            suggestions=["Remove the neighbour_rings_hobday parameter when using method_extreme='global_extreme'"],
+            context={"method_extreme": method_extreme, "neighbour_rings_hobday": rings},
+        )
+    if method_percentile == "exact":
+        raise ConfigurationError(
+            "neighbour_rings_hobday is not supported with method_percentile='exact'",
+            details="The neighbour_rings_hobday parameter is only implemented for the approximate percentile method.",
+            suggestions=["Remove the neighbour_rings_hobday parameter when using method_percentile='exact'"],
+            context={"method_percentile": method_percentile, "neighbour_rings_hobday": rings},
+        )
+    if neighbours is None:
+        raise ConfigurationError(
+            "neighbour_rings_hobday requires the neighbours array",
+            details="The pools are built from the mesh connectivity: neighbours with dims ('nv', cells), 1-based, 0 = none.",
+            suggestions=["Pass neighbours=... (the array the tracker takes)", "Remove the neighbour_rings_hobday parameter"],
+            context={"neighbour_rings_hobday": rings},
+        )
+    dims = getattr(neighbours, "dims", None)
+    nbr = np.asarray(to_numpy(neighbours) if dims is not None else neighbours)
+    if dims is not None and nbr.ndim == 2 and dims[0] == cells_dim and dims[1] != cells_dim:
+        nbr = nbr.T
+    if nbr.ndim != 2 or not 1 <= nbr.shape[0] <= 3 or nbr.shape[1] != n_cells:
+        raise ConfigurationError(
+            "neighbours must have shape (nv <= 3, ncells)",
+            details=f"neighbours has shape {tuple(nbr.shape)}, the data has {n_cells} cells.",
+            suggestions=["Pass the connectivity with dims ('nv', cells): up to three neighbours per cell"],
+            context={"neighbours_shape": tuple(nbr.shape), "ncells": n_cells},
+        )
+    if nbr.dtype.kind == "f":
+        if not np.isfinite(nbr).all() or (nbr != np.floor(nbr)).any():
+            nbr = np.full(nbr.shape, -1, dtype=np.int64)  # refused below
+    elif nbr.dtype.kind not in "iu":
+        nbr = np.full(nbr.shape, -1, dtype=np.int64)
+    nbr = nbr.astype(np.int64)
+    if nbr.size and (nbr.min() < 0 or nbr.max() > n_cells):
+        raise ConfigurationError(
+            f"neighbours entries must lie in 0..{n_cells}",
+            details="neighbours lists cells by their 1-based index, 0 = no neighbour.",
+            suggestions=["Check the index base of the connectivity (the reference's neighbours are 1-based)"],
+            context={"min": int(nbr.min()), "max": int(nbr.max()), "ncells": n_cells},
+        )
+    return nbr
+
+
+def _pool_samples(pool_tab: np.ndarray, ocean: np.ndarray) -> float:
+    """What stands for ``window_spatial_hobday ** 2`` in the low-sample warning: the median over ocean cells of the number of
+    ocean members of their pool."""
+    ocean = np.asarray(ocean, dtype=bool)
+    if not ocean.any():
+        return 1.0
+    member_ocean = (pool_tab >= 0) & ocean[np.maximum(pool_tab, 0)]
+    return float(np.median(member_ocean.sum(axis=0)[ocean]))
+
+
+def _pool_setup(field, nbr: np.ndarray, rings: int, bt, wd: int, window_year_baseline: Optional[int]):
+    """Host side of ``neighbour_rings_hobday``: the pool table of the whole mesh, the kernel's size caps checked on the
+    calendar the run will use, and the sample count of the low-sample warning."""
+    from .engine import HotPath, check_pool_caps
+
+    pool_tab = HotPath.pool_table(nbr, rings)
+    cal = calendar.build_calendar(field.time, **({} if window_year_baseline is None else {"window_year_baseline": window_year_baseline}))
+    if cal.T_out > 0:  # an empty calendar is the anomaly stage's error
+        check_pool_caps(bt.nb, cal.max_bucket, wd, int(pool_tab.shape[0]), int(pool_tab.shape[1]))
+    x0 = field.x[0] if field.x is not None else field._x_dev[0].cpu().numpy()
+    return pool_tab, _pool_samples(pool_tab, np.isfinite(x0))
+
+
+class _PoolShard:
+    """A mesh block with pooling: the owned cell range ``[own0, own1)`` followed by its halo -- the sorted cells outside the
+    range that pools of owned cells reach -- and the pool table in block-local indices (the owned cells lead, so
+    ``own_cell_slice`` and the host stitching are those of a plain cell range)."""
+
+    gridded = False
+
+    def __init__(self, rank: int, own0: int, own1: int, pool_tab: np.ndarray):
+        self.rank, self.own0, self.own1 = rank, int(own0), int(own1)
+        self.in0, self.cell_base = self.own0, self.own0
+        n_own = self.own1 - self.own0
+        mine = pool_tab[:, self.own0:self.own1]
+        outside = mine[(mine >= 0) & ((mine < self.own0) | (mine >= self.own1))]
+        self.halo = np.unique(outside).astype(np.int64)
+        if self.halo.size and self.halo[-1] >= pool_tab.shape[1]:
+            raise ProcessingError("a pool member is missing from the field",
+                                  details=f"block {rank} (cells {own0}..{own1}) pools cell {int(self.halo[-1])} of {pool_tab.shape[1]}")
+        self.cells_own, self.cells_in = n_own, n_own + int(self.halo.size)
+        self.ny_in = 0
+        #: global ids of the ingested cells, in block order
+        self.cell_ids = np.concatenate([np.arange(self.own0, self.own1, dtype=np.int64), self.halo])
+        local = np.full((pool_tab.shape[0], self.cells_in), -1, dtype=np.int32)
+        local[0] = np.arange(self.cells_in, dtype=np.int32)  # a halo cell is a pool of its own: its thresholds are not asked for
+        inside = (mine >= self.own0) & (mine < self.own1)
+        pos = np.searchsorted(self.halo, mine) if self.halo.size else np.zeros(mine.shape, dtype=np.int64)
+        pos = np.minimum(pos, max(self.halo.size - 1, 0))
+        found = (self.halo[pos] == mine) if self.halo.size else np.zeros(mine.shape, dtype=bool)
+        if ((mine >= 0) & ~inside & ~found).any():
+            raise ProcessingError("a pool member is missing from its block", details=f"block {rank}: cells {own0}..{own1}")
+        loc = np.where(inside, mine - self.own0, n_own + pos)
+        local[:, :n_own] = np.where(mine >= 0, loc, -1).astype(np.int32)
+        self.pool_local = local
+
+    def own_cell_slice(self) -> slice:
+        return slice(0, self.cells_own)
+
+
+def plan_pool_blocks(shards, pool_tab: np.ndarray):
+    """The cell ranges of ``plan_shards`` as blocks with halo cells and block-local pool tables."""
+    return [_PoolShard(sh.rank, sh.own0, sh.own1, pool_tab) for sh in shards]
+
+
+class _PoolFieldBlock:
+    """``_FieldBlock`` for a block with halo cells: the columns are gathered, on the host or with ``index_select`` when the
+    field is resident."""
+
+    def __init__(self, field, sh: _PoolShard):
+        self.parent, self.shard = field, sh
+        self.time, self.gridded = field.time, False
+        self.ny, self.nx = 0, sh.cells_in
+        self.shape = (field.shape[0], sh.cells_in)
+
+    def device_x(self, eng):
+        import torch
+
+        f, sh = self.parent, self.shard
+        if f._x_dev is not None:
+            idx = torch.from_numpy(sh.cell_ids).to(f._x_dev.device)
+            return f._x_dev.index_select(1, idx).to(device=eng.device, dtype=torch.float32).contiguous()
+        if sh.halo.size == 0:
+            return _pipe(eng).upload(f.x[:, sh.own0:sh.own1], np.float32)
+        return _pipe(eng).upload(np.ascontiguousarray(f.x[:, sh.cell_ids]), np.float32)
+
+
+# ======================================================================================
 # core on flat arrays (device)
 # ======================================================================================
 def _anomaly_core(eng, field: _Field, method_anomaly, window_year_baseline, smooth_days_baseline, detrend_orders,
@@ -565,10 +733,12 @@ def _warn_threshold_range(stats: Dict[str, float], bt, max_anomaly: float) -> No
 
 
 def _extremes_core(eng, a, field, method_extreme, threshold_percentile, window_days_hobday, ws_eff,
-                   method_percentile, bt: Optional[binning.BinTable], max_anomaly, wsp=None, rows=None, defer=None):
+                   method_percentile, bt: Optional[binning.BinTable], max_anomaly, wsp=None, rows=None, defer=None, pool=None):
     """Threshold + mask stage on the device.  Returns (extreme uint8 [T', C], thresholds (host layout), dims tag).
     ``rows``: grid rows of a latitude band whose thresholds are wanted (the others are overlap rows); ``defer``: a dict
-    that collects the threshold-range statistics instead of warning at once (block-wise runs warn once, at the end)."""
+    that collects the threshold-range statistics instead of warning at once (block-wise runs warn once, at the end).
+    ``pool`` (``neighbour_rings_hobday``): ``{"table": int32 [K, cells] on the device, "cells": (c0, c1) owned cells or None,
+    "samples": what stands for ws ** 2 in the low-sample warning}``."""
     cal, dcal = a["cal"], a["dcal"]
 
     def range_stats(stats, table):
@@ -580,6 +750,8 @@ def _extremes_core(eng, a, field, method_extreme, threshold_percentile, window_d
     if method_extreme == "hobday_extreme":
         n_years = cal.n_years_present if cal.T_out == cal.T else int(np.unique(cal.year[cal.kept]).size)
         n_above = n_years * window_days_hobday * (ws_eff if ws_eff is not None else 1) ** 2 * (1.0 - threshold_percentile / 100.0)
+        if pool is not None:
+            n_above = n_years * window_days_hobday * pool["samples"] * (1.0 - threshold_percentile / 100.0)
         if n_above < 50 and not (defer or {}).get("logged"):  # detect.py:1905-1915
             if defer is not None:
                 defer["logged"] = True
@@ -592,10 +764,16 @@ def _extremes_core(eng, a, field, method_extreme, threshold_percentile, window_d
             thr_doy = eng.hobday_thresholds_exact(a["anom"], dcal, float(threshold_percentile), int(window_days_hobday))
             m = eng.mask_ge_doy(a["anom"], thr_doy, dcal)
             return m["extreme"], thr_doy, "doy_first", m["n_true"]
-        t = eng.hobday_approx(
-            a["anom"], dcal, bt, threshold_percentile / 100.0, int(window_days_hobday),
-            int(ws_eff) if ws_eff else 1, field.ny, field.nx, rows=rows, binsb=a.get("bins"), tails=a.get("tails"),
-        )
+        if pool is not None:
+            t = eng.hobday_approx(
+                a["anom"], dcal, bt, threshold_percentile / 100.0, int(window_days_hobday), 1, field.ny, field.nx,
+                cells=pool["cells"], tails=a.get("tails"), pool=pool["table"],
+            )
+        else:
+            t = eng.hobday_approx(
+                a["anom"], dcal, bt, threshold_percentile / 100.0, int(window_days_hobday),
+                int(ws_eff) if ws_eff else 1, field.ny, field.nx, rows=rows, binsb=a.get("bins"), tails=a.get("tails"),
+            )
         thr = eng.transpose(t["thr_doy_major"])
         range_stats(eng.decode_thr_stats(t["stats_dev"]), bt)
         return t["extreme"], thr, "doy_last", t["n_true"]
@@ -613,9 +791,11 @@ def _extremes_core(eng, a, field, method_extreme, threshold_percentile, window_d
 def dataset_attrs(method_anomaly="shifting_baseline", method_extreme="hobday_extreme", threshold_percentile=95,
                   std_normalise=False, detrend_orders=None, window_year_baseline=15, smooth_days_baseline=21,
                   window_days_hobday=11, window_spatial_hobday=None, reference_period=None, force_zero_mean=True,
-                  method_percentile="approximate", precision=0.01, max_anomaly=5.0, **_other) -> Dict[str, object]:
+                  method_percentile="approximate", precision=0.01, max_anomaly=5.0, neighbour_rings_hobday=None,
+                  **_other) -> Dict[str, object]:
     """The Dataset attrs of ``preprocess_data`` exactly as detect.py:731-783 builds them -- a function of the options alone
-    (defaults = those of ``preprocess_data``; options that leave no attr are ignored)."""
+    (defaults = those of ``preprocess_data``; options that leave no attr are ignored).  ``neighbour_rings_hobday`` (extension)
+    leaves an attr and its words in the steps only when it is set."""
     if detrend_orders is None:
         detrend_orders = [1]
     attrs: Dict[str, object] = {
@@ -625,6 +805,7 @@ def dataset_attrs(method_anomaly="shifting_baseline", method_extreme="hobday_ext
         "preprocessing_steps": _get_preprocessing_steps(
             method_anomaly, method_extreme, std_normalise, detrend_orders, window_year_baseline,
             smooth_days_baseline, window_days_hobday, window_spatial_hobday, reference_period,
+            neighbour_rings_hobday=neighbour_rings_hobday or None,
         ),
     }
     if method_anomaly == "detrend_harmonic":
@@ -640,6 +821,8 @@ def dataset_attrs(method_anomaly="shifting_baseline", method_extreme="hobday_ext
             attrs["reference_period"] = list(reference_period)
     if method_extreme == "hobday_extreme":
         attrs["window_days_hobday"] = window_days_hobday
+        if neighbour_rings_hobday:
+            attrs["neighbour_rings_hobday"] = int(neighbour_rings_hobday)
     attrs.update({"method_percentile": method_percentile, "precision": precision, "max_anomaly": max_anomaly})
     return attrs
 
@@ -671,6 +854,7 @@ def preprocess_data(
     device: int = 0,
     devices: Optional[List[int]] = None,
     require_dask: bool = False,
+    neighbour_rings_hobday: Optional[int] = None,
     _validation: str = "raise",
     _own_rows: Optional[Tuple[int, int]] = None,
     _defer_warnings: bool = False,
@@ -689,6 +873,12 @@ def preprocess_data(
     are about -- the others are overlap rows (the call then runs as ONE device block: a caller that cuts the field itself sizes its
     blocks to the HBM); ``_defer_warnings``: the threshold-range statistics (detect.py:2711-2730) are returned as
     ``ds.attrs["_thr_stats"]`` instead of being warned about, so that a caller with several blocks warns once for the field.
+
+    ``neighbour_rings_hobday=1 | 2`` (extension; unstructured meshes, ``hobday_extreme`` with the approximate percentile,
+    ``neighbours`` given): the day-of-year histograms behind a cell's thresholds are summed over the cell and one or two rings of
+    its listed neighbours (at most 13 cells; only listed links count, every member once) -- the mesh counterpart of
+    ``window_spatial_hobday``, which the reference refuses on meshes.  ``None`` / ``0``: no pooling.  Spatial blocks then carry
+    the halo cells their pools reach; results do not depend on the blocks.
 
     ``devices=[0, 1, ...]`` (extension): the field is cut into at least that many spatial blocks (latitude bands
     with ``ws//2`` overlap rows / cell ranges -- cells are independent along time) and every listed device works through its
@@ -753,12 +943,21 @@ def preprocess_data(
     bt = binning.hobday_bins(precision, max_anomaly) if method_percentile == "approximate" else None
     need_bins = bt if (method_extreme == "hobday_extreme" and method_percentile == "approximate") else None
     want_stn = bool(std_normalise) and method_anomaly == "detrend_harmonic"
+    pool_tab = pool_samples = None
+    if neighbour_rings_hobday is not None:
+        nbr = _validate_pool_options(field.gridded, neighbour_rings_hobday, neighbours, field.shape[1],
+                                     field.sdims[-1], method_extreme, method_percentile)
+        if nbr is not None:
+            pool_tab, pool_samples = _pool_setup(field, nbr, int(neighbour_rings_hobday), bt, int(window_days_hobday),
+                                                 int(window_year_baseline) if method_anomaly == "shifting_baseline" else None)
 
     # Spatial blocks sized to the free HBM (one block when everything fits): every stage is per cell along time except
     # the ws x ws pooling, so latitude bands carry ws//2 overlap rows and nothing is exchanged between blocks.
     T = field.shape[0]
     halo = (int(ws_eff) // 2) if (need_bins is not None and ws_eff) else 0
     per_cell = (4 * T + 7 * T) + (8 * T if method_anomaly.startswith("detrend") else 0) + (11 * T if want_stn else 0) + 366 * 24
+    if pool_tab is not None:
+        per_cell += 4 * pool_tab.shape[0]
     dev_list = [int(d) for d in devices] if devices else [int(device)]
     seen: Dict[int, int] = {}
     engines = []
@@ -771,6 +970,8 @@ def preprocess_data(
         from .dist import plan_shards as _plan_shards
 
         blocks = _plan_shards(field.ny if field.gridded else 0, field.nx, 1, halo)
+        if pool_tab is not None:
+            blocks = plan_pool_blocks(blocks, pool_tab)
         if eng.device.type == "cuda":
             import torch as _torch
 
@@ -782,7 +983,7 @@ def preprocess_data(
                     suggestions=["use smaller blocks (block_rows / block_cells of preprocess_data_lazy)"],
                 )
     else:
-        blocks = plan_blocks(field, eng, halo, int(per_cell * 1.25), min_blocks=len(engines), engines=engines)
+        blocks = plan_blocks(field, eng, halo, int(per_cell * 1.25), min_blocks=len(engines), engines=engines, pool_tab=pool_tab)
     single = len(blocks) == 1
     if not single:
         logger.info(f"Field processed in {len(blocks)} spatial blocks of <= {max(b.cells_in for b in blocks)} cells"
@@ -821,7 +1022,10 @@ def preprocess_data(
     def run_block(e, sh, stop):
         """Anomaly + threshold + mask stages of one spatial block on engine ``e``; its owned cells go to the host arrays.
         Returns the block's validation counts, deferred warning statistics, calendar and extreme count."""
-        fb = field if single else field.block(sh)
+        fb = field if single else (field.block(sh) if pool_tab is None else _PoolFieldBlock(field, sh))
+        pool = None
+        if pool_tab is not None:  # the table in block-local indices, uploaded once per block and shared by both extreme passes
+            pool = {"table": e._dev(sh.pool_local, np.int32), "cells": None if single else (0, sh.cells_own), "samples": pool_samples}
         rows = None if single or not field.gridded else (sh.own0 - sh.in0, sh.own1 - sh.in0)
         defer = {"stats": [], "logged": logged["logged"]}
         bins_for = None
@@ -849,7 +1053,7 @@ def preprocess_data(
             return res  # the run ends in the reference's validation error: only the counts of the other blocks matter
         ext, thr, thr_kind, n_true = _extremes_core(
             e, a, fb, method_extreme, threshold_percentile, window_days_hobday, ws_eff, method_percentile, bt, max_anomaly,
-            rows=rows, defer=defer,
+            rows=rows, defer=defer, pool=pool,
         )
         put(e, "dat_anomaly", a["anom"], "cells_last", sh)
         put(e, "mask", a["mask"], "cells_last", sh)
@@ -864,7 +1068,7 @@ def preprocess_data(
             a_stn = {"anom": sn["dat_stn"], "cal": a["cal"], "dcal": a["dcal"], "bins": None}
             ext_s, thr_s, kind_s, _ = _extremes_core(
                 e, a_stn, fb, method_extreme, threshold_percentile, window_days_hobday, ws_eff, method_percentile, bt,
-                max_anomaly, wsp={}, rows=rows, defer=defer,
+                max_anomaly, wsp={}, rows=rows, defer=defer, pool=pool,
             )
             put(e, "dat_stn", sn["dat_stn"], "cells_last", sh)
             put(e, "STD", e.transpose(sn["STD"], name="std_cells_major"), "doy_last", sh)  # flox appends the group dim
@@ -946,6 +1150,8 @@ def preprocess_data(
         ds["extreme_events_stn"] = field.labelled(as_bool(out["extreme_events_stn"]), tlead)
         ds["thresholds_stn"] = with_doy("thresholds_stn", kinds["thresholds_stn"])
     if neighbours is not None:
+        if pool_tab is not None and not hasattr(neighbours, "dims"):  # a plain array: labelled as the reference's ('nv', cells)
+            neighbours = DataArray(np.asarray(neighbours), dims=("nv", field.sdims[-1]))
         ds["neighbours"] = neighbours.astype(np.int32)
     if cell_areas is not None:
         ds["cell_areas"] = cell_areas.astype(np.float32)
@@ -955,7 +1161,8 @@ def preprocess_data(
         std_normalise=std_normalise, detrend_orders=detrend_orders, window_year_baseline=window_year_baseline,
         smooth_days_baseline=smooth_days_baseline, window_days_hobday=window_days_hobday,
         window_spatial_hobday=window_spatial_hobday, reference_period=reference_period, force_zero_mean=force_zero_mean,
-        method_percentile=method_percentile, precision=precision, max_anomaly=max_anomaly))
+        method_percentile=method_percentile, precision=precision, max_anomaly=max_anomaly,
+        neighbour_rings_hobday=neighbour_rings_hobday if pool_tab is not None else None))
     if _validation != "raise":
         ds.attrs["_validation"] = dict(total)
     if _defer_warnings:
@@ -1033,8 +1240,12 @@ def identify_extremes(
     verbose: Optional[bool] = None,
     quiet: Optional[bool] = None,
     device: int = 0,
+    neighbours=None,
+    neighbour_rings_hobday: Optional[int] = None,
 ):
-    """Threshold + mask stage on given anomalies (detect.py:1119-1503).  Returns ``(extremes, thresholds)``."""
+    """Threshold + mask stage on given anomalies (detect.py:1119-1503).  Returns ``(extremes, thresholds)``.
+    ``neighbours`` / ``neighbour_rings_hobday`` (extension): thresholds pooled over mesh neighbour rings, as in
+    :func:`preprocess_data`."""
     import torch
 
     dimensions, coordinates = _infer_dims_coords(da, dimensions, coordinates)
@@ -1044,14 +1255,22 @@ def identify_extremes(
         method_percentile, precision, max_anomaly,
     )
     field = _Field(da, dimensions, coordinates)
-    eng = get_engine(device)
     bt = binning.hobday_bins(precision, max_anomaly) if method_percentile == "approximate" else None
+    pool_tab = None
+    if neighbour_rings_hobday is not None:
+        nbr = _validate_pool_options(field.gridded, neighbour_rings_hobday, neighbours, field.shape[1], field.sdims[-1],
+                                     method_extreme, method_percentile)
+        if nbr is not None:
+            pool_tab, samples = _pool_setup(field, nbr, int(neighbour_rings_hobday), bt, int(window_days_hobday), None)
+    eng = get_engine(device)
     cal = calendar.build_calendar(field.time)
     dcal = eng.upload_calendar(cal)
+    pool = None if pool_tab is None else {"table": eng._dev(pool_tab, np.int32), "cells": None, "samples": samples}
     anom = field.device_x(eng)
     a = {"anom": anom, "cal": cal, "dcal": dcal, "bins": None}
     ext, thr, kind, _ = _extremes_core(
-        eng, a, field, method_extreme, threshold_percentile, window_days_hobday, ws_eff, method_percentile, bt, max_anomaly
+        eng, a, field, method_extreme, threshold_percentile, window_days_hobday, ws_eff, method_percentile, bt, max_anomaly,
+        pool=pool,
     )
     eng.sync()
     extremes = field.labelled(ext.cpu().numpy().astype(bool), (field.tdim, field.time))

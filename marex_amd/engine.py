@@ -104,6 +104,21 @@ def _linear_percentile(values: torch.Tensor, q: float) -> float:
     return a + (b - a) * g if g < 0.5 else b - (b - a) * (1.0 - g)
 
 
+def check_pool_caps(nb: int, max_bucket: int, wd: int, K: int, C: Optional[int] = None) -> None:
+    """What the pooled threshold kernel (``neighbour_rings_hobday``) takes: the list kernels' table and bucket sizes, and a
+    pooled window of at most 65535 samples (its 16-bit packed counters; the gridded kernel's cap with ``K`` for ``ws * ws``)."""
+    if nb <= 511 and 1 <= max_bucket <= 128 and max_bucket * wd * K <= 65535 and (C is None or C <= (1 << 24)):
+        return
+    raise ConfigurationError(
+        "neighbour_rings_hobday is not supported for this configuration",
+        details=f"The pooled threshold kernel takes at most 511 bins (here {nb}), day-of-year buckets of at most 128 rows "
+                f"(here {max_bucket}) and pooled windows of at most 65535 samples (here {max_bucket} x {wd} days x {K} cells).",
+        suggestions=["Use a smaller window_days_hobday or fewer neighbour rings", "Use a coarser precision or a smaller max_anomaly",
+                     "Remove the neighbour_rings_hobday parameter"],
+        context={"bins": nb, "max_bucket": max_bucket, "window_days_hobday": wd, "pool_members": K},
+    )
+
+
 @dataclass
 class DeviceCalendar:
     """Calendar tables resident on the device."""
@@ -422,6 +437,76 @@ class HotPath:
                   float(bins.lower_bound), float(bins.upper_bound), int(row0), int(row1), thr, stats)
         return {"thr_doy_major": thr, "stats_dev": stats, "_keep": centres}
 
+    # ------------------------------------------------------------------ pooling over mesh neighbour rings
+    #: most members a pool can have: the cell, three neighbours, their three neighbours each
+    POOL_MAX_MEMBERS = 13
+
+    @staticmethod
+    def pool_table(neighbours_1based, rings: int) -> np.ndarray:
+        """The pools of ``neighbour_rings_hobday`` as the int32 table ``[K, C]`` the pooled threshold kernel reads
+        (include/marex_hip.h): row 0 is the cell, the other rows its further members in ascending order, ``-1`` = empty slot,
+        no member twice, ``K`` = size of the largest pool.  ``neighbours_1based`` is ``[nv <= 3, C]``, 1-based, 0 = none; only
+        listed links count (a link listed from one end is one-way) and ``pool(c, r)`` is what ``r`` steps along listed links
+        reach from ``c``, ``c`` included.  Host NumPy: built once per run."""
+        nbr = np.asarray(neighbours_1based)
+        if nbr.ndim != 2 or nbr.shape[0] > 3 or nbr.shape[0] < 1:
+            raise ValueError("neighbours must be [nv <= 3, cells]")
+        if rings not in (1, 2):
+            raise ValueError("rings must be 1 or 2")
+        Cn = nbr.shape[1]
+        n0 = nbr.astype(np.int64) - 1  # 0-based, -1 = none
+        if n0.size and (n0.min() < -1 or n0.max() >= Cn):
+            raise ValueError("neighbours entries must lie in 0..cells")
+        cand = [n0[a] for a in range(n0.shape[0])]
+        if rings == 2:
+            for a in range(n0.shape[0]):
+                via = n0[a]
+                for b in range(n0.shape[0]):
+                    cand.append(np.where(via >= 0, n0[b][np.maximum(via, 0)], -1))
+        big = np.int64(Cn)  # sorts behind every cell
+        m = np.stack(cand) if cand else np.empty((0, Cn), np.int64)
+        m = np.where((m < 0) | (m == np.arange(Cn, dtype=np.int64)[None, :]), big, m)
+        m = np.sort(m, axis=0)
+        dup = np.zeros(m.shape, dtype=bool)
+        dup[1:] = m[1:] == m[:-1]
+        m = np.sort(np.where(dup, big, m), axis=0)
+        k_more = int((m < big).sum(axis=0).max()) if m.size else 0
+        tab = np.full((1 + k_more, Cn), -1, dtype=np.int32)
+        tab[0] = np.arange(Cn, dtype=np.int32)
+        tab[1:] = np.where(m[:k_more] < big, m[:k_more], -1).astype(np.int32)
+        return tab
+
+    def pool_plan(self, dcal: DeviceCalendar, bins: BinTable, q: float, wd: int, K: int, C: Optional[int] = None) -> int:
+        """Rows of the largest dayofyear bucket when the pooled threshold kernel takes this configuration with pools of ``K``
+        members; raises the ``ConfigurationError`` of ``neighbour_rings_hobday`` otherwise (pooling needs the key lists)."""
+        check_pool_caps(bins.nb, dcal.plan.max_bucket, int(wd), int(K), C)
+        nd = self.tails_plan(dcal, bins, q, wd, 1, C)
+        if nd is None:
+            raise ConfigurationError(
+                "neighbour_rings_hobday needs the sorted key lists of the day-of-year histograms",
+                details=f"this configuration takes the bin-matrix threshold kernels (hobday_path={self.hobday_path!r}, q={q})",
+                suggestions=["Remove the neighbour_rings_hobday parameter", "Leave engine.hobday_path at None or 'tails'"],
+            )
+        return nd
+
+    def hobday_thresholds_pool(self, tl: dict, anom: torch.Tensor, dcal: DeviceCalendar, bins: BinTable, q: float, wd: int,
+                               pool: torch.Tensor, cells: Optional[tuple] = None, wsp: Optional[dict] = None):
+        """Day-of-year thresholds from the key lists, the histogram of a cell summed over its pool (``pool``: int32 ``[K, C]``
+        on the device, :meth:`pool_table`); written for ``cells=(c0, c1)`` only.  Options THR_POOL_RING (1 / 0: the first
+        chunks wait in LDS / are read from global memory at every probe) and THR_POOL_BLOCKS; same bits on either path
+        (DESIGN.md section 4)."""
+        T_out, Cn = anom.shape
+        if pool.dtype != torch.int32 or pool.dim() != 2 or pool.shape[1] != Cn:
+            raise ProcessingError("hobday_thresholds_pool: the pool table must be int32 [K, cells]",
+                                  details=f"got {pool.dtype} {tuple(pool.shape)} for {Cn} cells")
+        c0, c1 = cells if cells is not None else (0, Cn)
+        thr, stats = self._threshold_buffers(wsp, Cn)
+        centres = self.bin_tables(bins)[1]
+        self.call("marex_hobday_thresholds_pool_f32", tl["tails"], tl["aux"], int(tl["list_rows"]), anom, T_out, Cn,
+                  int(tl["max_bucket"]), pool, int(pool.shape[0]), int(c0), int(c1), centres, bins.nb, float(q), int(wd),
+                  float(bins.lower_bound), float(bins.upper_bound), thr, stats)
+        return {"thr_doy_major": thr, "stats_dev": stats, "_keep": (centres, pool)}
+
     def _extreme_buffers(self, wsp: Optional[dict], T_out: int, Cn: int):
         """``(extreme [T_out, Cn] uint8, n_true [1] int64 = 0)`` of the compare kernels."""
         ext = self._buf(wsp, "extreme", (T_out, Cn), torch.uint8, self.device)
@@ -441,9 +526,18 @@ class HotPath:
 
     def hobday_approx(self, anom: torch.Tensor, dcal: DeviceCalendar, bins: BinTable, q: float, wd: int, ws: int, ny: int,
                       nx: int, rows: Optional[tuple] = None, cells: Optional[tuple] = None, wsp: Optional[dict] = None,
-                      binsb: Optional[torch.Tensor] = None, tails: Optional[dict] = None) -> Dict[str, object]:
+                      binsb: Optional[torch.Tensor] = None, tails: Optional[dict] = None,
+                      pool: Optional[torch.Tensor] = None) -> Dict[str, object]:
         """Approximate Hobday thresholds + extreme mask of an anomaly field (detect.py:1957-2004): through tails when
-        ``tails_plan`` takes the configuration, else through the bin matrix (``binsb``, made here when missing)."""
+        ``tails_plan`` takes the configuration, else through the bin matrix (``binsb``, made here when missing).
+        ``pool`` (int32 ``[K, C]``, :meth:`pool_table`): thresholds pooled over mesh neighbour rings, for ``cells`` only."""
+        if pool is not None:
+            self.pool_plan(dcal, bins, q, wd, int(pool.shape[0]), anom.shape[1])
+            tl = tails if tails is not None else self.tail_extract(anom, dcal, bins, wsp=wsp)
+            t = self.hobday_thresholds_pool(tl, anom, dcal, bins, q, wd, pool, cells=cells, wsp=wsp)
+            m = self.mask_ge_doy_tails(tl, anom, t["thr_doy_major"], dcal, bins, cells=cells, wsp=wsp)
+            return {"thr_doy_major": t["thr_doy_major"], "stats_dev": t["stats_dev"], "extreme": m["extreme"], "n_true": m["n_true"],
+                    "path": "tails", "_keep": (tl, t["_keep"])}
         K = self.tails_plan(dcal, bins, q, wd, ws, anom.shape[1])
         if K is not None:
             tl = tails if tails is not None else self.tail_extract(anom, dcal, bins, wsp=wsp)
