@@ -101,7 +101,7 @@ int marex_set_option(marex_ctx* ctx, const char* name, int value);
 int marex_clear_option(marex_ctx* ctx, const char* name);
 /* Event counters of the tail kernels (host uint64[8], synchronises the stream): [0] column rebuilds, [1] probes the per-cell and pooled threshold kernels recounted from every chunk,
  * [2] extra passes for stragglers, [3] days walked (per tile and block),
- * [4] (4-cell, dayofyear) groups the mask kernel decided on the anomalies, [5..7] phase timers of -DMAREX_STAMPS builds.
+ * [4] (4-cell, dayofyear) groups the mask kernel decided on the anomalies, [5..7] unused (always 0).
  * The pooled threshold kernel adds per workgroup: [0] one when its first chunks waited in LDS, [2] one, [3] its days.
  * reset != 0 zeroes them afterwards. */
 int marex_debug_counters(marex_ctx* ctx, uint64_t* out8, int reset);

@@ -573,13 +573,7 @@ static int detrend_impl(marex_ctx* ctx, const float* x, int64_t T, int64_t C, co
     const int ntb = (int)((T + DETREND_TBLOCK - 1) / DETREND_TBLOCK);
     // scratch: partial [ntb][n][C] f64 (reused as psum [ntb][C]) + coef [n][C] f64 + mean [C] f32
     const size_t need = ((size_t)ntb * n_coef + n_coef + 1) * (size_t)C * sizeof(double);
-    if (need > ctx->detrend_scratch_bytes) {
-        if (ctx->detrend_scratch) HIP_TRY(ctx, hipFree(ctx->detrend_scratch));
-        ctx->detrend_scratch = nullptr;
-        ctx->detrend_scratch_bytes = 0;
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->detrend_scratch, need));
-        ctx->detrend_scratch_bytes = need;
-    }
+    HIP_TRY(ctx, grow_scratch(ctx->detrend_scratch, ctx->detrend_scratch_bytes, need));
     double* partial = reinterpret_cast<double*>(ctx->detrend_scratch);
     double* coef = partial + (size_t)ntb * n_coef * C;
     float* mean = reinterpret_cast<float*>(coef + (size_t)n_coef * C);

@@ -76,12 +76,6 @@ static inline int ctx_opt(marex_ctx* ctx, const char* name, int dflt) {
     return it == ctx->opts.end() ? dflt : it->second;
 }
 
-#ifdef MAREX_ABLATION
-#define MAREX_ABLATE_OPT(ctx, name) ctx_opt(ctx, name, 0)
-#else
-#define MAREX_ABLATE_OPT(ctx, name) 0
-#endif
-
 static inline unsigned long long* ctx_debug_counters(marex_ctx* ctx) {
     if (!ctx->dbg_counters) {
         if (hipMalloc((void**)&ctx->dbg_counters, MAREX_DBG_COUNTERS * sizeof(unsigned long long)) != hipSuccess) return nullptr;
@@ -114,6 +108,23 @@ static inline int fail(marex_ctx* ctx, int code, const char* fmt, ...) {
         hipError_t e__ = (expr);                                                                \
         if (e__ != hipSuccess) return fail(ctx, -2, "%s failed: %s", #expr, hipGetErrorString(e__)); \
     } while (0)
+
+// Grow a device scratch buffer of the context (pointer and its size field) to at least `need` bytes; the old contents are
+// not kept.  Returns the HIP error for HIP_TRY: after a failed hipMalloc the buffer is empty (null, 0 bytes), after a failed
+// hipFree it is as it was.
+template <typename T>
+static inline hipError_t grow_scratch(T*& buf, size_t& bytes, size_t need) {
+    if (need <= bytes) return hipSuccess;
+    if (buf) {
+        const hipError_t e = hipFree(buf);
+        if (e != hipSuccess) return e;
+    }
+    buf = nullptr;
+    bytes = 0;
+    const hipError_t e = hipMalloc((void**)&buf, need);
+    if (e == hipSuccess) bytes = need;
+    return e;
+}
 
 struct LaunchTimer {
     marex_ctx* ctx;

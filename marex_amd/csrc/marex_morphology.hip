@@ -182,13 +182,7 @@ k_time_closing(const unsigned char* __restrict__ data, long T, long C, int c, un
 }
 
 static int ensure_scratch(marex_ctx* ctx, size_t need) {
-    if (need > ctx->morph_scratch_bytes) {
-        if (ctx->morph_scratch) HIP_TRY(ctx, hipFree(ctx->morph_scratch));
-        ctx->morph_scratch = nullptr;
-        ctx->morph_scratch_bytes = 0;
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->morph_scratch, need));
-        ctx->morph_scratch_bytes = need;
-    }
+    HIP_TRY(ctx, grow_scratch(ctx->morph_scratch, ctx->morph_scratch_bytes, need));
     return 0;
 }
 

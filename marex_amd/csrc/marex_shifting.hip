@@ -20,11 +20,8 @@ __global__ void __launch_bounds__(256)
 k_shifting(const float* __restrict__ x, long T, long C, const int4* __restrict__ year_plan, int n_cal, int W,
            int S_rt, int write_clim, const float* __restrict__ edges, int nb, long T_out, float* __restrict__ out,
            unsigned short* __restrict__ bins, unsigned char* __restrict__ mask, int* __restrict__ invalid_count,
-           int ncb, int nchunks, int ablate, const int* __restrict__ skip) {
+           int ncb, int nchunks, const int* __restrict__ skip) {
     extern __shared__ float lds[];
-#ifndef MAREX_ABLATION
-    ablate = 0;  // the timing-only ablation bits (wrong results by design) exist only in -DMAREX_ABLATION builds
-#endif
     // W-year history of every (cell, dayofyear).  LDS ring [D][WCAP][256] (slots W..WCAP-1 hold +0.0, neutral in
     // the sum), or -- RREG -- a register shift line per dayofyear: rr[i][WCAP-W .. WCAP-1] = years y-W .. y-1,
     // the leading WCAP-W entries stay +0.0.  The register line frees the LDS, so occupancy is set by VGPRs only.
@@ -51,7 +48,7 @@ k_shifting(const float* __restrict__ x, long T, long C, const int4* __restrict__
         for (int i = 0; i < D; ++i)
 #pragma unroll
             for (int j = 0; j < WCAP; ++j) rr[i][j] = j >= npad ? nan_f() : 0.f;
-    } else if (!(ablate & 128)) {
+    } else {
         for (int i = tid; i < D * WCAP * 256; i += 256) ring[i] = ((i >> 8) % WCAP) < W ? nan_f() : 0.f;
     }
     // ring_read: the W history values in ascending year order plus the +0.0 pads (LDS: pads last, RREG: pads first;
@@ -97,12 +94,11 @@ k_shifting(const float* __restrict__ x, long T, long C, const int4* __restrict__
         e_first = e[1];
         e_delta = e[2] - e[1];
         e_last = e[nb];
-        arange_tab = edges_are_arange(e, nb) && !(ablate & 512);
+        arange_tab = edges_are_arange(e, nb);
     }
 
     int n_invalid = 0;
     if (chunk == 0 && mask && active) mask[c] = finite_f(x[c]) ? 1 : 0;
-    if (ablate & 256) return;  // timing only: launch + init
     // Inactive lanes (beyond C) stream -- and store -- the last cell instead of being masked off: loads and
     // stores stay unconditional and uniform in control flow (duplicate stores write identical values).
     const unsigned cidx = active ? (unsigned)c : (unsigned)(C - 1);
@@ -111,45 +107,36 @@ k_shifting(const float* __restrict__ x, long T, long C, const int4* __restrict__
     // pl = {timestep, output row, bin-matrix row} (-1: none).  The ring is read with NO predicates: the slots
     // of years y-W .. y-1 in ascending order (slot0, slot0+1, ... mod W), then the +0.0 pad slots.
     auto emit = [&](int i, int slot0, const int4 pl, float xc, float s) {
-        if (ablate & 1) {  // timing only: keep the inputs alive, skip climatology / anomaly / bins / stores
-            if (xc + s == 12345.678f) out[cidx] = xc;
-            return;
-        }
         if (pl.x >= 0) {  // uniform
             n_invalid += finite_f(xc) ? 0 : 1;
             if (pl.y >= 0) {  // uniform: this timestep is an output row
                 float rv[WCAP];
                 float acc = 0.f;
                 int n = W;
-                if (ablate & 8) {
-                    acc = s;
-                } else {
-                    ring_read(i, slot0, rv);
+                ring_read(i, slot0, rv);
 #pragma unroll
-                    for (int j = 0; j < WCAP; ++j) acc += rv[j];
-                    // a NaN term (leap day, first days of the series, gaps): redo as nanmean.  Land lanes (NaN
-                    // centre value) never need it -- their anomaly is NaN whatever the climatology is.
-                    if (!(acc == acc) && (write_clim || xc == xc)) {
-                        acc = 0.f;
-                        n = 0;
+                for (int j = 0; j < WCAP; ++j) acc += rv[j];
+                // a NaN term (leap day, first days of the series, gaps): redo as nanmean.  Land lanes (NaN
+                // centre value) never need it -- their anomaly is NaN whatever the climatology is.
+                if (!(acc == acc) && (write_clim || xc == xc)) {
+                    acc = 0.f;
+                    n = 0;
 #pragma unroll
-                        for (int j = 0; j < WCAP; ++j) {
-                            if (is_real(j) && rv[j] == rv[j]) {
-                                acc += rv[j];
-                                ++n;
-                            }
+                    for (int j = 0; j < WCAP; ++j) {
+                        if (is_real(j) && rv[j] == rv[j]) {
+                            acc += rv[j];
+                            ++n;
                         }
                     }
                 }
-                const float clim = (ablate & 16) ? acc : acc / (float)n;  // n == 0 -> 0/0 = NaN
+                const float clim = acc / (float)n;  // n == 0 -> 0/0 = NaN
                 const float a = xc - clim;
                 // lanes beyond C duplicate the last cell (same inputs, same values): stores need no guard
-                if (!(ablate & 64)) out[(size_t)pl.y * C + cidx] = write_clim ? clim : a;
-                if (do_bins && !(ablate & 32))
-                    bins[(ablate & 1024) ? (size_t)cidx : bins_index(pl.z, cidx, T_out)] = (unsigned short)(
+                out[(size_t)pl.y * C + cidx] = write_clim ? clim : a;
+                if (do_bins)
+                    bins[bins_index(pl.z, cidx, T_out)] = (unsigned short)(
                         arange_tab ? digitize_arange(a, e_first, e_delta, e_last, nb, inv_width)
                                    : digitize_bin(a, e, nb, inv_width));
-                if ((ablate & 96) == 96 && a == 12345.678f) out[cidx] = a;
             }
         }
         ring_push(i, slot0, (pl.x >= 0) ? s : nan_f());
@@ -231,34 +218,24 @@ k_shifting(const float* __restrict__ x, long T, long C, const int4* __restrict__
         const long r0 = (long)pl[0].x - lo;
         if (fast && SEXACT && r0 >= 0 && r0 + NL <= T) {
             // D consecutive timesteps, whole batch inside the series: NL unconditional row loads, no predicates
-            if (ablate & 4) {
+            const float* rowp = x + (size_t)r0 * C;
 #pragma unroll
-                for (int j = 0; j < NL; ++j) xw[j] = (float)(j + y) * 0.25f;
-            } else {
-                const float* rowp = x + (size_t)r0 * C;
-#pragma unroll
-                for (int j = 0; j < NL; ++j) {
-                    xw[j] = rowp[cidx];
-                    rowp += C;
-                }
+            for (int j = 0; j < NL; ++j) {
+                xw[j] = rowp[cidx];
+                rowp += C;
             }
             float sacc[D], xcen[D], smo[D];
-            bool all_out = !ablate;
+            bool all_out = true;
 #pragma unroll
             for (int i = 0; i < D; ++i) {
                 sacc[i] = xw[i];
                 xcen[i] = xw[i + SCAP / 2];
                 all_out &= pl[i].y >= 0;
             }
-            if (ablate & 2) {
 #pragma unroll
-                for (int i = 0; i < D; ++i) sacc[i] = xw[i] + xw[NL - 1];
-            } else {
+            for (int k = 1; k < SCAP; ++k)
 #pragma unroll
-                for (int k = 1; k < SCAP; ++k)
-#pragma unroll
-                    for (int i = 0; i < D; ++i) sacc[i] += xw[i + k];
-            }
+                for (int i = 0; i < D; ++i) sacc[i] += xw[i + k];
 #pragma unroll
             for (int i = 0; i < D; ++i) smo[i] = sacc[i] / Sf;
             if (all_out) {
@@ -579,19 +556,16 @@ __global__ void k_shift_classify(const int4* __restrict__ year_plan, int n_cal, 
 // years of the wave's 4 dayofyears wait as packed key pairs in LDS (one uniform slot per year, no per-lane counters);
 // every 15th year the wave sorts them (63 packed compare-exchanges per pair of dayofyears) and writes one list per
 // dayofyear as two 16-byte chunks per lane -- whole 1-KiB lines per wave, nothing is ever read back.
-#ifndef SHIFT_EXP
-#define SHIFT_EXP 0  // timing experiments (wrong results by design), alt builds only: 1 no barriers, 2 no row prefetch, 4 no anomaly stores, 8 no keys, 16 no smoothing sums, 32 no climatology sums
-#endif
 #define SHIFT_LIST 15   // output years per emitted list (15 x 2 pairs x 256 B x 4 waves + one 9-KiB stage = 39 KiB: 4 workgroups per CU)
 struct TailOut {
     uint4* lists;              // [366][NPER][2][C] chunks
     unsigned* aux;             // [366][C] count | samples beyond the table (marex_tails.hip.h)
     const int* doy_start;      // [367] first bin-matrix row of every dayofyear (key positions = row - doy_start)
     int nper;
-    unsigned long long* dbg;   // debug counters (-DSHIFT_STAMPS builds: phase timers)
+    unsigned long long* dbg;   // debug counters
 };
 
-template <int W, bool TAILS, int S = 21, bool DMA = false>
+template <int W, bool TAILS, int S = 21>
 __global__ void __launch_bounds__(256)
 k_shift_fast(const float* __restrict__ x, long T, long C, const int4* __restrict__ fplan, int n_cal,
              const int* __restrict__ info, int write_clim, const float* __restrict__ edges, int nb, long T_out, float* __restrict__ out, unsigned short* __restrict__ bins, unsigned char* __restrict__ mask,
@@ -610,17 +584,9 @@ k_shift_fast(const float* __restrict__ x, long T, long C, const int4* __restrict
     static_assert((S & 1) == 1 && S >= 5 && S <= 25, "k_shift_fast: odd smoothing widths 5..25");
     constexpr int H = S / 2, NPAIR = (S + 3) / 2, NST = S + 15, RPW = (NST + 3) / 4;  // RPW: rows each wave stages per year
     constexpr int NSTAGE = TAILS ? 1 : 2;
-    // DMA (TAILS only): the rows go from memory straight into the stage (DmaRows above) and the rows of the year AFTER next are
-    // prefetched into the L2 through a scratch kilobyte; every wave issues the same instructions, so the stage has 4 RPW rows
-    static_assert(!DMA || TAILS, "k_shift_fast: LDS-DMA staging is built for the single stage buffer of the TAILS variant");
-    constexpr int NROWS = DMA ? 4 * RPW : NST;
+    constexpr int NROWS = NST;
     __shared__ float stage[NSTAGE][NROWS * 64];
-    __shared__ float pf_dump[DMA ? 256 : 1];
     __shared__ unsigned newkeys[TAILS ? 4 : 1][2][TAILS ? SHIFT_LIST : 1][64];  // [wave][pair of dayofyears][year slot][lane]
-#ifdef SHIFT_PAD  // experiment: extra LDS (floats) to lower the number of resident workgroups
-    __shared__ float lds_pad[SHIFT_PAD];
-    if (T == -12345) out[0] = lds_pad[threadIdx.x];
-#endif
     const bool mine = chunk < 92 && info[chunk] != 0;  // wave-uniform; the other waves only help staging
     const int d0 = mine ? chunk * 4 : 0;
     // per-year records (k_shift_classify): the wave's chunk, and the workgroup's first chunk (its first timestep places the
@@ -669,33 +635,7 @@ k_shift_fast(const float* __restrict__ x, long T, long C, const int4* __restrict
     };
     int tb_cur = fplan[(size_t)(bc * 4) * 2].x;
     int tb_n1 = prec[1].w;  // year 1 (record of year 0), known one iteration ahead of its row prefetch
-    // DMA: lane offsets of the 4-row instruction (lane 16 r + s: row r, cells 4 s .. 4 s + 3 of the group; a segment beyond C --
-    // C is a multiple of 4 on this path -- reads the last four cells instead: those lanes are masked wherever they store)
-    typedef __attribute__((address_space(3))) float lds_f32;
-    unsigned dma_voff4 = 0, dma_lds = 0, dma_dump = 0;
-    if (DMA) {
-        const long c4 = (long)cg * 64 + (lane & 15) * 4;
-        dma_voff4 = (unsigned)(lane >> 4) * (unsigned)rowb + (unsigned)(c4 + 4 <= C ? c4 : C - 4) * 4u;
-        dma_lds = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(size_t)(lds_f32*)&stage[0][(RPW * wave) * 64]);
-        dma_dump = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(size_t)(lds_f32*)&pf_dump[0]);
-    }
-    // rows 365 days after a staged block lie inside the series (the prefetch of the year after next: 365 or 366 days on, the
-    // difference is one row of 4 RPW)
-    auto pf_ok = [&](int tb) { return (long)tb + 365 - H + NROWS <= T; };
-    // stage the rows of the year whose workgroup block starts at timestep tb (+ prefetch the same rows 365 days on)
-    auto dma_year = [&](int tb, bool pf) {
-        const tl_out_rsrc_t rs = tl_out_make_rsrc(x + (size_t)(tb - H + RPW * wave) * C);
-        DmaRows<RPW>::issue(rs, dma_voff4, voff, dma_lds, 256u, 0u, (unsigned)rowb);
-        if (pf) DmaRows<RPW>::issue(rs, dma_voff4, voff, dma_dump, 0u, 365u * (unsigned)rowb, (unsigned)rowb);
-    };
-    bool dma_pf = false;
-    if (DMA) {
-        if (stage_ok(tb_cur)) {
-            dma_year(tb_cur, pf_ok(tb_cur));
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        asm volatile("s_barrier" ::: "memory");
-    } else {
+    {
         float nx[RPW];
         if (stage_ok(tb_cur)) {
             stage_load(tb_cur, nx);
@@ -744,7 +684,7 @@ k_shift_fast(const float* __restrict__ x, long T, long C, const int4* __restrict
                             w[i] = h == 0 ? ((a & 0xFFFFu) | (b << 16)) : ((a >> 16) | (b & 0xFFFF0000u));
                         }
                         const int li = __builtin_amdgcn_readfirstlane((di * tails.nper + t_list) * 2 + jj);
-                        if (!DMA || active) tl_out_store(rl, lvoff, (unsigned)li * (unsigned)C * 16u, w);
+                        tl_out_store(rl, lvoff, (unsigned)li * (unsigned)C * 16u, w);
                     }
                 }
             }
@@ -754,24 +694,15 @@ k_shift_fast(const float* __restrict__ x, long T, long C, const int4* __restrict
     };
 
     int4 nA = prec[0], nB = prec[1];  // year 0
-#ifdef SHIFT_STAMPS
-    unsigned long long st_top = 0, st_mid = 0, st_end = 0, st_flush = 0;
-#define SSTAMP(v) const unsigned long long v = __builtin_amdgcn_s_memtime()
-#else
-#define SSTAMP(v)
-#endif
     auto one_year = [&](int y, auto Jc) {
         constexpr int J = decltype(Jc)::value;
-        SSTAMP(tsA);
         const int4 pA = nA, pB = nB;  // {first timestep, first output row, dayofyears present, row 0}, {rows 1..3, next tb}
         const int tb = tb_cur;
-        float nx[RPW];  // (unused with DMA)
+        float nx[RPW];
         // next year's rows, one iteration ahead (its first timestep arrived during the previous iteration)
-        const bool stage_next = y + 1 < n_cal && stage_ok(tb_n1) && !(SHIFT_EXP & 2);
-        if (!DMA && stage_next) stage_load(tb_n1, nx);
+        const bool stage_next = y + 1 < n_cal && stage_ok(tb_n1);
+        if (stage_next) stage_load(tb_n1, nx);
         v2f smA = splat2(qnan), smB = splat2(qnan);
-        v2f oA = splat2(0.f), oB = splat2(0.f);  // DMA: this year's output rows, stored at the end
-        int o_n = 0;
         v2f xp[NPAIR];  // xp[m] = rows (r0 + 2m, r0 + 2m + 1), r0 = first timestep - H
         const bool staged = mine && pA.z > 0 && stage_ok(tb) && pA.x == tb + 4 * wave;
         if (staged) {
@@ -785,12 +716,7 @@ k_shift_fast(const float* __restrict__ x, long T, long C, const int4* __restrict
         if (TAILS) {
             // single stage buffer: every wave has its rows in registers before anyone overwrites the buffer with the next
             // year's (LDS traffic only: no vector-memory wait here, the row prefetch stays in flight)
-            if (!(SHIFT_EXP & 1)) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            if (DMA && stage_next) {
-                // the stage is free: next year's rows on their way into it, the rows of the year after next on their way into the L2
-                dma_pf = y + 2 < n_cal && pf_ok(tb_n1);
-                dma_year(tb_n1, dma_pf);
-            }
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         }
         else asm volatile("" ::: "memory");
         // scalar loads of the years to come go out HERE, after the wait for the staged rows: they are in flight during the
@@ -802,7 +728,6 @@ k_shift_fast(const float* __restrict__ x, long T, long C, const int4* __restrict
             tb_cur = tb_n1;
             tb_n1 = nB.w;  // first timestep of the workgroup in year y + 2
         }
-        SSTAMP(tsB);
         if (mine && pA.z > 0) {
             const long r0 = (long)pA.x - H;
             const bool edge = r0 < 0 || r0 + 2 * NPAIR > T;
@@ -828,11 +753,11 @@ k_shift_fast(const float* __restrict__ x, long T, long C, const int4* __restrict
             // high halves of their pairs)
             v2f accA = (v2f){xp[0].x, -0.0f};
 #pragma unroll
-            for (int s = 1; s <= ((SHIFT_EXP & 16) ? 2 : S - 1); ++s) accA = (s & 1) ? pk_add_bc_hi(accA, xp[s >> 1]) : pk_add_bc_lo(accA, xp[s >> 1]);
+            for (int s = 1; s <= S - 1; ++s) accA = (s & 1) ? pk_add_bc_hi(accA, xp[s >> 1]) : pk_add_bc_lo(accA, xp[s >> 1]);
             accA.y += xp[S >> 1].y;
             v2f accB = (v2f){xp[1].x, -0.0f};
 #pragma unroll
-            for (int s = 3; s <= ((SHIFT_EXP & 16) ? 4 : S + 1); ++s) accB = (s & 1) ? pk_add_bc_hi(accB, xp[s >> 1]) : pk_add_bc_lo(accB, xp[s >> 1]);
+            for (int s = 3; s <= S + 1; ++s) accB = (s & 1) ? pk_add_bc_hi(accB, xp[s >> 1]) : pk_add_bc_lo(accB, xp[s >> 1]);
             accB.y += xp[(S + 2) >> 1].y;
             smA = div_const2(accA, Sf, yS);
             smB = div_const2(accB, Sf, yS);
@@ -860,7 +785,7 @@ k_shift_fast(const float* __restrict__ x, long T, long C, const int4* __restrict
             if (pA.y >= 0) {  // output rows
                 v2f sA = splat2(0.f), sB = splat2(0.f);
 #pragma unroll
-                for (int j = 0; j < ((SHIFT_EXP & 32) ? 2 : W); ++j) {
+                for (int j = 0; j < W; ++j) {
                     sA = sA + rA[J + j];
                     sB = sB + rB[J + j];
                 }
@@ -900,20 +825,12 @@ k_shift_fast(const float* __restrict__ x, long T, long C, const int4* __restrict
                     if (!(climB.y == climB.y)) climB.y = acc[3] / (float)n[3];
                 }
                 const v2f aA = xcA - climA, aB = xcB - climB;
-                if (DMA) {  // stored at the end of the year, behind the wait for the staged rows (the stores stay younger than it)
-                    oA = write_clim ? climA : aA;
-                    oB = write_clim ? climB : aB;
-                    o_n = pA.z;
-                } else {
                 const rsrc_t ro = make_rsrc(out + (size_t)pA.y * C);
-                if (!(SHIFT_EXP & 4) || aA.x == 12345.678f) {
-                    stb_f32(ro, voff, 0, write_clim ? climA.x : aA.x);
-                    if (has1) stb_f32(ro, voff, rowb, write_clim ? climA.y : aA.y);
-                    if (has2) stb_f32(ro, voff, 2 * rowb, write_clim ? climB.x : aB.x);
-                    if (has3) stb_f32(ro, voff, 3 * rowb, write_clim ? climB.y : aB.y);
-                }
-                }
-                if ((do_bins || TAILS) && (!(SHIFT_EXP & 8) || aB.y == 12345.678f)) {
+                stb_f32(ro, voff, 0, write_clim ? climA.x : aA.x);
+                if (has1) stb_f32(ro, voff, rowb, write_clim ? climA.y : aA.y);
+                if (has2) stb_f32(ro, voff, 2 * rowb, write_clim ? climB.x : aB.x);
+                if (has3) stb_f32(ro, voff, 3 * rowb, write_clim ? climB.y : aB.y);
+                if (do_bins || TAILS) {
                     // np.digitize(a, edges) - 1 on the arange table (contract C4): the guess, biased down, is the
                     // true bin or the one below (k_shift_classify checked the error bound); one comparison with
                     // the edge above it -- recomputed with the table's own arithmetic -- settles which.  A NaN
@@ -974,34 +891,8 @@ k_shift_fast(const float* __restrict__ x, long T, long C, const int4* __restrict
         }
         rA[J + W] = smA;  // year y joins the history
         rB[J + W] = smB;
-        SSTAMP(tsC);
-        if (DMA) {
-            // the staged rows of next year have landed (everything older than the prefetch loads issued behind them), then the
-            // anomaly stores, then the barrier that lets every wave read the stage
-            if (stage_next) {
-                if (dma_pf)
-                    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DmaRows<RPW>::NL) : "memory");
-                else
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
-            if (o_n > 0 && active) {  // lanes beyond C hold other cells' rows on this path: they store nothing
-                const rsrc_t ro = make_rsrc(out + (size_t)pA.y * C);
-                stb_f32(ro, voff, 0, oA.x);
-                if (o_n > 1) stb_f32(ro, voff, rowb, oA.y);
-                if (o_n > 2) stb_f32(ro, voff, 2 * rowb, oB.x);
-                if (o_n > 3) stb_f32(ro, voff, 3 * rowb, oB.y);
-            }
-            asm volatile("s_barrier" ::: "memory");
-        } else {
         if (stage_next) stage_store((y + 1) & 1, nx);
-        if (!(SHIFT_EXP & 1)) __syncthreads();
-        }
-#ifdef SHIFT_STAMPS
-        const unsigned long long tsD = __builtin_amdgcn_s_memtime();
-        st_top += tsB - tsA;
-        st_mid += tsC - tsB;
-        st_end += tsD - tsC;
-#endif
+        __syncthreads();
     };
     for (int y = 0; y < n_cal; y += 2) {
         one_year(y, std::integral_constant<int, 0>{});
@@ -1028,14 +919,6 @@ k_shift_fast(const float* __restrict__ x, long T, long C, const int4* __restrict
         }
     }
     if (invalid_count && active && n_invalid) atomicAdd(&invalid_count[c], n_invalid);
-#ifdef SHIFT_STAMPS
-    if (TAILS && lane == 0 && tails.dbg) {
-        atomicAdd(&tails.dbg[5], st_top);
-        atomicAdd(&tails.dbg[6], st_mid);
-        atomicAdd(&tails.dbg[7], st_end);
-        atomicAdd(&tails.dbg[4], 1ull);
-    }
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1161,7 +1044,6 @@ k_shift_lean(const float* __restrict__ x, int T, int C, const int4* __restrict__
     int n_invalid = 0;
     unsigned t_cntA = 0, t_cntB = 0, t_ovfA = 0, t_ovfB = 0;
     int t_slot = 0, t_list = 0;
-    int n_lean = 0, n_gen = 0;  // years of this wave that took the straight-line / the general body (debug counters 6 / 7)
     auto tails_flush = [&]() __attribute__((always_inline)) {
         const tl_out_rsrc_t rl = tl_out_make_rsrc(tails.lists + (size_t)d0 * tails.nper * 2 * (size_t)C);
         const unsigned lvoff = cidx * 16u;
@@ -1539,10 +1421,8 @@ k_shift_lean(const float* __restrict__ x, int T, int C, const int4* __restrict__
         const int4 cA = nA, cB = nB;                                                                            \
         if (mine && (cA.x & LR_REG)) {                                                                          \
             lean_year(std::integral_constant<int, J>{}, cA, cB);                                                \
-            ++n_lean;                                                                                           \
         } else {                                                                                                \
             general_year(std::integral_constant<int, J>{}, yy, cA);                                             \
-            n_gen += mine ? 1 : 0;                                                                              \
         }                                                                                                       \
         asm volatile("s_barrier" ::: "memory"); /* every wave's DMA has landed: the stage holds next year's rows */ \
         if (!BINS && t_slot == SHIFT_LIST) tails_flush();                                                       \
@@ -1571,12 +1451,6 @@ k_shift_lean(const float* __restrict__ x, int T, int C, const int4* __restrict__
         }
     }
     if (invalid_count && active && n_invalid) atomicAdd(&invalid_count[c], n_invalid);
-#ifdef MAREX_LEAN_COUNTERS  // diagnostic builds only: two atomics per wave on two addresses cost 4 ms on a 10-yr field (750 000 waves)
-    if (tails.dbg && lane == 0) {
-        atomicAdd(&tails.dbg[6], (unsigned long long)n_lean);
-        atomicAdd(&tails.dbg[7], (unsigned long long)n_gen);
-    }
-#endif
 }
 
 static bool lean_instance(int W, int S) { return S == 21 && (W == 15 || W == 5); }
@@ -1613,7 +1487,7 @@ static int launch_shifting(marex_ctx* ctx, const ShiftArgs& a) {
         HIP_TRY(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(kern, dim3(xcd_grid(ncb, nchunks)), dim3(256), lds, ctx->stream, a.x, (long)a.T, (long)a.C,
                        a.year_plan, a.n_cal, a.W, a.S, a.write_clim, a.edges, a.nb, (long)a.T_out, a.out, a.bins,
-                       a.mask, a.invalid_count, ncb, nchunks, MAREX_ABLATE_OPT(ctx, "SHIFT_ABLATE"), D == 4 ? a.skip : nullptr);
+                       a.mask, a.invalid_count, ncb, nchunks, D == 4 ? a.skip : nullptr);
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }
@@ -1635,20 +1509,11 @@ static void launch_shift_fast(marex_ctx* ctx, const ShiftArgs& a) {
                                    a.bins, (long)a.T_out);
         }
     } else if (a.tails.lists) {
-        // LDS-DMA staging + L2 prefetch (option SHIFT_DMA=1; measured round 3 on a 100-yr band: 12.17 ms against 11.84 ms with
-        // the rows staged through VGPRs -- the kernel is bound by instruction issue, not by the latency of its loads -- so it
-        // is off by default and instantiated for the two benchmark shapes only): whole 16-byte segments of a row are either
-        // inside the field or beyond it (C a multiple of 4), and the prefetch offset of 365 rows fits the 32-bit buffer offset
-        constexpr int RPW = (S + 15 + 3) / 4;
-        constexpr bool has_dma = S == 21 && (W == 15 || W == 5);
-        const bool dma = has_dma && ctx_opt(ctx, "SHIFT_DMA", 0) != 0 && a.C >= 4 && a.C % 4 == 0 &&
-                         (unsigned long long)(365 + 4 * RPW + 4) * (unsigned long long)a.C * 4ull < 0xFFFFFFFFull;
-        if (dma)
-            hipLaunchKernelGGL((k_shift_fast<W, true, S, has_dma>), MAREX_SF_ARGS);
-        else
-            hipLaunchKernelGGL((k_shift_fast<W, true, S, false>), MAREX_SF_ARGS);
+        // (staging the rows by LDS-DMA with an L2 prefetch a year ahead measured 12.17 ms against 11.84 ms on a 100-yr band in
+        // round 3: the kernel is bound by instruction issue, not by the latency of its loads)
+        hipLaunchKernelGGL((k_shift_fast<W, true, S>), MAREX_SF_ARGS);
     } else {
-        hipLaunchKernelGGL((k_shift_fast<W, false, S, false>), MAREX_SF_ARGS);
+        hipLaunchKernelGGL((k_shift_fast<W, false, S>), MAREX_SF_ARGS);
     }
 #undef MAREX_SF_ARGS
 }
@@ -1683,7 +1548,7 @@ static int shifting_impl(marex_ctx* ctx, const char* who, const float* x, int64_
     const bool fast_w = W == 3 || W == 4 || W == 5 || W == 6 || W == 7 || W == 10 || W == 13 || W == 15;
     const bool fast_ws = S == 21 ? fast_w : ((S == 11 || S == 15) && (W == 5 || W == 10 || W == 15));
     const bool fast_cfg = ctx_opt(ctx, "SHIFT_FAST", 1) != 0 && fast_ws && forceD == 0 && T >= S + 3 &&
-                          T_out < (1 << 24) && C < (1 << 24) && MAREX_ABLATE_OPT(ctx, "SHIFT_ABLATE") == 0;
+                          T_out < (1 << 24) && C < (1 << 24);
     if (all_fast_possible) *all_fast_possible = fast_cfg;
     if (fast_cfg && !ctx->shift_info) HIP_TRY(ctx, hipMalloc((void**)&ctx->shift_info, SHIFT_INFO_WORDS * sizeof(int)));
     if (fast_cfg && ctx->shift_plan_years < (size_t)n_cal_years) {

@@ -233,14 +233,7 @@ int marex_tail_extract_impl(marex_ctx* ctx, const float* anom, int64_t T_out, in
     if (((uintptr_t)lists & 15) != 0) return fail(ctx, -1, "marex_tail_extract_f32: lists must be 16-byte aligned");
     if (C * 4 > 0xFFFFFFFFll) return fail(ctx, -4, "marex_tail_extract_f32: more than 2^30 cells");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t need = (size_t)T_out * sizeof(long long);
-    if (need > ctx->row_off_bytes) {
-        if (ctx->row_off) HIP_TRY(ctx, hipFree(ctx->row_off));
-        ctx->row_off = nullptr;
-        ctx->row_off_bytes = 0;
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->row_off, need));
-        ctx->row_off_bytes = need;
-    }
+    HIP_TRY(ctx, grow_scratch(ctx->row_off, ctx->row_off_bytes, (size_t)T_out * sizeof(long long)));
     const unsigned ncb = (unsigned)((C + 255) / 256);
     unsigned chunks = (2048 + ncb - 1) / ncb;  // enough workgroups to fill the chip whatever the number of cells
     chunks = chunks < 1 ? 1 : (chunks > 61 ? 61 : chunks);
@@ -395,7 +388,7 @@ struct TailBucket {
 // bucket instead of a modulo and a 64-bit product per use, and the key loop that needs no count in front of it (tl_scan_chunk).
 // LN = 0: list geometry from the arguments.
 template <int P, int TC, int NT, int NPERT, int TR_ = NT / TC, int LN = 0, int LC = 0>
-__global__ void __launch_bounds__(NT, NT == 256 ? 4 : (NT == 512 ? 2 : 1))
+__global__ void __launch_bounds__(NT, NT == 256 ? 4 : 1)
 k_thr_tails(const uint4* __restrict__ lists, const unsigned* __restrict__ aux, int NPER_rt, int nch_rt, const float* __restrict__ anom,
             long C, int ny, int nx, int row0, int row1, int tiles_x, int Dd, const float* __restrict__ centres, int nb, double q,
             int wd, float lower_bound, float upper_bound, float* __restrict__ thr, marex_thr_stats* __restrict__ stats,
@@ -765,16 +758,9 @@ k_thr_tails(const uint4* __restrict__ lists, const unsigned* __restrict__ aux, i
     const unsigned* out_a = aux + (size_t)out_d * C;
 #pragma unroll
     for (int p = 0; p < NPF; ++p) pin.c0[p] = pout.c0[p] = make_uint4(0, 0, 0, 0);
-#ifdef MAREX_STAMPS
-    unsigned long long st_p1 = 0, st_p2 = 0, st_bar = 0;
-#define STAMP() __builtin_amdgcn_s_memtime()
-#endif
     for (int dd = 0; dd < ndays; ++dd) {
         const int d = d_begin + dd;
         const int dpar = dd & 1;
-#ifdef MAREX_STAMPS
-        const unsigned long long tA = STAMP();
-#endif
         // ---------------- P1: this lane's column for day d
         if (need_rebuild) {
             rebuild(d);
@@ -803,24 +789,13 @@ k_thr_tails(const uint4* __restrict__ lists, const unsigned* __restrict__ aux, i
             pin = load_bucket(wrap(d + 1 + pd));
             pout = load_bucket(wrap(d - pd));
         }
-#ifdef MAREX_STAMPS
-        const unsigned long long tB = STAMP();
-        st_p1 += tB - tA;
-#endif
         // ---------------- P2: quantile level of every output cell; stragglers move the band
         bool resolved = !(is_out && !land);
         int tried_lo = B0, tried_hi = B0;
         bool excursion = false;
         for (int pass = 0;; ++pass) {
             const int par = pass & 1;
-#ifdef MAREX_STAMPS
-            const unsigned long long tC0 = STAMP();
-#endif
             __syncthreads();
-#ifdef MAREX_STAMPS
-            const unsigned long long tC = STAMP();
-            st_bar += tC - tC0;
-#endif
             if (t == 0) {
                 s_lo[par ^ 1] = 0;
                 s_hi[par ^ 1] = 0;
@@ -870,14 +845,7 @@ k_thr_tails(const uint4* __restrict__ lists, const unsigned* __restrict__ aux, i
                     atomicMax(&s_iumax[dpar], whi);
                 }
             }
-#ifdef MAREX_STAMPS
-            const unsigned long long tD = STAMP();
-            st_p2 += tD - tC;
-#endif
             __syncthreads();
-#ifdef MAREX_STAMPS
-            st_bar += STAMP() - tD;
-#endif
             const int lo = s_lo[par], hi = s_hi[par];
             if (!lo && !hi) break;
             if (pass >= pass_limit) {  // cannot happen while the bands of the passes overlap (static_assert above), but a wave must
@@ -933,18 +901,6 @@ k_thr_tails(const uint4* __restrict__ lists, const unsigned* __restrict__ aux, i
         if (nlow) atomicAdd(&stats->n_too_low, nlow);
         if (nhigh) atomicAdd(&stats->n_too_high, nhigh);
     }
-#ifdef MAREX_STAMPS
-#ifdef MAREX_STAMPS_WAVE  // phase timers of wave MAREX_STAMPS_WAVE (-1: a different wave per tile) instead of wave 0
-    const int st_wave = MAREX_STAMPS_WAVE >= 0 ? MAREX_STAMPS_WAVE : (int)((blockIdx.x + blockIdx.y) % (NT / 64));
-    if (dbg && t == st_wave * 64) {
-#else
-    if (dbg && t == 0) {
-#endif
-        atomicAdd(&dbg[5], st_p1);
-        atomicAdd(&dbg[6], st_p2);
-        atomicAdd(&dbg[7], st_bar);
-    }
-#endif
     if (dbg && t == 0) {
         atomicAdd(&dbg[0], n_rebuild);
         atomicAdd(&dbg[2], n_pass);
@@ -1198,7 +1154,7 @@ extern "C" int marex_hobday_thresholds_tails_f32(marex_ctx* ctx, const void* lis
         LaunchTimer lt(ctx, MAREX_K_THRESHOLDS);
         const size_t lds = (size_t)((wd * NPER + 3) & ~3) * 64 * sizeof(uint4);
         const int nslot = (wd * NPER + 3) & ~3;
-        const bool cached = nslot == 12 && ctx_opt(ctx, "THR_CELLS_CACHE", 1);  // the default 11-day window of single-list buckets
+        const bool cached = nslot == 12;  // the default 11-day window of single-list buckets
         if (lds > 64 * 1024) HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_thr_cells<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(cached ? k_thr_cells<12> : k_thr_cells<0>, dim3((unsigned)ncg, (unsigned)nblk), dim3(64), lds, ctx->stream,
                            reinterpret_cast<const uint4*>(lists), aux, NPER, nch, anom, (long)C, c0, c1, nblk, centres, nb, q, wd,
@@ -1209,14 +1165,9 @@ extern "C" int marex_hobday_thresholds_tails_f32(marex_ctx* ctx, const void* lis
     if (NPER > 6)
         return fail(ctx, -4, "marex_hobday_thresholds_tails_f32: %d rows per bucket in lists of %d: more than 6 lists", max_bucket, list_rows);
     const int tile_pref = ctx_opt(ctx, "THR_TILE", (ny > 0 && p > 0 && max_bucket >= 24) ? 32 : 16);
-    // 3216 (experiments): 32 wide x 16 tall tiles on 512 threads, P = 2 -- half a CU's LDS and registers per workgroup, so that
-    // workgroups of ANOTHER kernel (the anomaly kernel of the neighbouring stream) can share the CU; THR_LDS_PAD (KiB of unused
-    // dynamic LDS per workgroup) keeps a second tile of this kernel off the CU
-    const bool half = (ny > 0 && p == 2) && tile_pref == 3216 && (row1 - row0) >= 12 && nx >= 16;
-    const bool big = !half && (ny > 0 && p > 0) && tile_pref == 32 && (row1 - row0) >= 16 && nx >= 16;
-    const int NT = big ? 1024 : (half ? 512 : 256);
+    const bool big = (ny > 0 && p > 0) && tile_pref == 32 && (row1 - row0) >= 16 && nx >= 16;
+    const int NT = big ? 1024 : 256;
     int TR = (ny > 0 && p > 0) ? (big ? 32 : 16) : 1, TC = NT / TR;
-    const size_t lds_pad = (size_t)ctx_opt(ctx, "THR_LDS_PAD", 0) * 1024;
     bool tall = false;
     if (big && p == 2 && ctx_opt(ctx, "THR_TALL", 1)) {
         auto ntiles = [&](int tr, int tc) {
@@ -1231,7 +1182,7 @@ extern "C" int marex_hobday_thresholds_tails_f32(marex_ctx* ctx, const void* lis
     if (Dd < 1 || Dd > NDOY) {
         // every block pays a window build-up of wd buckets; pick the block length with the least total work per CU slot
         const long cus = device_cus(ctx), tiles = (long)tiles_x * tiles_y;
-        const long slots = cus * (big ? 1 : (half ? 2 : 4));
+        const long slots = cus * (big ? 1 : 4);
         long best = -1;
         for (int d = 16; d <= NDOY; ++d) {
             const long blocks = tiles * ((NDOY + d - 1) / d);
@@ -1249,11 +1200,11 @@ extern "C" int marex_hobday_thresholds_tails_f32(marex_ctx* ctx, const void* lis
 #define MAREX_TT_LAUNCH(PP, TCC, NTT, ...)                                                                                           \
     do {                                                                                                                             \
         if (NPER <= 1)                                                                                                               \
-            hipLaunchKernelGGL((k_thr_tails<PP, TCC, NTT, 1, ##__VA_ARGS__>), grid, dim3(NTT), lds_pad, ctx->stream, MAREX_TT_ARGS); \
+            hipLaunchKernelGGL((k_thr_tails<PP, TCC, NTT, 1, ##__VA_ARGS__>), grid, dim3(NTT), 0, ctx->stream, MAREX_TT_ARGS);       \
         else if (NPER <= 2)                                                                                                          \
-            hipLaunchKernelGGL((k_thr_tails<PP, TCC, NTT, 2, ##__VA_ARGS__>), grid, dim3(NTT), lds_pad, ctx->stream, MAREX_TT_ARGS); \
+            hipLaunchKernelGGL((k_thr_tails<PP, TCC, NTT, 2, ##__VA_ARGS__>), grid, dim3(NTT), 0, ctx->stream, MAREX_TT_ARGS);       \
         else /* two lists prefetched across the barrier, the others loaded at use */                                                 \
-            hipLaunchKernelGGL((k_thr_tails<PP, TCC, NTT, 3, ##__VA_ARGS__>), grid, dim3(NTT), lds_pad, ctx->stream, MAREX_TT_ARGS); \
+            hipLaunchKernelGGL((k_thr_tails<PP, TCC, NTT, 3, ##__VA_ARGS__>), grid, dim3(NTT), 0, ctx->stream, MAREX_TT_ARGS);       \
     } while (0)
     // the lean instance (k_thr_tails, LN x LC): 6 lists of 2 chunks -- the lists the anomaly kernel emits for buckets of 76..90
     // samples, a century of days -- on the 1024-thread tiles of a 5 x 5 pooling window; THR_LEAN=0 keeps the general body, which
@@ -1262,13 +1213,11 @@ extern "C" int marex_hobday_thresholds_tails_f32(marex_ctx* ctx, const void* lis
     {
         LaunchTimer lt(ctx, MAREX_K_THRESHOLDS);
         if (lean && tall)
-            hipLaunchKernelGGL((k_thr_tails<2, 30, 1024, 3, 34, 6, 2>), grid, dim3(1024), lds_pad, ctx->stream, MAREX_TT_ARGS);
+            hipLaunchKernelGGL((k_thr_tails<2, 30, 1024, 3, 34, 6, 2>), grid, dim3(1024), 0, ctx->stream, MAREX_TT_ARGS);
         else if (lean)
-            hipLaunchKernelGGL((k_thr_tails<2, 32, 1024, 3, 32, 6, 2>), grid, dim3(1024), lds_pad, ctx->stream, MAREX_TT_ARGS);
+            hipLaunchKernelGGL((k_thr_tails<2, 32, 1024, 3, 32, 6, 2>), grid, dim3(1024), 0, ctx->stream, MAREX_TT_ARGS);
         else if (TR == 1)
             MAREX_TT_LAUNCH(0, 256, 256);
-        else if (half)
-            MAREX_TT_LAUNCH(2, 32, 512, 16);
         else if (big && p == 1)
             MAREX_TT_LAUNCH(1, 32, 1024);
         else if (big && p == 2 && tall)
@@ -1847,38 +1796,20 @@ extern "C" int marex_mask_ge_doy_tails_f32(marex_ctx* ctx, const void* lists, co
         // 122 chunks 2.11 ms; the whole pass 125.7 -> 124.3 ms)
         unsigned chunks = (16384 + ncb - 1) / ncb;
         chunks = chunks < MASK_DOY_CHUNKS ? MASK_DOY_CHUNKS : (chunks > 61 ? 61 : chunks);
-        {
-            const int forced = ctx_opt(ctx, "MASK_CHUNKS", 0);  // dayofyear chunks of the grid (experiments)
-            if (forced >= 1 && forced <= 366) chunks = (unsigned)forced;
-        }
         unsigned long long* dbg = ctx_debug_counters(ctx);
         const uint4* tl = reinterpret_cast<const uint4*>(lists);
         // byte offset of every kept row of the MASK array (one byte per cell) in dayofyear order
         const size_t need = (size_t)T_out * sizeof(long long);
-        if (need > ctx->row_off_mask_bytes) {
-            if (ctx->row_off_mask) HIP_TRY(ctx, hipFree(ctx->row_off_mask));
-            ctx->row_off_mask = nullptr;
-            ctx->row_off_mask_bytes = 0;
-            HIP_TRY(ctx, hipMalloc((void**)&ctx->row_off_mask, need));
-            ctx->row_off_mask_bytes = need;
-        }
+        HIP_TRY(ctx, grow_scratch(ctx->row_off_mask, ctx->row_off_mask_bytes, need));
         hipLaunchKernelGGL(k_row_offsets, dim3((unsigned)((T_out + 255) / 256)), dim3(256), 0, ctx->stream, doy_rows, (long)T_out, (long)C,
                            ctx->row_off_mask, 1);
-        const size_t need4 = (size_t)T_out * sizeof(long long);
-        if (need4 > ctx->row_off_bytes) {
-            if (ctx->row_off) HIP_TRY(ctx, hipFree(ctx->row_off));
-            ctx->row_off = nullptr;
-            ctx->row_off_bytes = 0;
-            HIP_TRY(ctx, hipMalloc((void**)&ctx->row_off, need4));
-            ctx->row_off_bytes = need4;
-        }
+        HIP_TRY(ctx, grow_scratch(ctx->row_off, ctx->row_off_bytes, need));
         hipLaunchKernelGGL(k_row_offsets, dim3((unsigned)((T_out + 255) / 256)), dim3(256), 0, ctx->stream, doy_rows, (long)T_out, (long)C,
                            ctx->row_off, (int)sizeof(float));
 #define MAREX_MT_ARGS tl, aux, NPER, nch, anom, edges, nb, thr_doy_major, doy_start, doy_rows, ctx->row_off_mask, ctx->row_off, (long)C, (long)c0, (long)c1, extreme, n_true, dbg
-        const int grp = ctx_opt(ctx, "MASK_GROUP", 0);  // lists handled at once (experiments: 1, 2, 3)
-        if (NPER <= 1 || grp == 1)
+        if (NPER <= 1)
             hipLaunchKernelGGL(k_mask_tails<1>, dim3(ncb, chunks), dim3(256), 0, ctx->stream, MAREX_MT_ARGS);
-        else if ((NPER != 3 && grp != 3) || grp == 2)  // pairs of lists: 117 VGPRs = four waves per SIMD (three lists: 136)
+        else if (NPER != 3)  // pairs of lists: 117 VGPRs = four waves per SIMD (three lists: 136)
             hipLaunchKernelGGL(k_mask_tails<2>, dim3(ncb, chunks), dim3(256), 0, ctx->stream, MAREX_MT_ARGS);
         else  // exactly 3 lists: one group
             hipLaunchKernelGGL(k_mask_tails<3>, dim3(ncb, chunks), dim3(256), 0, ctx->stream, MAREX_MT_ARGS);

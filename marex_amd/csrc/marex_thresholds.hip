@@ -251,7 +251,7 @@ static_assert(TB_STEP <= TB_BWF - 8, "straggler passes must overlap: a quantile 
 template <int P, int TC, int NT, int TR_ = NT / TC>
 __global__ void __launch_bounds__(NT, NT == 256 ? 4 : 1)
 k_thr_band(const unsigned short* __restrict__ bins, long T_out, long C, int ny, int nx, int row0, int row1, int tiles_x,
-           int Dd, int shift, int env_exact, int ablate, const int* __restrict__ doy_start,
+           int Dd, int shift, int env_exact, const int* __restrict__ doy_start,
            const float* __restrict__ first_anom, const float* __restrict__ centres, int nb, double q, int wd,
            float lower_bound, float upper_bound, float* __restrict__ thr, marex_thr_stats* __restrict__ stats,
            unsigned char* __restrict__ gscratch, int coarse_pd, int two_ended, int bwf) {
@@ -261,9 +261,6 @@ k_thr_band(const unsigned short* __restrict__ bins, long T_out, long C, int ny, 
     constexpr int NCELL = TR * TC;
     static_assert(NCELL <= NT && NT - NCELL < 64, "tile does not match the thread count");
     constexpr int OR = TR - 2 * P, OC = TC - 2 * P;
-#ifndef MAREX_ABLATION
-    ablate = 0;  // timing-only ablation bits: -DMAREX_ABLATION builds only
-#endif
     // lane-major level columns: TB_LS dwords (= 68 uint16 levels) per lane.  The stride 34 keeps 8-byte
     // alignment and makes 8-byte accesses of 32 consecutive lanes hit 64 distinct banks.
     __shared__ unsigned lev[NT * TB_LS];
@@ -552,10 +549,6 @@ k_thr_band(const unsigned short* __restrict__ bins, long T_out, long C, int ny, 
 
     // exact threshold of one output-day from level k of the current band (ck = cs[iu], cb = cs[iu-1])
     auto emit_threshold = [&](int d, int iu, int ck, int cb, double qpos) {
-        if (ablate & 16) {  // timing only: no table look-ups, no float64 interpolation
-            thr[(size_t)d * C + cell] = (float)(iu + ck + cb);
-            return;
-        }
         const int il = iu > 0 ? iu - 1 : 0;
         const int cs_iu = ck;
         const int cs_il = iu > 0 ? cb : ck;
@@ -606,30 +599,26 @@ k_thr_band(const unsigned short* __restrict__ bins, long T_out, long C, int ny, 
             // ---------------- P1: this lane's column
             if (dd == 0) {
                 for (int r = 0; r < TB_LS / 2; ++r) mycol2[r] = make_uint2(0u, 0u);
-                if (!(ablate & 4)) {
-                    Pre cur = load_bucket(((d - init_pd) % NDOY + NDOY) % NDOY);
-                    for (int o = -init_pd + 1; o <= init_pd; ++o) {
-                        const Pre nxt = load_bucket(((d + o) % NDOY + NDOY) % NDOY);
-                        apply_bucket(cur, +1);
-                        cur = nxt;
-                    }
+                Pre cur = load_bucket(((d - init_pd) % NDOY + NDOY) % NDOY);
+                for (int o = -init_pd + 1; o <= init_pd; ++o) {
+                    const Pre nxt = load_bucket(((d + o) % NDOY + NDOY) % NDOY);
                     apply_bucket(cur, +1);
+                    cur = nxt;
                 }
+                apply_bucket(cur, +1);
             } else {
-                if (!(ablate & 2)) unprefix(nlp);
-                if (!(ablate & 4)) {
-                    apply_bucket(pin, +1);
-                    apply_bucket(pout, -1);
-                }
+                unprefix(nlp);
+                apply_bucket(pin, +1);
+                apply_bucket(pout, -1);
             }
-            if (!(ablate & 2)) tot_s[ci] = prefix(nlp);
-            if (dd + 1 < nd_pass && !(ablate & 4)) {
+            tot_s[ci] = prefix(nlp);
+            if (dd + 1 < nd_pass) {
                 pin = load_bucket((d + 1 + pd) % NDOY);
                 pout = load_bucket(((d - pd) % NDOY + NDOY) % NDOY);
             }
             __syncthreads();
             // ---------------- P2: quantile level of this lane's output cell
-            const int g = (ablate & 1) ? 255 : gst[dg][t];
+            const int g = gst[dg][t];
             if (mode == 0) {
                 int g_lo = 255, g_hi = -1;
                 if (g == 254) {
@@ -934,7 +923,7 @@ k_thr_band(const unsigned short* __restrict__ bins, long T_out, long C, int ny, 
     }
     (void)two_ended;
     __syncthreads();
-    if (s_unres && !(ablate & 8)) {  // exact path for whatever is not resolved yet
+    if (s_unres) {  // exact path for whatever is not resolved yet
         for (int dd = 0; dd < ndays; ++dd)
             if (gst[dd][t] < 254) gst[dd][t] = 254;  // day-0 groups of a skipped speculative sweep: redo
         __syncthreads();
@@ -1040,22 +1029,13 @@ extern "C" int marex_hobday_thresholds_f32(marex_ctx* ctx, const uint16_t* bins,
             }
         }
         dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)((NDOY + Dd - 1) / Dd));
-        unsigned char* gscratch = nullptr;
-        {  // per-(tile, day, lane) state bytes
-            const size_t need = (size_t)grid.x * grid.y * (size_t)Dd * NT;
-            if (need > ctx->thr_scratch_bytes) {
-                if (ctx->thr_scratch) HIP_TRY(ctx, hipFree(ctx->thr_scratch));
-                ctx->thr_scratch = nullptr;
-                ctx->thr_scratch_bytes = 0;
-                HIP_TRY(ctx, hipMalloc((void**)&ctx->thr_scratch, need));
-                ctx->thr_scratch_bytes = need;
-            }
-            gscratch = ctx->thr_scratch;
-        }
+        // per-(tile, day, lane) state bytes
+        HIP_TRY(ctx, grow_scratch(ctx->thr_scratch, ctx->thr_scratch_bytes, (size_t)grid.x * grid.y * (size_t)Dd * NT));
+        unsigned char* gscratch = ctx->thr_scratch;
         const int coarse_pd = ctx_opt(ctx, "THR_COARSE_PD", 1);
         int bwf = ctx_opt(ctx, "THR_BWF", TB_BWF);  // bins of the band that follows the thresholds (experiments: 24..64)
         bwf = bwf < 24 ? 24 : (bwf > TB_BWF ? TB_BWF : bwf);
-#define MAREX_BAND_ARGS bins, (long)T_out, (long)C, ny, nx, row0, row1, tiles_x, Dd, shift, ctx_opt(ctx, "THR_EXACT_PATH", 0), MAREX_ABLATE_OPT(ctx, "THR_ABLATE"), doy_start, first_anom, centres, nb, q, wd, lower_bound, upper_bound, thr_doy_major, stats, gscratch, coarse_pd, ctx_opt(ctx, "THR_TWO_ENDS", 1), bwf
+#define MAREX_BAND_ARGS bins, (long)T_out, (long)C, ny, nx, row0, row1, tiles_x, Dd, shift, ctx_opt(ctx, "THR_EXACT_PATH", 0), doy_start, first_anom, centres, nb, q, wd, lower_bound, upper_bound, thr_doy_major, stats, gscratch, coarse_pd, ctx_opt(ctx, "THR_TWO_ENDS", 1), bwf
         {
             LaunchTimer lt(ctx, MAREX_K_THRESHOLDS);
             if (TR == 1)

@@ -16,7 +16,7 @@ wsp = {}
 a = hot.shifting_baseline_tails(x, dcal, 15, 21, bt, wsp=wsp)
 tl = a["tails"]
 print("max_bucket", tl["max_bucket"], "list_rows", tl["list_rows"], "lists", tuple(tl["tails"].shape))
-for opts in [{}, {"THR_CELLS_CACHE": 0}, {"THR_CELLS": 0}]:
+for opts in [{}, {"THR_CELLS": 0}]:
     with hot.ctx.options(**opts):
         for it in range(3):
             if it == 1:

@@ -1,5 +1,5 @@
-"""Which years take the straight-line body of k_shift_lean (debug counters 6 / 7 = wave-years lean / general) and what the
-anomaly stage costs with either kernel, for a few (series length, W, cells) shapes.  Run on the GPU box."""
+"""What the anomaly stage costs with k_shift_lean and with k_shift_fast (SHIFT_LEAN=0), for a few (series length, W, cells)
+shapes.  Run on the GPU box."""
 import sys, time
 import numpy as np, torch
 sys.path.insert(0, '.')
@@ -16,15 +16,13 @@ for (start, T, W, ny, nx) in (("1925-01-01", 36500, 15, 8, 1440), ("2015-01-01",
     wsp = {}
     for lean in (1, 0):
         with hot.ctx.options(SHIFT_LEAN=lean):
-            hot.ctx.debug_counters(reset=True)
             hot.shifting_baseline_tails(x, dcal, W, 21, bt, wsp=wsp)
             hot.sync()
-            cnt = hot.ctx.debug_counters(reset=True)
             t0 = time.perf_counter()
             for _ in range(3):
                 hot.shifting_baseline_tails(x, dcal, W, 21, bt, wsp=wsp)
             hot.sync()
             ms = (time.perf_counter() - t0) / 3 * 1e3
-        print(f"T={T} W={W} C={ny*nx} lean={lean}: {ms:.2f} ms, wave-years lean/general {cnt[6]}/{cnt[7]}", flush=True)
+        print(f"T={T} W={W} C={ny*nx} lean={lean}: {ms:.2f} ms", flush=True)
     del x, wsp
     torch.cuda.empty_cache()
