@@ -1555,11 +1555,14 @@ extern "C" int marex_hobday_thresholds_pool_f32(marex_ctx* ctx, const void* list
 // those in it are compared as numbers (a handful per wave and day).  Buckets holding values beyond the edge table (aux bit 15) are decided on
 // the anomalies themselves (float4 rows, like the plain mask kernel).
 // Lane = 4 consecutive cells: 16-byte key chunks of 4 cells are one contiguous 64-byte run, mask stores are 4 bytes.
+// Chunks are fetched only for buckets whose keys can matter (not for land, empty buckets, thresholds beyond the table).
 // ------------------------------------------------------------------------------------------------
 #ifndef MASK_WAVES
-#define MASK_WAVES 5  // waves per SIMD the mask kernel is compiled for (96 VGPRs, a few spilled: 2.24 -> 2.03 ms; 6 is worse)
+#define MASK_WAVES 5  // waves per SIMD the mask kernel is compiled for, at least: pairs of lists take 96 VGPRs, one list at a time
+                      // 80 (six waves), both without scratch; compiled for 6 the pairs spill 44 bytes, for 7 one list 12
 #endif
-template <int NPERT>  // lists handled per group (their first chunks are in flight together)
+template <int NPERT, int NW>  // NPERT: lists handled per group (their first chunks are in flight together); NW: 32-bit words
+                              // of row bits per cell (3: buckets of at most 96 rows, 4: up to TAIL_MAX_BUCKET)
 __global__ void __launch_bounds__(256, MASK_WAVES)
 k_mask_tails(const uint4* __restrict__ lists, const unsigned* __restrict__ aux, int NPER_all, int nch, const float* __restrict__ anom,
              const float* __restrict__ edges, int nb, const float* __restrict__ thr, const int* __restrict__ doy_start,
@@ -1572,34 +1575,51 @@ k_mask_tails(const uint4* __restrict__ lists, const unsigned* __restrict__ aux, 
     // offset of the row (with two overlap rows of 1440 cells c0 = 2880 = 11.25 x 256, and every wave store straddled three
     // 128-byte lines: the 1.21 x write amplification of the 100-yr bands, round 3)
     const long c = (c0 & ~255L) + ((long)blockIdx.x * 256 + threadIdx.x) * 4;
+    // Every address below is a pointer plus a 32-bit lane byte offset (C x 16 < 2^31, the launcher checks), and the lane's
+    // first cell goes through an empty asm statement at every use: the compiler then cannot lift a 64-bit address per
+    // array and cell out of the dayofyear loop (it kept 30 registers of them there and spilled around the list groups).
+    const unsigned cu = (unsigned)c;
+    auto cell = [&](int i) { unsigned v = cu; asm volatile("" : "+v"(v)); return v + (unsigned)i; };
+    auto lane_ptr = [](const void* base, unsigned lane_bytes) { return reinterpret_cast<const char*>(base) + lane_bytes; };
     unsigned cnt_true = 0;
-    unsigned long long n_slow = 0;
+    unsigned n_slow = 0;
     if (c >= c0 && c < c1) {
         const float inv_width = (float)(nb - 1) / (edges[nb] - edges[1]);
         for (int d = dA; d < dB; ++d) {
             const int r0 = doy_start[d], nd = doy_start[d + 1] - r0;
             if (nd == 0) continue;
-            const float4 th4 = *reinterpret_cast<const float4*>(thr + (size_t)d * C + c);
+            const float4 th4 = *reinterpret_cast<const float4*>(lane_ptr(thr + (size_t)d * C, cell(0) * 4u));
             const float tv[4] = {th4.x, th4.y, th4.z, th4.w};
-            const uint4 ax = *reinterpret_cast<const uint4*>(aux + (size_t)d * C + c);
-            const unsigned av[4] = {ax.x, ax.y, ax.z, ax.w};
             unsigned beyond = 0;  // some cell of the lane has samples beyond the table and a threshold that is a number
-            unsigned bits[4][4];
-            unsigned lim_ge[4];  // keys > lim_ge: bin >= the threshold's bin
-            int kt[4];
+            unsigned bits[4][NW];
+            unsigned lim_ge[4];  // keys > lim_ge: bin >= the threshold's bin (the bin itself is bits 7..15 of a half)
             bool slow = false, walk[4];
+            {
+                const uint4 ax = *reinterpret_cast<const uint4*>(lane_ptr(aux + (size_t)d * C, cell(0) * 4u));
+                const unsigned av[4] = {ax.x, ax.y, ax.z, ax.w};
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+#pragma unroll
+                    for (int wi = 0; wi < NW; ++wi) bits[i][wi] = 0u;
+                    const bool isnum = tv[i] == tv[i];
+                    const int kt = isnum ? digitize_bin(tv[i], edges, nb, inv_width) : nb;  // NaN threshold: nothing is extreme
+                    // values beyond the table are extremes of every threshold INSIDE the table (any threshold the histogram
+                    // quantile produces); more than two of them, or a threshold beyond the table itself: look at the values
+                    slow = slow || (isnum && (av[i] & TAIL_AUX_BEYOND) && ((av[i] & TAIL_AUX_MANY) || kt >= nb));
+                    beyond |= (isnum && (av[i] & TAIL_AUX_BEYOND)) ? 1u : 0u;
+                    walk[i] = isnum && (av[i] & 0x3FFu) > 0 && kt < nb;
+                    const unsigned lim = ((unsigned)(kt + 1) << TAIL_POS_BITS) - 1u;
+                    lim_ge[i] = lim | (lim << 16);
+                }
+            }
+            // A cell's chunks are fetched only where a key can matter: a threshold that is a number inside the table, a bucket
+            // with keys, a lane that is not on the value path.  The loads stay one batch without a branch: the lane offset
+            // of any other cell lies beyond the chunk row's descriptor, whose range check returns zeros and fetches nothing.
+            unsigned voff[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                bits[i][0] = bits[i][1] = bits[i][2] = bits[i][3] = 0u;
-                const bool isnum = tv[i] == tv[i];
-                kt[i] = isnum ? digitize_bin(tv[i], edges, nb, inv_width) : nb;  // NaN threshold: nothing is extreme
-                // values beyond the table are extremes of every threshold INSIDE the table (any threshold the histogram quantile
-                // produces); more than two of them, or a threshold beyond the table itself: look at the values
-                slow = slow || (isnum && (av[i] & TAIL_AUX_BEYOND) && ((av[i] & TAIL_AUX_MANY) || kt[i] >= nb));
-                beyond |= (isnum && (av[i] & TAIL_AUX_BEYOND)) ? 1u : 0u;
-                walk[i] = isnum && (av[i] & 0x3FFu) > 0 && kt[i] < nb;
-                const unsigned lim = ((unsigned)(kt[i] + 1) << TAIL_POS_BITS) - 1u;
-                lim_ge[i] = lim | (lim << 16);
+                walk[i] = walk[i] && !slow;
+                voff[i] = walk[i] ? cell(i) * 16u : 0x80000000u;
             }
             // Keys of a chunk at or above the threshold's bin are a prefix of n_ge keys; the first n_gt of them lie in higher
             // bins (extremes), the rest sit IN the threshold's bin and are compared as numbers.  Those compares need a value
@@ -1614,7 +1634,7 @@ k_mask_tails(const uint4* __restrict__ lists, const unsigned* __restrict__ aux, 
                     if (on) {
                         const int pos = (int)(tl_key(q, u) & (TAIL_MAX_BUCKET - 1));
 #pragma unroll
-                        for (int wi = 0; wi < 4; ++wi)
+                        for (int wi = 0; wi < NW; ++wi)
                             if ((pos >> 5) == wi) bits[i][wi] |= 1u << (pos & 31);
                     }
                 }
@@ -1624,11 +1644,15 @@ k_mask_tails(const uint4* __restrict__ lists, const unsigned* __restrict__ aux, 
                 const int NPER = (NPER_all - pg) < NPERT ? (NPER_all - pg) : NPERT;
                 // every list's first chunk of the 4 cells: 64 contiguous bytes per list, all loads in flight together
                 uint4 ch[NPERT][4];
-                const uint4* row0 = lists + (((size_t)d * NPER_all + pg) * nch) * C + c;
+                const uint4* grp = lists + (((size_t)d * NPER_all + pg) * nch) * C;  // wave-uniform: chunk row 0 of list pg
 #pragma unroll
-                for (int p = 0; p < NPERT; ++p)
+                for (int p = 0; p < NPERT; ++p) {
+                    // one descriptor per chunk row of C x 16 bytes (a list the group does not have: an empty range)
+                    const tl_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4*>(grp + (size_t)(p * nch) * C), 0,
+                                                                           p < NPER ? (int)(C * 16) : 0, 0x00020000);
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) ch[p][i] = p < NPER ? row0[(size_t)(p * nch) * C + i] : make_uint4(0, 0, 0, 0);
+                    for (int i = 0; i < 4; ++i) ch[p][i] = tl_load_chunk(rs, voff[i], 0u);
+                }
             float cand_val[NPERT][4];
             int cand_pos[NPERT][4];
             unsigned redo = 0;  // (list, cell) pairs the batched pass could not finish
@@ -1639,7 +1663,7 @@ k_mask_tails(const uint4* __restrict__ lists, const unsigned* __restrict__ aux, 
                     for (int i = 0; i < 4; ++i) {
                         cand_pos[p][i] = -1;
                         cand_val[p][i] = 0.f;
-                        if (p < NPER && walk[i] && !slow) {
+                        if (p < NPER && walk[i]) {
                             const unsigned lgt = lim_ge[i] + (0x10001u << TAIL_POS_BITS);  // keys > lgt: bin > the threshold's bin
                             const int n_ge = tl_count_above(ch[p][i], lim_ge[i]);
                             const int n_gt = tl_count_above(ch[p][i], lgt);
@@ -1664,7 +1688,7 @@ k_mask_tails(const uint4* __restrict__ lists, const unsigned* __restrict__ aux, 
 #pragma unroll
                     for (int i = 0; i < 4; ++i)
                         if (cand_pos[p][i] >= 0)
-                            cand_val[p][i] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(anom) + row_off_anom[r0 + cand_pos[p][i]] + (size_t)(c + i) * 4);
+                            cand_val[p][i] = *reinterpret_cast<const float*>(lane_ptr(reinterpret_cast<const char*>(anom) + row_off_anom[r0 + cand_pos[p][i]], cell(i) * 4u));
 #pragma unroll
                 for (int p = 0; p < NPERT; ++p)
 #pragma unroll
@@ -1672,7 +1696,7 @@ k_mask_tails(const uint4* __restrict__ lists, const unsigned* __restrict__ aux, 
                         if (cand_pos[p][i] >= 0 && cand_val[p][i] >= tv[i]) {
                             const int pos = cand_pos[p][i];
 #pragma unroll
-                            for (int wi = 0; wi < 4; ++wi)
+                            for (int wi = 0; wi < NW; ++wi)
                                 if ((pos >> 5) == wi) bits[i][wi] |= 1u << (pos & 31);
                         }
                 // the rare leftovers: walk the whole list key by key, one value fetch per key of the threshold's bin
@@ -1684,20 +1708,21 @@ k_mask_tails(const uint4* __restrict__ lists, const unsigned* __restrict__ aux, 
                         for (int i = 0; i < 4; ++i) {
                             if (__builtin_amdgcn_ballot_w64((redo >> (p * 4 + i)) & 1u) == 0) continue;
                             bool on = (redo >> (p * 4 + i)) & 1u;
+                            const int kt = (int)((lim_ge[i] & 0xFFFFu) >> TAIL_POS_BITS);  // the threshold's bin
                             for (int jj = 0; jj < nch; ++jj) {
                                 if (__builtin_amdgcn_ballot_w64(on) == 0) break;
-                                const uint4 q = on ? row0[(size_t)(p * nch + jj) * C + i] : make_uint4(0, 0, 0, 0);
+                                const uint4 q = on ? *reinterpret_cast<const uint4*>(lane_ptr(grp + (size_t)(p * nch + jj) * C, cell(i) * 16u)) : make_uint4(0, 0, 0, 0);
 #pragma unroll
                                 for (int u = 0; u < 8; ++u) {
                                     const unsigned key = tl_key(q, u);
                                     const int bin = (int)(key >> TAIL_POS_BITS) - 1, pos = (int)(key & (TAIL_MAX_BUCKET - 1));
-                                    on = on && bin >= kt[i];
+                                    on = on && bin >= kt;
                                     if (on) {
-                                        bool ext = bin > kt[i];
-                                        if (!ext) ext = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(anom) + row_off_anom[r0 + pos] + (size_t)(c + i) * 4) >= tv[i];
+                                        bool ext = bin > kt;
+                                        if (!ext) ext = *reinterpret_cast<const float*>(lane_ptr(reinterpret_cast<const char*>(anom) + row_off_anom[r0 + pos], cell(i) * 4u)) >= tv[i];
                                         if (ext) {
 #pragma unroll
-                                            for (int wi = 0; wi < 4; ++wi)
+                                            for (int wi = 0; wi < NW; ++wi)
                                                 if ((pos >> 5) == wi) bits[i][wi] |= 1u << (pos & 31);
                                         }
                                     }
@@ -1708,14 +1733,17 @@ k_mask_tails(const uint4* __restrict__ lists, const unsigned* __restrict__ aux, 
             }
             }  // list groups
             // samples beyond the table have no key but are extremes of every finite threshold: their positions come with aux
+            // (the aux words are read again here, from the cache, instead of being kept across the list groups)
             if (__builtin_amdgcn_ballot_w64(beyond != 0u && !slow) != 0) {
+                const uint4 ax = *reinterpret_cast<const uint4*>(lane_ptr(aux + (size_t)d * C, cell(0) * 4u));
+                const unsigned av[4] = {ax.x, ax.y, ax.z, ax.w};
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     if (!slow && tv[i] == tv[i] && (av[i] & TAIL_AUX_BEYOND)) {
                         const int p1 = (int)((av[i] >> 16) & 0x7Fu), p2 = (int)((av[i] >> 23) & 0x7Fu);
                         const bool two = (av[i] & TAIL_AUX_SECOND) != 0u;
 #pragma unroll
-                        for (int wi = 0; wi < 4; ++wi) {
+                        for (int wi = 0; wi < NW; ++wi) {
                             if ((p1 >> 5) == wi) bits[i][wi] |= 1u << (p1 & 31);
                             if (two && (p2 >> 5) == wi) bits[i][wi] |= 1u << (p2 & 31);
                         }
@@ -1725,17 +1753,16 @@ k_mask_tails(const uint4* __restrict__ lists, const unsigned* __restrict__ aux, 
             if (slow) {
                 ++n_slow;
                 for (int r = 0; r < nd; ++r) {
-                    const size_t off = (size_t)doy_rows[r0 + r] * C + c;
-                    const float4 a = *reinterpret_cast<const float4*>(anom + off);
+                    const size_t off = (size_t)doy_rows[r0 + r] * C;
+                    const float4 a = *reinterpret_cast<const float4*>(lane_ptr(anom + off, cell(0) * 4u));
                     const unsigned m0 = a.x >= tv[0], m1 = a.y >= tv[1], m2 = a.z >= tv[2], m3 = a.w >= tv[3];
                     cnt_true += m0 + m1 + m2 + m3;
-                    __builtin_nontemporal_store(m0 | (m1 << 8) | (m2 << 16) | (m3 << 24), reinterpret_cast<unsigned*>(out + off));
+                    __builtin_nontemporal_store(m0 | (m1 << 8) | (m2 << 16) | (m3 << 24), reinterpret_cast<unsigned*>(out + off + cell(0)));
                 }
             } else {
                 // rows in groups of 8: eight row offsets per scalar load batch, bit positions known at compile time
-                unsigned char* obase = out + c;
 #pragma unroll
-                for (int wi = 0; wi < 4; ++wi) {
+                for (int wi = 0; wi < NW; ++wi) {
                     const unsigned b0 = bits[0][wi], b1 = bits[1][wi], b2 = bits[2][wi], b3 = bits[3][wi];
                     cnt_true += __popc(b0) + __popc(b1) + __popc(b2) + __popc(b3);
                     if (wi * 32 >= nd) break;
@@ -1749,12 +1776,12 @@ k_mask_tails(const uint4* __restrict__ lists, const unsigned* __restrict__ aux, 
 #pragma unroll
                             for (int rr = 0; rr < 8; ++rr) {
                                 const unsigned m = ((q0 >> rr) & 1u) | (((q1 >> rr) & 1u) << 8) | (((q2 >> rr) & 1u) << 16) | (((q3 >> rr) & 1u) << 24);
-                                __builtin_nontemporal_store(m, reinterpret_cast<unsigned*>(obase + ro[rr]));
+                                __builtin_nontemporal_store(m, reinterpret_cast<unsigned*>(out + ro[rr] + cu));
                             }
                         } else {
                             for (int rr = 0; rr < nd - rlo; ++rr) {
                                 const unsigned m = ((q0 >> rr) & 1u) | (((q1 >> rr) & 1u) << 8) | (((q2 >> rr) & 1u) << 16) | (((q3 >> rr) & 1u) << 24);
-                                __builtin_nontemporal_store(m, reinterpret_cast<unsigned*>(obase + ro[rr]));
+                                __builtin_nontemporal_store(m, reinterpret_cast<unsigned*>(out + ro[rr] + cu));
                             }
                         }
                     }
@@ -1768,7 +1795,7 @@ k_mask_tails(const uint4* __restrict__ lists, const unsigned* __restrict__ aux, 
     }
     if (dbg) {
         for (int s = 32; s > 0; s >>= 1) n_slow += __shfl_down(n_slow, s, 64);
-        if ((threadIdx.x & 63) == 0 && n_slow) atomicAdd(&dbg[4], n_slow);
+        if ((threadIdx.x & 63) == 0 && n_slow) atomicAdd(&dbg[4], (unsigned long long)n_slow);
     }
 }
 
@@ -1785,7 +1812,8 @@ extern "C" int marex_mask_ge_doy_tails_f32(marex_ctx* ctx, const void* lists, co
     if (!tails_geometry(max_bucket, list_rows, NPER, nch))
         return fail(ctx, -4, "marex_mask_ge_doy_tails_f32: buckets must hold 1..%d rows, lists 8..32 rows", TAIL_MAX_BUCKET);
     const bool vec = (C % 4 == 0) && (c0 % 4 == 0) && (c1 % 4 == 0) && (((uintptr_t)anom | (uintptr_t)thr_doy_major) % 16 == 0) &&
-                     ((uintptr_t)extreme % 4 == 0) && ((uintptr_t)aux % 16 == 0) && nb < 0x7fff;
+                     ((uintptr_t)extreme % 4 == 0) && ((uintptr_t)aux % 16 == 0) && nb < 0x7fff &&
+                     C * 16 < 0x80000000ll;  // a chunk row is one buffer range; lane offsets from 2^31 on mean "no fetch"
     if (!vec)  // shapes the 4-cell kernel does not cover: the plain compare on the anomalies
         return marex_mask_ge_doy_f32(ctx, anom, thr_doy_major, doy_start, doy_rows, T_out, C, c0, c1, extreme, n_true);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -1807,12 +1835,13 @@ extern "C" int marex_mask_ge_doy_tails_f32(marex_ctx* ctx, const void* lists, co
         hipLaunchKernelGGL(k_row_offsets, dim3((unsigned)((T_out + 255) / 256)), dim3(256), 0, ctx->stream, doy_rows, (long)T_out, (long)C,
                            ctx->row_off, (int)sizeof(float));
 #define MAREX_MT_ARGS tl, aux, NPER, nch, anom, edges, nb, thr_doy_major, doy_start, doy_rows, ctx->row_off_mask, ctx->row_off, (long)C, (long)c0, (long)c1, extreme, n_true, dbg
-        if (NPER <= 1)
-            hipLaunchKernelGGL(k_mask_tails<1>, dim3(ncb, chunks), dim3(256), 0, ctx->stream, MAREX_MT_ARGS);
-        else if (NPER != 3)  // pairs of lists: 117 VGPRs = four waves per SIMD (three lists: 136)
-            hipLaunchKernelGGL(k_mask_tails<2>, dim3(ncb, chunks), dim3(256), 0, ctx->stream, MAREX_MT_ARGS);
-        else  // exactly 3 lists: one group
-            hipLaunchKernelGGL(k_mask_tails<3>, dim3(ncb, chunks), dim3(256), 0, ctx->stream, MAREX_MT_ARGS);
+        // Buckets of at most 96 rows: three words of row bits per cell and one list per round trip -- 80 VGPRs, six waves per
+        // SIMD, which beat pairs and triples of lists in flight at five (profiles/r06_experiments.md).  Longer buckets: four
+        // words, lists in pairs (96 VGPRs, five waves).  Neither instance uses scratch.
+        if (max_bucket <= 96)
+            hipLaunchKernelGGL((k_mask_tails<1, 3>), dim3(ncb, chunks), dim3(256), 0, ctx->stream, MAREX_MT_ARGS);
+        else
+            hipLaunchKernelGGL((k_mask_tails<2, 4>), dim3(ncb, chunks), dim3(256), 0, ctx->stream, MAREX_MT_ARGS);
 #undef MAREX_MT_ARGS
     }
     HIP_TRY(ctx, hipGetLastError());
