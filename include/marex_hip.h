@@ -629,6 +629,35 @@ int marex_event_intensity_f32(marex_ctx* ctx, const int32_t* ids, const float* a
                               int n_ev, const int32_t* ev_tmin, const int64_t* ev_off, int64_t n_slots, const float* w,
                               uint64_t* cnt, double* sums, uint32_t* vmax, uint64_t* status);
 
+/* Severity categories of tracked events (Hobday et al. 2018: moderate, strong, severe, extreme as multiples of the
+ * threshold): the event field joined with the anomaly field and the day-of-year thresholds, per (timestep, event).
+ *
+ * marex_event_categories_f32: ids, anom, t0, Tb, C, n_ev, ev_tmin, ev_off and n_slots as in marex_event_intensity_f32 (the
+ *   same slots s = ev_off[e] + t - ev_tmin[e]).  thr float32 [n_doy][C]; doy int32 [T], indexed by the global step t = t0 +
+ *   row, gives the row of thr of every step and must reach t0 + Tb.  w: float32 [C] cell weights with cat_area, or both
+ *   NULL.  A cell of an event with a finite anomaly a has, with h = thr[doy[t]][c] and the float32 products h2 = 2 h, h3 =
+ *   3 h, h4 = 4 h (one rounding each), the class k of marex_local_intensity_*: 5 where h is NaN, +-inf or <= 0, else 0 for
+ *   a < h, 1 for h <= a < h2, 2 for h2 <= a < h3, 3 for h3 <= a < h4, 4 for a >= h4.  A cell whose anomaly is NaN or +-inf
+ *   has class 6: counted, not classified.
+ *   cat_cnt uint64 [n_slots][7]: cat_cnt[s][k] += 1 per cell.  cat_area float64 [n_slots][6]: cat_area[s][k] += (double)w[c]
+ *   for k = 0 .. 5, under the summation contract of sums of marex_event_intensity_f32 (exact terms, atomic adds).
+ *   field uint8, or NULL: the base of the WHOLE [T][C] output, addressed with the global step as the mask of
+ *   marex_cell_events_u8 is.  Every cell of the rows t0 .. t0 + Tb - 1 is written: 0 where the cell belongs to no event,
+ *   k + 1 otherwise (7: a non-finite anomaly).  No atomic touches field.
+ *   status uint64 [2].  A cell whose event lies outside its declared span (t < ev_tmin[e], s >= ev_off[e + 1] or s >=
+ *   n_slots) adds one to status[0] and nothing else, and gets 0 in field: no slot index that was not range-checked
+ *   addresses cat_cnt or cat_area.  Under a row whose doy label lies outside 0 .. n_doy - 1 nothing in thr is addressed:
+ *   its event cells add one each to status[1] and nothing else, and the row of field is 0.
+ *   anom is fetched only under cells of an event, thr and w only under those of them with a finite anomaly.  The function
+ *   only adds: the caller zeroes cat_cnt, cat_area and status before the first block.  The counts and field are exact and
+ *   independent of any order and of the blocks.
+ *   -1: the conditions of marex_event_intensity_f32 (cat_cnt for cnt), thr or doy NULL, n_doy <= 0, or w and cat_area given
+ *   in part; -4: as marex_event_intensity_f32.  Asynchronous on the context's stream. */
+int marex_event_categories_f32(marex_ctx* ctx, const int32_t* ids, const float* anom, int64_t t0, int64_t Tb, int64_t C,
+                               int n_ev, const int32_t* ev_tmin, const int64_t* ev_off, int64_t n_slots, const float* thr,
+                               const int32_t* doy, int n_doy, const float* w, uint64_t* cat_cnt, double* cat_area,
+                               uint8_t* field, uint64_t* status);
+
 /* Occurrence statistics of an event mask (extreme_events) or a tracked ID field, from one streaming pass (the reference
  * leaves them to notebook code: 03_visualise_events over ID_field, 01_preprocess_extremes over extreme_events).
  *

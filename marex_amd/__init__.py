@@ -6,7 +6,9 @@ its absence is an error (no CPU fallback).
 
 Beyond the reference: ``preprocess_data`` and ``identify_extremes`` take ``neighbour_rings_hobday=1 | 2`` with ``neighbours``
 on unstructured meshes -- day-of-year thresholds pooled over the cell and one or two rings of its listed neighbours, the mesh
-counterpart of ``window_spatial_hobday``.
+counterpart of ``window_spatial_hobday``.  ``event_categories`` and ``tracker.event_categories`` give the severity
+categories (Hobday et al. 2018) of every tracked event and the category map of every timestep, from ``ID_field``,
+``dat_anomaly`` and ``thresholds`` on the device.
 """
 from .detect import (
     compute_normalised_anomaly,
@@ -26,6 +28,7 @@ from .exceptions import (
 )
 from .dask_adapter import preprocess_data_lazy
 from .intensity import event_intensity
+from .event_categories import event_categories
 from .occurrence import event_occurrence
 from .local_intensity import local_intensity
 from .cell_events import cell_events
@@ -37,6 +40,6 @@ __all__ = [
     "smoothed_rolling_climatology", "MarExError", "DataValidationError", "ConfigurationError",
     "ProcessingError", "DependencyError", "create_data_validation_error", "DataArray", "Dataset",
     "tracker", "TrackingError", "event_intensity", "event_occurrence", "local_intensity",
-    "cell_events",
+    "cell_events", "event_categories",
 ]
 __version__ = "0.1.0"

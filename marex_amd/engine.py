@@ -1487,6 +1487,79 @@ class HotPath:
                    vmax=key_float(acc["vmax"][:n_slots].cpu().numpy().view(np.uint32)))  # key 0: a NaN
         return out
 
+    def event_categories(self, ids: torch.Tensor, anom: torch.Tensor, ev_tmin, ev_tmax, thr: torch.Tensor, doy,
+                         weights: Optional[torch.Tensor] = None, t0: int = 0, field: Optional[torch.Tensor] = None,
+                         acc: Optional[dict] = None, finish: bool = False) -> Dict[str, object]:
+        """Per (timestep, event) severity categories of the rows ``t0 .. t0 + Tb - 1`` of a tracked field
+        (``marex_event_categories_f32``): ``ids`` int32 and ``anom`` float32 ``[Tb, C]``, ``ev_tmin`` / ``ev_tmax`` and
+        ``weights`` as in :meth:`event_intensity` (the same slots), ``thr`` float32 ``[n_doy, C]`` on the device and ``doy``
+        (int ``[T]``, the row of ``thr`` of every global step).  ``field``: the WHOLE uint8 ``[T, C]`` output (the rows of
+        this window are written: 0 no event, class + 1 otherwise), or None.  The first block allocates zeroed accumulators
+        and uploads the tables; a later block passes the ``"acc"`` entry of the previous result, whatever the block length.
+        Returns ``off``, ``acc`` and -- with ``finish``, which costs the one host read -- ``cat_cnt`` int64 ``[n, 7]``
+        (cells below, moderate, strong, severe, extreme, undefined, with a non-finite anomaly) and ``cat_area`` float64
+        ``[n, 6]`` (None without ``weights``).  A cell of an event outside its declared span, or under a ``doy`` label
+        outside ``0 .. n_doy - 1``, raises :class:`ProcessingError` (it was counted, nothing was written out of range)."""
+        Tb, Cn = self._ids_check(ids)
+        self._anomaly_window_check("event_categories", anom, Tb, Cn)
+        if weights is not None and (weights.dtype != torch.float32 or tuple(weights.shape) != (Cn,) or not weights.is_contiguous()
+                                    or weights.device != self.device):
+            raise ProcessingError(f"event_categories: the weights must be a contiguous float32 [{Cn}] tensor on the engine's "
+                                  f"device", details=f"got {weights.dtype} {tuple(weights.shape)} on {weights.device}")
+        if thr is None or doy is None or thr.dim() != 2 or thr.dtype != torch.float32 or int(thr.shape[1]) != Cn or \
+                int(thr.shape[0]) <= 0 or not thr.is_contiguous() or thr.device != self.device:
+            raise ProcessingError(f"event_categories: the thresholds must be a contiguous float32 [n_doy, {Cn}] tensor on the "
+                                  "engine's device, with the row of every step",
+                                  details="one of thr / doy is missing" if thr is None or doy is None else
+                                  f"got {thr.dtype} {tuple(thr.shape)} on {thr.device}")
+        tmin_h, tmax_h = np.asarray(ev_tmin, dtype=np.int64), np.asarray(ev_tmax, dtype=np.int64)
+        n_ev = int(tmin_h.size) - 1
+        t0 = int(t0)
+        if n_ev <= 0 or tmin_h.ndim != 1 or tmax_h.shape != tmin_h.shape or t0 < 0:
+            raise ProcessingError("event_categories: ev_tmin and ev_tmax must have one entry per event 0..n_ev, n_ev > 0, and t0 "
+                                  "must not be negative", details=f"spans {tmin_h.shape} / {tmax_h.shape}, t0 = {t0}")
+        if field is not None and (field.dtype != torch.uint8 or field.dim() != 2 or int(field.shape[1]) != Cn or
+                                  int(field.shape[0]) < t0 + Tb or not field.is_contiguous() or field.device != self.device):
+            raise ProcessingError(f"event_categories: the field must be the whole contiguous uint8 [T, {Cn}] output on the "
+                                  f"engine's device, T >= {t0 + Tb}", details=f"got {field.dtype} {tuple(field.shape)} on {field.device}")
+        off = self.event_slot_plan(tmin_h, tmax_h)
+        n_slots = int(off[-1])
+        alloc = max(n_slots, 1)  # no event has a step: one slot that nothing addresses
+        n_doy = int(thr.shape[0])
+        weighted = weights is not None
+        if acc is None:
+            tabs = label_tables("event_categories", (("doy", doy, None),))
+            self._check_fits((56 + (48 if weighted else 0)) * n_slots + 12 * (n_ev + 2) + 4 * tabs["doy"].size + 16, "event categories",
+                             f"{n_slots} (timestep, event) slots between each event's first and last timestep, "
+                             f"{56 + (48 if weighted else 0)} bytes each, the tables of {n_ev} events and the row of every step")
+            acc = {"cnt": self._buf(None, "cat_cnt", (alloc, 7), torch.int64, self.device).zero_(),
+                   "area": self._buf(None, "cat_area", (alloc, 6), torch.float64, self.device).zero_() if weighted else None,
+                   "status": self._buf(None, "cat_status", (2,), torch.int64, self.device).zero_(),
+                   "tmin": self._dev(np.clip(tmin_h, 0, 2**31 - 1).astype(np.int32)), "off": self._dev(off), "plan": off,
+                   "n_doy": n_doy, **self._upload_tables(tabs)}
+        elif tuple(acc["cnt"].shape) != (alloc, 7) or not np.array_equal(acc["plan"], off) or acc["n_doy"] != n_doy or \
+                (acc["area"] is not None) != weighted:
+            raise ProcessingError("event_categories: the accumulators were planned for another call",
+                                  details=f"{tuple(acc['cnt'].shape)[0]} slots and {acc['n_doy']} threshold rows there, {alloc} "
+                                          f"and {n_doy} here")
+        if acc["len"]["doy"] < t0 + Tb:
+            raise ProcessingError(f"event_categories: doy has {acc['len']['doy']} labels, the window ends at step {t0 + Tb}")
+        self.call("marex_event_categories_f32", ids, anom, t0, Tb, Cn, n_ev, acc["tmin"], acc["off"], alloc, thr,
+                  acc["tabs"]["doy"], n_doy, weights, acc["cnt"], acc["area"], field, acc["status"])
+        out: Dict[str, object] = {"off": off, "acc": acc}
+        if not finish:
+            return out
+        bad, lost = (int(v) for v in acc["status"].cpu().numpy())
+        if bad:
+            raise ProcessingError(f"event_categories: {bad} cells belong to an event outside its declared span of timesteps",
+                                  details="ev_tmin / ev_tmax do not cover the field; the cells were counted, not accumulated")
+        if lost:
+            raise ProcessingError(f"event_categories: {lost} event cells lie under a step label outside its range",
+                                  details=f"doy must hold 0 .. {n_doy - 1}; the cells were counted, nothing was read out of range")
+        out.update(cat_cnt=acc["cnt"][:n_slots].cpu().numpy(),
+                   cat_area=acc["area"][:n_slots].cpu().numpy() if weighted else None)
+        return out
+
     def occurrence(self, x: torch.Tensor, t0: int = 0, grp=None, G: int = 1, sgrp=None, G2: int = 0, cls=None, R: int = 0,
                    runs: bool = True, event_ids=(), acc: Optional[dict] = None, finish: bool = True) -> Dict[str, object]:
         """Occurrence statistics of the rows ``t0 .. t0 + Tb - 1`` of a mask or an ID field (``marex_occurrence_u8`` /

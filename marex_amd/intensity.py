@@ -67,14 +67,9 @@ def _validate(ID_field, dat_anomaly, cell_areas):
     return shape, tname, tv, w
 
 
-def _device_slots(eng, ID_field, dat_anomaly, w, T: int, C: int, block_steps):
-    """The two passes over the field: the events' spans, then the sums.  ``(N, tmin, off, cnt, sums, vmax)`` on the host."""
-    import torch
-
-    ids_w = _Windows(eng, ID_field, T, C, np.int32, True)
-    an_w = _Windows(eng, dat_anomaly, T, C, np.float32, False)
-    B = _plan_windows(eng, T, C, ids_w.upload_bytes_per_step + an_w.upload_bytes_per_step, block_steps)
-    wins = [(a, min(T, a + B)) for a in range(0, T, B)]
+def _event_spans(eng, ids_w, wins):
+    """The first pass over the field: ``(tmin, tmax, kept)``, the first and last step of the events 0..N (int64, entry 0
+    unused) and the window itself where the field is taken whole."""
     kept = None
     tmin, tmax = np.zeros(1, np.int64), np.zeros(1, np.int64)
     tmin[0], tmax[0] = _I32_MAX, -1
@@ -95,8 +90,20 @@ def _device_slots(eng, ID_field, dat_anomaly, w, T: int, C: int, block_steps):
         tmin[:n] = np.where(seen, np.minimum(tmin[:n], lo + a), tmin[:n])
         tmax[:n] = np.where(seen, np.maximum(tmax[:n], hi + a), tmax[:n])
         del x
-    N = int(tmin.size) - 1
     tmin[0], tmax[0] = _I32_MAX, -1
+    return tmin, tmax, kept
+
+
+def _device_slots(eng, ID_field, dat_anomaly, w, T: int, C: int, block_steps):
+    """The two passes over the field: the events' spans, then the sums.  ``(N, tmin, off, cnt, sums, vmax)`` on the host."""
+    import torch
+
+    ids_w = _Windows(eng, ID_field, T, C, np.int32, True)
+    an_w = _Windows(eng, dat_anomaly, T, C, np.float32, False)
+    B = _plan_windows(eng, T, C, ids_w.upload_bytes_per_step + an_w.upload_bytes_per_step, block_steps)
+    wins = [(a, min(T, a + B)) for a in range(0, T, B)]
+    tmin, tmax, kept = _event_spans(eng, ids_w, wins)
+    N = int(tmin.size) - 1
     if N <= 0:
         return 0, tmin, np.zeros(2, np.int64), np.zeros((0, 2), np.int64), np.zeros((0, 2)), np.zeros(0, np.float32)
     wd = None if w is None else torch.from_numpy(w).to(eng.device)

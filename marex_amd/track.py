@@ -929,6 +929,31 @@ class tracker(_MeshStages):  # noqa: N801 -- the reference's public name (marEx.
         ds.attrs.update(events_ds.attrs)
         return ds
 
+    def event_categories(self, events_ds, extremes_ds, thresholds=None, per_timestep: bool = False, return_field: bool = False,
+                         block_steps: Union[int, str, None] = None):
+        """The events Dataset of :meth:`run` with the severity categories of every event added
+        (:func:`marex_amd.event_categories.event_categories` has the variables): ``events_ds["ID_field"]`` joined with
+        ``extremes_ds["dat_anomaly"]`` and, unless ``thresholds`` is passed, ``extremes_ds["thresholds"]`` (the Dataset of
+        ``preprocess_data``), on this tracker's device, under its time names and with the area weights
+        :meth:`event_intensity` takes.  Returns a new Dataset; ``events_ds`` is not changed.  The ``ID`` axis of a merge
+        tracker's Dataset is checked against what the pass found (:class:`ProcessingError`)."""
+        from .event_categories import _event_categories
+        from .xr_compat import Dataset
+
+        w = np.asarray(self.cell_area, np.float32) if self.unstructured_grid else getattr(self, "_cell_weights", None)
+        n = int(np.asarray(events_ds["ID"].values).size) if "ID" in events_ds else None
+        thr = extremes_ds["thresholds"] if thresholds is None else thresholds
+        out = _event_categories(events_ds["ID_field"], extremes_ds["dat_anomaly"], thr, w, per_timestep, return_field,
+                                block_steps, self.device, n_events=n, time=(self.timedim, self.timecoord, self.time_values))
+        if n is not None and not np.array_equal(np.asarray(out["ID"].values), np.asarray(events_ds["ID"].values)):
+            raise ProcessingError("event_categories: the events of the ID field are not those of the events Dataset",
+                                  details=f"IDs 1..{int(np.asarray(out['ID'].values).size)} found, the Dataset lists {n}")
+        data = dict(events_ds.data_vars)
+        data.update(out.data_vars)
+        ds = Dataset(data)
+        ds.attrs.update(events_ds.attrs)
+        return ds
+
     def event_occurrence(self, events_ds, **kw):
         """Occurrence statistics of the events of :meth:`run` (:func:`marex_amd.occurrence.event_occurrence` has the
         arguments and the variables) from ``events_ds["ID_field"]``, on this tracker's device.  On a mesh ``lat`` defaults
