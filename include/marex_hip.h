@@ -775,6 +775,46 @@ int marex_cell_events_u8(marex_ctx* ctx, const uint8_t* x, const float* anom, in
                          int32_t* rec_end, uint32_t* rec_vmax, int32_t* rec_tmax, double* rec_sum, uint32_t* rec_invalid,
                          uint64_t* status);
 
+/* Compound events of two presence fields A and B, from one streaming pass over both (the reference's guide builds the
+ * joint mask on the host, docs/user_guide.rst:821-833: sst_extremes.extreme_events & salinity_extremes.extreme_events, and
+ * leaves every statistic of it to the user).
+ *
+ * marex_compound_u8: a, b uint8 [Tb][C] are the rows t0 .. t0 + Tb - 1 of the fields; a cell is present where the byte is
+ *   not 0.  With A[t], B[t] the presence of a cell at the global step t, L = max_lag and K = tolerance (both 0 .. 30):
+ *   cell_cnt uint32 [3][G][C]: per present row cell_cnt[0][grp[t]][c] += A, [1] += B, [2] += A and B.  grp int32 [T] is
+ *   indexed by the global step and must reach t0 + Tb; NULL with G == 1: every step is group 0.  A label outside
+ *   0 .. G - 1 addresses nothing: the present cells of A and those of B add to status[1].
+ *   state uint32 [13][C]: what a cell carries between calls, read at the start and written at the end of a call, so a
+ *   record walked in any sequence of time windows gives the arrays of one call.  Rows 0 .. 2: the joint run open after the
+ *   rows seen so far, the joint runs begun, the longest joint run (run_state of marex_occurrence_* on A and B).  Rows 3, 4:
+ *   the history of A and of B, bit l the presence l steps ago (with L == 0 kept up to bit K; with L > 0 rows 11, 12 hold
+ *   the steps 32 .. 61 ago; max_lag and tolerance must be those of the record's first call).  Rows 5, 6: the run coincidence
+ *   of A and of B (bit 30: a run is open, bit 31: it has met the other field, bits 0 .. K - 1: unmet runs that ended
+ *   i + 1 steps ago).  Rows 7 .. 10: the runs of A, those of them that are coincident, the runs of B, those of them that
+ *   are coincident.  A run [s, e] of A (maximal, consecutive present steps) is coincident when B is present at some step
+ *   of [max(0, s - K), min(T - 1, e + K)]; the same for B with the roles swapped.  A run open after the last row is a
+ *   run, judged on the rows seen.
+ *   lag_cnt uint32 [2 L + 1][C], given exactly with L > 0: lag_cnt[L + l][c] is the number of steps t with A[t] and
+ *   B[t + l], both steps inside the record, l = -L .. L; row L equals the sum over the groups of cell_cnt[2].
+ *   sec_cnt uint64 [3][G2][R] with sgrp int32 [T] and cls int32 [C], or all three NULL: the three counts per (step label,
+ *   cell class) as sec_cnt of marex_occurrence_*; under a label outside 0 .. G2 - 1 the cells of A and those of B that
+ *   have a class add to status[1].
+ *   mask uint8, or NULL: the base of the WHOLE [T][C] joint mask, addressed with the global step.  Every byte of the rows
+ *   t0 .. t0 + Tb - 1 is written: 1 where A and B, else 0.  mask must not overlap a or b.
+ *   status uint64 [2]; [0] is not used.  The function only continues state, cell_cnt, lag_cnt, sec_cnt and status: the
+ *   caller zeroes them before the first window.  All results are integers, exact and independent of the order of
+ *   execution and of the windows.  No atomic touches a per-cell output.
+ *   Four cells per lane through 32-bit accesses when C % 4 == 0, a, b and mask are 4-byte and state, cell_cnt and lag_cnt
+ *   are 16-byte aligned; one cell per lane otherwise: same results.
+ *   -1: null a, b, state, cell_cnt or status, empty shape, t0 < 0, G <= 0, NULL grp with G != 1, max_lag or tolerance
+ *   outside 0 .. 30, lag_cnt given without max_lag > 0 or missing with it, sec_cnt / sgrp / cls given in part or with
+ *   G2 <= 0 or R <= 0; -4: C or t0 + Tb of 2^31 - 1 or more (the fields themselves may hold any number of cells: they are
+ *   addressed with 64-bit offsets).  Asynchronous on the context's stream. */
+int marex_compound_u8(marex_ctx* ctx, const uint8_t* a, const uint8_t* b, int64_t t0, int64_t Tb, int64_t C, int max_lag,
+                      int tolerance, const int32_t* grp, int G, const int32_t* sgrp, int G2, const int32_t* cls, int R,
+                      uint32_t* state, uint32_t* cell_cnt, uint32_t* lag_cnt, uint64_t* sec_cnt, uint8_t* mask,
+                      uint64_t* status);
+
 /* The partition kernels of the split-and-merge stage on an unstructured mesh (tracker.split_and_merge_objects_parallel,
  * marEx/track.py:3804-4814, 5246-5419).  A slice is int32 [C], values <= 0 are background, C below 2^31 - 1.  u: float64
  * [3][C], the unit vectors of the cells; pv: float64 [3][n], the unit vectors of the parents' centroids.  "Nearest" is the

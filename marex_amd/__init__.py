@@ -8,7 +8,8 @@ Beyond the reference: ``preprocess_data`` and ``identify_extremes`` take ``neigh
 on unstructured meshes -- day-of-year thresholds pooled over the cell and one or two rings of its listed neighbours, the mesh
 counterpart of ``window_spatial_hobday``.  ``event_categories`` and ``tracker.event_categories`` give the severity
 categories (Hobday et al. 2018) of every tracked event and the category map of every timestep, from ``ID_field``,
-``dat_anomaly`` and ``thresholds`` on the device.
+``dat_anomaly`` and ``thresholds`` on the device.  ``compound_events`` joins two presence fields in one pass on the device:
+joint, lagged and run-level coincidence per cell, by time group and by latitude class.
 """
 from .detect import (
     compute_normalised_anomaly,
@@ -32,6 +33,7 @@ from .event_categories import event_categories
 from .occurrence import event_occurrence
 from .local_intensity import local_intensity
 from .cell_events import cell_events
+from .compound import compound_events
 from .track import tracker
 from .xr_compat import DataArray, Dataset
 
@@ -40,6 +42,6 @@ __all__ = [
     "smoothed_rolling_climatology", "MarExError", "DataValidationError", "ConfigurationError",
     "ProcessingError", "DependencyError", "create_data_validation_error", "DataArray", "Dataset",
     "tracker", "TrackingError", "event_intensity", "event_occurrence", "local_intensity",
-    "cell_events", "event_categories",
+    "cell_events", "event_categories", "compound_events",
 ]
 __version__ = "0.1.0"

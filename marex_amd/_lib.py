@@ -124,6 +124,7 @@ PROTOTYPES = {
     "marex_event_categories_f32": (_i32, [_p, _p, _p, _i64, _i64, _i64, _i32, _p, _p, _i64, _p, _p, _i32, _p, _p, _p, _p, _p]),
     "marex_occurrence_u8": (_i32, [_p, _p, _i64, _i64, _i64, _i32, _p, _i32, _p, _i32, _p, _i32, _p, _p, _p, _p]),
     "marex_occurrence_i32": (_i32, [_p, _p, _i64, _i64, _i64, _i32, _p, _i32, _p, _i32, _p, _i32, _p, _p, _p, _p]),
+    "marex_compound_u8": (_i32, [_p, _p, _p, _i64, _i64, _i64, _i32, _i32, _p, _i32, _p, _i32, _p, _i32, _p, _p, _p, _p, _p, _p]),
     "marex_local_intensity_u8": (_i32, [_p, _p, _p, _i64, _i64, _i64, _i32, _p, _i32, _p, _p, _i32, _p, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _p]),
     "marex_local_intensity_i32": (_i32, [_p, _p, _p, _i64, _i64, _i64, _i32, _p, _i32, _p, _p, _i32, _p, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _p]),
     "marex_cell_events_u8": (_i32, [_p, _p, _p, _i64, _i64, _i64, _i32, _i32, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,

@@ -68,10 +68,13 @@ def _time_of(field, T: int):
     return name, (v if v.shape == (T,) else None)
 
 
-def plan_field(field, what: str, partner=None) -> dict:
+def plan_field(field, what: str, partner=None, names=("field", "dat_anomaly"), presence_partner: bool = False) -> dict:
     """What a presence field says without a device: ``shape``, ``T``, ``C``, ``kind`` ('m' mask, 'i' IDs), ``bool``, the
     time axis (``tname``, ``tv``), the spatial dimensions ``sdims`` and their coordinates ``scoords``.  ``partner``: the
-    anomaly field, which must agree in shape, dimensions and time; its names and coordinates fill in what the field lacks."""
+    anomaly field, which must agree in shape, dimensions and time; its names and coordinates fill in what the field lacks.
+    ``presence_partner``: the partner is a second presence field, not a float one (adds ``kind_b`` and ``bool_b``);
+    ``names``: what the errors call the two."""
+    fname, pname = names
     shape = tuple(int(k) for k in field.shape)
     if len(shape) not in (2, 3):
         raise create_data_validation_error("field must be (time, y, x) or (time, cells)", details=f"got shape {shape}")
@@ -80,13 +83,14 @@ def plan_field(field, what: str, partner=None) -> dict:
     if partner is not None:
         ashape = tuple(int(k) for k in partner.shape)
         if ashape != shape:
-            raise create_data_validation_error("field and dat_anomaly differ in shape", details=f"field {shape}, dat_anomaly {ashape}")
+            raise create_data_validation_error(f"{fname} and {pname} differ in shape", details=f"{fname} {shape}, {pname} {ashape}")
         d_a = tuple(getattr(partner, "dims", ()) or ())
         if dims and d_a and dims != d_a:
-            raise create_data_validation_error("field and dat_anomaly differ in their dimensions",
-                                               details=f"field {dims}, dat_anomaly {d_a}; the order must agree too")
+            raise create_data_validation_error(f"{fname} and {pname} differ in their dimensions",
+                                               details=f"{fname} {dims}, {pname} {d_a}; the order must agree too")
     kind = _field_kind(field)
-    if partner is not None and _kind(partner) != "f":
+    kind_b = _field_kind(partner) if presence_partner and partner is not None else None
+    if partner is not None and not presence_partner and _kind(partner) != "f":
         raise create_data_validation_error("dat_anomaly must be a floating-point field",
                                            details=f"Found dtype {_dtype_name(partner)}",
                                            data_info={"actual_dtype": _dtype_name(partner)})
@@ -98,7 +102,7 @@ def plan_field(field, what: str, partner=None) -> dict:
     if partner is not None:
         _, tv_a = _time_of(partner, T)
         if tv is not None and tv_a is not None and not np.array_equal(tv, tv_a):
-            raise create_data_validation_error("field and dat_anomaly differ in their time coordinate",
+            raise create_data_validation_error(f"{fname} and {pname} differ in their time coordinate",
                                                details=f"the first difference is at step {int(np.argmax(tv != tv_a))}")
         tv = tv if tv is not None else tv_a
     labelled = dims or d_a
@@ -109,8 +113,11 @@ def plan_field(field, what: str, partner=None) -> dict:
             cd = tuple(getattr(c, "dims", ()) or ())
             if cd and all(d in sdims for d in cd):
                 coords[k] = (cd, np.asarray(_host(c)))
-    return dict(kind=kind, bool=_dtype_name(field) == "bool", shape=shape, T=T, C=C, tname=tname, tv=tv, labelled=bool(labelled),
-                sdims=sdims, scoords=coords)
+    p = dict(kind=kind, bool=_dtype_name(field) == "bool", shape=shape, T=T, C=C, tname=tname, tv=tv, labelled=bool(labelled),
+             sdims=sdims, scoords=coords)
+    if kind_b is not None:
+        p.update(kind_b=kind_b, bool_b=_dtype_name(partner) == "bool")
+    return p
 
 
 def plan_sections(p: dict, zonal_by, lat, lat_bins):

@@ -1618,6 +1618,79 @@ class HotPath:
                    dur=host(acc["dur"], np.uint32) if ids else np.zeros((0, Cn), np.uint32))
         return out
 
+    #: rows of the state a cell carries between the windows of :meth:`compound` (include/marex_hip.h)
+    COMPOUND_STATE_ROWS = 13
+    #: the largest ``max_lag`` / ``tolerance`` of :meth:`compound`: what the history words of a field hold
+    COMPOUND_MAX_LAG = 30
+
+    def compound(self, a: torch.Tensor, b: torch.Tensor, t0: int = 0, max_lag: int = 0, tolerance: int = 0, grp=None, G: int = 1,
+                 sgrp=None, G2: int = 0, cls=None, R: int = 0, mask: Optional[torch.Tensor] = None, acc: Optional[dict] = None,
+                 finish: bool = True) -> Dict[str, object]:
+        """Compound events of the rows ``t0 .. t0 + Tb - 1`` of two presence fields (``marex_compound_u8``): ``a`` and ``b``
+        uint8 or bool (read as uint8) ``[Tb, C]``, present where nonzero.  ``max_lag`` and ``tolerance``: ``0 .. 30``.
+        ``grp``, ``G``, ``sgrp``, ``G2``, ``cls`` and ``R`` as in :meth:`occurrence`.  ``mask``: the WHOLE contiguous uint8
+        ``[T, C]`` joint mask on the engine's device, ``T >= t0 + Tb`` (the rows of this window are written, zeros
+        included), or None.  The first window allocates zeroed accumulators and uploads the tables; a later window passes
+        the ``"acc"`` entry of the previous result -- the window lengths do not matter, histories, open and waiting runs
+        are carried.  Returns ``acc`` and -- unless ``finish`` is False, which defers them and the one host read --
+        ``days`` uint32 ``[3, G, C]`` (steps with A, with B, with both), ``runs`` uint32 ``[3, C]`` (the joint mask's open
+        run, runs begun, longest run), ``co`` uint32 ``[4, C]`` (runs of A, coincident runs of A, runs of B, coincident runs
+        of B), ``lag_days`` uint32 ``[2 max_lag + 1, C]`` (None with ``max_lag == 0``) and ``sec_cnt`` uint64
+        ``[3, G2, R]`` (None without sections).  A step label outside its range raises :class:`ProcessingError`; its
+        cells were counted, nothing was written out of range."""
+        a, Tb, Cn = self._presence_window("compound", a)
+        b, Tb_b, Cn_b = self._presence_window("compound", b)
+        if a.dtype != torch.uint8 or b.dtype != torch.uint8 or (Tb_b, Cn_b) != (Tb, Cn):
+            raise ProcessingError("compound: both fields must be uint8 or bool windows of one shape",
+                                  details=f"got {a.dtype} {tuple(a.shape)} and {b.dtype} {tuple(b.shape)}")
+        ints = (t0, max_lag, tolerance, G, G2, R)
+        if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in ints):
+            raise ProcessingError("compound: t0, max_lag, tolerance, G, G2 and R must be integers", details=f"got {ints}")
+        t0, L, K, G, G2, R = (int(v) for v in ints)
+        sect = sgrp is not None or cls is not None
+        if t0 < 0 or G <= 0 or (grp is None and G != 1) or not 0 <= L <= self.COMPOUND_MAX_LAG or not 0 <= K <= self.COMPOUND_MAX_LAG:
+            raise ProcessingError(f"compound: t0 must not be negative, G must be positive, G > 1 needs labels, and max_lag and "
+                                  f"tolerance must lie in 0 .. {self.COMPOUND_MAX_LAG}",
+                                  details=f"t0 = {t0}, G = {G}, labels {'given' if grp is not None else 'missing'}, max_lag = {L}, "
+                                          f"tolerance = {K}")
+        if sect and (sgrp is None or cls is None or G2 <= 0 or R <= 0):
+            raise ProcessingError("compound: the section counts need step labels, cell classes, G2 > 0 and R > 0 together",
+                                  details=f"G2 = {G2}, R = {R}")
+        if mask is not None and (mask.dtype != torch.uint8 or mask.dim() != 2 or int(mask.shape[1]) != Cn or
+                                 int(mask.shape[0]) < t0 + Tb or not mask.is_contiguous() or mask.device != self.device):
+            raise ProcessingError(f"compound: the mask must be the whole contiguous uint8 [T, {Cn}] output on the engine's "
+                                  f"device, T >= {t0 + Tb}", details=f"got {mask.dtype} {tuple(mask.shape)} on {mask.device}")
+        S = self.COMPOUND_STATE_ROWS
+        plan = (G, Cn, G2 if sect else 0, R if sect else 0, L, K)
+        if acc is None:
+            tabs = label_tables("compound", (("grp", grp, None), ("sgrp", sgrp if sect else None, None),
+                                             ("cls", cls if sect else None, Cn)))
+            rows = 3 * G + S + (2 * L + 1 if L else 0)
+            need = 4 * rows * Cn + (24 * G2 * R if sect else 0) + 16 + sum(4 * v.size for v in tabs.values() if v is not None)
+            self._check_fits(need, "compound",
+                             f"3 x {G} x {Cn} uint32 counts, {S} x {Cn} uint32 of carried state, {2 * L + 1 if L else 0} x {Cn} "
+                             f"uint32 lag counts, 3 x {G2 if sect else 0} x {R if sect else 0} uint64 section counts, and the "
+                             f"label tables")
+            acc = {"cell_cnt": self._buf(None, "cmp_cnt", (3, G, Cn), torch.int32, self.device).zero_(),
+                   "state": self._buf(None, "cmp_state", (S, Cn), torch.int32, self.device).zero_(),
+                   "lag": self._buf(None, "cmp_lag", (2 * L + 1, Cn), torch.int32, self.device).zero_() if L else None,
+                   "sec_cnt": self._buf(None, "cmp_sec", (3, G2, R), torch.int64, self.device).zero_() if sect else None,
+                   "status": self._buf(None, "cmp_status", (2,), torch.int64, self.device).zero_(),
+                   "plan": plan, **self._upload_tables(tabs)}
+        self._window_check("compound", acc, plan, ("grp", "sgrp"), t0, Tb, Cn)
+        tb = acc["tabs"]
+        self.call("marex_compound_u8", a, b, t0, Tb, Cn, L, K, tb["grp"], G, tb["sgrp"], G2 if sect else 0, tb["cls"],
+                  R if sect else 0, acc["state"], acc["cell_cnt"], acc["lag"], acc["sec_cnt"], mask, acc["status"])
+        out: Dict[str, object] = {"acc": acc}
+        if not finish:
+            return out
+        self._stream_status("compound", acc, 1, f"grp must hold 0 .. {G - 1}, sgrp 0 .. {G2 - 1}")
+        host = self._host
+        state = host(acc["state"], np.uint32)
+        out.update(days=host(acc["cell_cnt"], np.uint32), runs=state[0:3], co=state[7:11], lag_days=host(acc["lag"], np.uint32),
+                   sec_cnt=host(acc["sec_cnt"], np.uint64))
+        return out
+
     def local_intensity(self, x: torch.Tensor, anom: torch.Tensor, t0: int = 0, grp=None, G: int = 1,
                         thr: Optional[torch.Tensor] = None, doy=None, sgrp=None, G2: int = 0, cls=None, R: int = 0,
                         acc: Optional[dict] = None, finish: bool = True, match: int = 0) -> Dict[str, object]:
