@@ -1583,8 +1583,24 @@ k_mask_tails(const uint4* __restrict__ lists, const unsigned* __restrict__ aux, 
     auto lane_ptr = [](const void* base, unsigned lane_bytes) { return reinterpret_cast<const char*>(base) + lane_bytes; };
     unsigned cnt_true = 0;
     unsigned n_slow = 0;
+    // the threshold's bin without a table look-up where the table is the arange one and the fused guess is provably within
+    // one bin (the condition and the arithmetic of k_tail_extract's lean digitize); block-wide, before any lane leaves
+    bool lean = edges_are_arange(edges, nb);
+    const float e_first = edges[1], e_delta = edges[2] - edges[1], e_last = edges[nb];
+    {
+        const double m = fabs((double)e_first) > fabs((double)e_last) ? fabs((double)e_first) : fabs((double)e_last);
+        lean = lean && e_delta > 0.f && ((double)nb + 2.0 * m / (double)e_delta) * (1.0 / 1048576.0) < 1.0 / 256.0;
+    }
+    const float inv_width = (float)(nb - 1) / (e_last - e_first);
+    const float dg0 = (1.0f - e_first * inv_width) - 0.0078125f, nbm1f = (float)(nb - 1);  // +1 (edges[0] = -inf), 1/128 bin down
+    // one row's word of four mask bytes: a 4-byte non-temporal store at out + off + the lane's first cell.  Written as the
+    // instruction itself: from C++ the compiler adds the row offset to a 64-bit lane address (two more live registers and a
+    // 64-bit vector add per row) however the sum is spelled
+    auto store_row = [&](unsigned m, long long off) {
+        const unsigned char* base = out + off;  // wave-uniform: one scalar 64-bit add, the lane's cell is the 32-bit offset
+        asm volatile("global_store_dword %0, %1, %2 nt" : : "v"(cu), "v"(m), "s"(base) : "memory");
+    };
     if (c >= c0 && c < c1) {
-        const float inv_width = (float)(nb - 1) / (edges[nb] - edges[1]);
         for (int d = dA; d < dB; ++d) {
             const int r0 = doy_start[d], nd = doy_start[d + 1] - r0;
             if (nd == 0) continue;
@@ -1602,7 +1618,14 @@ k_mask_tails(const uint4* __restrict__ lists, const unsigned* __restrict__ aux, 
 #pragma unroll
                     for (int wi = 0; wi < NW; ++wi) bits[i][wi] = 0u;
                     const bool isnum = tv[i] == tv[i];
-                    const int kt = isnum ? digitize_bin(tv[i], edges, nb, inv_width) : nb;  // NaN threshold: nothing is extreme
+                    int kt = nb;  // NaN threshold: nothing is extreme
+                    if (lean) {
+                        const float t = __builtin_amdgcn_fmed3f(__builtin_floorf(__builtin_fmaf(tv[i], inv_width, dg0)), 0.0f, nbm1f);
+                        const float ehi = e_first + t * e_delta;  // edges[t + 1], the table's own arithmetic (separately rounded)
+                        if (isnum) kt = (int)t + (tv[i] >= ehi ? 1 : 0);
+                    } else if (isnum) {
+                        kt = digitize_bin(tv[i], edges, nb, inv_width);
+                    }
                     // values beyond the table are extremes of every threshold INSIDE the table (any threshold the histogram
                     // quantile produces); more than two of them, or a threshold beyond the table itself: look at the values
                     slow = slow || (isnum && (av[i] & TAIL_AUX_BEYOND) && ((av[i] & TAIL_AUX_MANY) || kt >= nb));
@@ -1760,29 +1783,35 @@ k_mask_tails(const uint4* __restrict__ lists, const unsigned* __restrict__ aux, 
                     __builtin_nontemporal_store(m0 | (m1 << 8) | (m2 << 16) | (m3 << 24), reinterpret_cast<unsigned*>(out + off + cell(0)));
                 }
             } else {
-                // rows in groups of 8: eight row offsets per scalar load batch, bit positions known at compile time
+                // rows in groups of 8: eight row offsets per scalar load batch.  The four cells' words of row bits are
+                // transposed byte-wise first (8 v_perm_b32 per 32 rows): X[g] holds byte g of cell j's word in its byte j,
+                // so row rr of group g is (X[g] >> rr) & 0x01010101 -- bit rr of every byte lands on the byte's bit 0 and the
+                // mask drops what crossed a byte boundary: two instructions per row instead of four extracts and three ors
 #pragma unroll
                 for (int wi = 0; wi < NW; ++wi) {
                     const unsigned b0 = bits[0][wi], b1 = bits[1][wi], b2 = bits[2][wi], b3 = bits[3][wi];
                     cnt_true += __popc(b0) + __popc(b1) + __popc(b2) + __popc(b3);
                     if (wi * 32 >= nd) break;
+                    // v_perm_b32: selector bytes 0..3 take the bytes of the second operand, 4..7 those of the first
+                    const unsigned t0 = __builtin_amdgcn_perm(b1, b0, 0x05010400u), t1 = __builtin_amdgcn_perm(b1, b0, 0x07030602u);
+                    const unsigned u0 = __builtin_amdgcn_perm(b3, b2, 0x05010400u), u1 = __builtin_amdgcn_perm(b3, b2, 0x07030602u);
+                    const unsigned X[4] = {__builtin_amdgcn_perm(u0, t0, 0x05040100u), __builtin_amdgcn_perm(u0, t0, 0x07060302u),
+                                           __builtin_amdgcn_perm(u1, t1, 0x05040100u), __builtin_amdgcn_perm(u1, t1, 0x07060302u)};
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
                         const int rlo = wi * 32 + g * 8;
                         if (rlo >= nd) break;
-                        const unsigned q0 = b0 >> (g * 8), q1 = b1 >> (g * 8), q2 = b2 >> (g * 8), q3 = b3 >> (g * 8);
                         const long long* ro = row_off + r0 + rlo;
                         if (rlo + 8 <= nd) {
+                            long long o[8];  // all eight offsets first: the stores are asm statements that clobber memory
 #pragma unroll
-                            for (int rr = 0; rr < 8; ++rr) {
-                                const unsigned m = ((q0 >> rr) & 1u) | (((q1 >> rr) & 1u) << 8) | (((q2 >> rr) & 1u) << 16) | (((q3 >> rr) & 1u) << 24);
-                                __builtin_nontemporal_store(m, reinterpret_cast<unsigned*>(out + ro[rr] + cu));
-                            }
+                            for (int rr = 0; rr < 8; ++rr) o[rr] = ro[rr];
+#pragma unroll
+                            for (int rr = 0; rr < 8; ++rr)
+                                store_row((X[g] >> rr) & 0x01010101u, o[rr]);
                         } else {
-                            for (int rr = 0; rr < nd - rlo; ++rr) {
-                                const unsigned m = ((q0 >> rr) & 1u) | (((q1 >> rr) & 1u) << 8) | (((q2 >> rr) & 1u) << 16) | (((q3 >> rr) & 1u) << 24);
-                                __builtin_nontemporal_store(m, reinterpret_cast<unsigned*>(out + ro[rr] + cu));
-                            }
+                            for (int rr = 0; rr < nd - rlo; ++rr)
+                                store_row((X[g] >> rr) & 0x01010101u, ro[rr]);
                         }
                     }
                 }
