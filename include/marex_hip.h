@@ -815,6 +815,34 @@ int marex_compound_u8(marex_ctx* ctx, const uint8_t* a, const uint8_t* b, int64_
                       uint32_t* state, uint32_t* cell_cnt, uint32_t* lag_cnt, uint64_t* sec_cnt, uint8_t* mask,
                       uint64_t* status);
 
+/* Per-cell trends of a short series of maps: y float64 [G][C], the G maps of C cells (2 <= G <= 256, C below 2^31 - 1),
+ * x float64 [G] their finite, strictly increasing abscissae (the caller checks that).  A sample that is not finite is a
+ * missing sample of its cell; n is the number of valid ones and P = n (n - 1) / 2 the number of pairs i < j of them.  The
+ * slope of a pair is ((y[j] - y[i]) / (x[j] - x[i])) + 0.0: two subtractions, one IEEE division, and the addition that
+ * makes -0.0 and +0.0 one value; nothing is contracted.
+ *
+ * marex_trend_stats_f64, one launch, per cell c: n[c]; s[c] = sum over the pairs of sign(y[j] - y[i]) (Mann-Kendall S);
+ *   ties[c] = sum over the valid samples of (t - 1)(2 t + 5), t the number of valid samples equal to it, itself included
+ *   (that is sum over the tie groups of t (t - 1)(2 t + 5); -0.0 equals +0.0); med float64 [2][C]: [0] the median of the
+ *   valid y, (0.5 * (lower + upper middle of the sorted samples)) + 0.0, found from the counts of smaller and equal
+ *   samples without a sort, [1] the same of the x of the valid samples; sums float64 [5][C]: xbar = (sum x) / n,
+ *   ybar = (sum y) / n, Sxx = sum (x - xbar)^2, Sxy = sum (x - xbar)(y - ybar), Syy = sum (y - ybar)^2, each sum over the
+ *   valid samples in ascending step order by sequential float64 additions of separately rounded products.  A cell with
+ *   n == 0 has NaN medians and means and zero sums; status is not touched.
+ * marex_trend_select_f64: ranks int32 [K][C], out float64 [K][C] (K >= 1): out[k][c] is the ranks[k][c]-th smallest
+ *   (0-based) of the P slopes of cell c, NaN for a rank outside 0 .. P - 1.  The slopes are never stored: a bisection over
+ *   the order-preserving 64-bit keys of the doubles between -inf and +inf recomputes them in each of its at most 64 steps
+ *   and counts those not above the pivot, each quotient compared with up to four pivots of the cell.  A selection that
+ *   has not closed after 64 steps writes NaN and adds 1 to status[1] (int64 [2], continued: the caller zeroes it; [0] is
+ *   not used).
+ * A lane owns a cell; a wave keeps its 64 cells' samples in LDS up to G = 128 (statistics) or G = 64 (selection) and
+ * re-reads y above (same results).  y needs no more than its natural 8-byte alignment.
+ * -1: null pointer, G outside 2 .. 256, C <= 0, K <= 0; -4: C of 2^31 - 1 or more.  Asynchronous on the context's stream. */
+int marex_trend_stats_f64(marex_ctx* ctx, const double* y, const double* x, int G, int64_t C, int32_t* n, int32_t* s,
+                          int32_t* ties, double* med, double* sums, int64_t* status);
+int marex_trend_select_f64(marex_ctx* ctx, const double* y, const double* x, int G, int64_t C, const int32_t* ranks, int K,
+                           double* out, int64_t* status);
+
 /* The partition kernels of the split-and-merge stage on an unstructured mesh (tracker.split_and_merge_objects_parallel,
  * marEx/track.py:3804-4814, 5246-5419).  A slice is int32 [C], values <= 0 are background, C below 2^31 - 1.  u: float64
  * [3][C], the unit vectors of the cells; pv: float64 [3][n], the unit vectors of the parents' centroids.  "Nearest" is the

@@ -9,7 +9,8 @@ on unstructured meshes -- day-of-year thresholds pooled over the cell and one or
 counterpart of ``window_spatial_hobday``.  ``event_categories`` and ``tracker.event_categories`` give the severity
 categories (Hobday et al. 2018) of every tracked event and the category map of every timestep, from ``ID_field``,
 ``dat_anomaly`` and ``thresholds`` on the device.  ``compound_events`` joins two presence fields in one pass on the device:
-joint, lagged and run-level coincidence per cell, by time group and by latitude class.
+joint, lagged and run-level coincidence per cell, by time group and by latitude class.  ``cell_trends`` gives the per-cell
+trend of a series of annual maps -- Theil-Sen slope with confidence bounds, Mann-Kendall test, least squares -- on the device.
 """
 from .detect import (
     compute_normalised_anomaly,
@@ -34,6 +35,7 @@ from .occurrence import event_occurrence
 from .local_intensity import local_intensity
 from .cell_events import cell_events
 from .compound import compound_events
+from .trends import cell_trends
 from .track import tracker
 from .xr_compat import DataArray, Dataset
 
@@ -42,6 +44,6 @@ __all__ = [
     "smoothed_rolling_climatology", "MarExError", "DataValidationError", "ConfigurationError",
     "ProcessingError", "DependencyError", "create_data_validation_error", "DataArray", "Dataset",
     "tracker", "TrackingError", "event_intensity", "event_occurrence", "local_intensity",
-    "cell_events", "event_categories", "compound_events",
+    "cell_events", "event_categories", "compound_events", "cell_trends",
 ]
 __version__ = "0.1.0"

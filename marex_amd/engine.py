@@ -1691,6 +1691,63 @@ class HotPath:
                    sec_cnt=host(acc["sec_cnt"], np.uint64))
         return out
 
+    #: the longest series :meth:`trend_stats` and :meth:`trend_select` take (include/marex_hip.h)
+    TREND_MAX_STEPS = 256
+
+    def _trend_check(self, what: str, y: torch.Tensor, x: torch.Tensor) -> tuple:
+        """``(G, C)`` of the maps ``y`` float64 ``[G, C]`` over ``x`` float64 ``[G]``, both contiguous on the engine's device."""
+        for name, t, nd in (("y", y, 2), ("x", x, 1)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.dim() != nd or not t.is_contiguous() or \
+                    t.device != self.device:
+                raise ProcessingError(f"{what}: {name} must be a contiguous float64 {'[G, C]' if nd == 2 else '[G]'} tensor on "
+                                      "the engine's device",
+                                      details=f"got {getattr(t, 'dtype', type(t).__name__)} {tuple(getattr(t, 'shape', ()))} on "
+                                              f"{getattr(t, 'device', 'the host')}")
+        G, Cn = int(y.shape[0]), int(y.shape[1])
+        if int(x.shape[0]) != G or not 2 <= G <= self.TREND_MAX_STEPS or not 0 < Cn < 2**31 - 1:
+            raise ProcessingError(f"{what}: y must be [G, C] and x [G] with 2 <= G <= {self.TREND_MAX_STEPS} and 0 < C < 2^31 - 1",
+                                  details=f"got y {tuple(y.shape)} and x {tuple(x.shape)}")
+        return G, Cn
+
+    def trend_stats(self, y: torch.Tensor, x: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """Per cell of the maps ``y`` float64 ``[G, C]`` over the abscissae ``x`` float64 ``[G]`` (finite and strictly
+        increasing: the caller checks; a non-finite sample of ``y`` is missing), in one launch (``marex_trend_stats_f64``):
+        ``n`` int32 ``[C]`` valid samples, ``s`` int32 ``[C]`` the Mann-Kendall S, ``ties`` int32 ``[C]`` the sum over the
+        tie groups of ``t (t - 1)(2 t + 5)``, ``med`` float64 ``[2, C]`` the medians of the valid y and of their x, ``sums``
+        float64 ``[5, C]``: x mean, y mean, Sxx, Sxy, Syy.  Device tensors; nothing is read back."""
+        G, Cn = self._trend_check("trend_stats", y, x)
+        self._check_fits(4 * 3 * Cn + 8 * 7 * Cn + 16, "trend_stats", f"3 x {Cn} int32 and 7 x {Cn} float64 of results")
+        buf = lambda name, shape, dt: self._buf(None, name, shape, dt, self.device)  # noqa: E731
+        out = {"n": buf("trend_n", (Cn,), torch.int32), "s": buf("trend_s", (Cn,), torch.int32),
+               "ties": buf("trend_ties", (Cn,), torch.int32), "med": buf("trend_med", (2, Cn), torch.float64),
+               "sums": buf("trend_sums", (5, Cn), torch.float64)}
+        status = torch.zeros((2,), dtype=torch.int64, device=self.device)
+        self.call("marex_trend_stats_f64", y, x, G, Cn, out["n"], out["s"], out["ties"], out["med"], out["sums"], status)
+        return out
+
+    def trend_select(self, y: torch.Tensor, x: torch.Tensor, ranks) -> torch.Tensor:
+        """Order statistics of the pairwise slopes ``((y[j] - y[i]) / (x[j] - x[i])) + 0.0``, ``i < j`` both valid, of every
+        cell (``marex_trend_select_f64``): ``ranks`` int32 ``[K, C]`` (an array or a tensor), returns float64 ``[K, C]`` on
+        the device, the ``ranks[k, c]``-th smallest slope of cell ``c`` (0-based), NaN for a rank outside ``0 .. P - 1``.
+        Synchronises for the status word: a selection that did not close in 64 bisection steps raises
+        :class:`ProcessingError` (its output is NaN, nothing else was written)."""
+        G, Cn = self._trend_check("trend_select", y, x)
+        r = ranks if isinstance(ranks, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(ranks))
+        if r.dtype != torch.int32 or r.dim() != 2 or int(r.shape[1]) != Cn or int(r.shape[0]) < 1:
+            raise ProcessingError(f"trend_select: ranks must be int32 [K, {Cn}] with K >= 1",
+                                  details=f"got {r.dtype} {tuple(r.shape)}")
+        K = int(r.shape[0])
+        self._check_fits(12 * K * Cn + 16, "trend_select", f"{K} x {Cn} int32 ranks and as many float64 results")
+        r = r.to(self.device).contiguous()
+        out = self._buf(None, "trend_sel", (K, Cn), torch.float64, self.device)
+        status = torch.zeros((2,), dtype=torch.int64, device=self.device)
+        self.call("marex_trend_select_f64", y, x, G, Cn, r, K, out, status)
+        open_ = int(status[1].item())
+        if open_:
+            raise ProcessingError(f"trend_select: {open_} selections did not close within 64 bisection steps",
+                                  details="their results are NaN; this is a defect of the kernel, not of the data")
+        return out
+
     def local_intensity(self, x: torch.Tensor, anom: torch.Tensor, t0: int = 0, grp=None, G: int = 1,
                         thr: Optional[torch.Tensor] = None, doy=None, sgrp=None, G2: int = 0, cls=None, R: int = 0,
                         acc: Optional[dict] = None, finish: bool = True, match: int = 0) -> Dict[str, object]:
