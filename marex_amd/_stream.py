@@ -1,5 +1,7 @@
-"""What the streaming statistics (``intensity``, ``occurrence``, ``local_intensity``) share in front of the engine: what a
-``[time, space]`` field says without a device, the windows it is walked in, and the way back to its spatial dimensions."""
+"""What the streaming statistics (``intensity``, ``event_categories``, ``occurrence``, ``local_intensity``, ``cell_events``,
+``compound``; ``trends`` for the free memory) share in front of the engine: what a ``[time, space]`` field says without a
+device, the windows it is walked in -- with or without a part that stays for the whole call -- and the way back to its
+spatial dimensions."""
 from __future__ import annotations
 
 from typing import Optional
@@ -232,6 +234,21 @@ def _plan_windows(eng, T: int, C: int, per_step: int, block_steps, what: str = "
         free -= free // 16  # the slots, the small tables and the allocator's rounding
         return max(1, min(T, cap, free // per_step if per_step else T))
     return min(int(block_steps), T, cap)
+
+
+def _window_steps(eng, what: str, T: int, C: int, per_step: int, fixed: int, block_steps, details: str, suggestions=()) -> int:
+    """Steps per window of a call that keeps ``fixed`` bytes for its whole length (accumulators, carried state, thresholds,
+    a whole output) beside the ``per_step`` bytes of :func:`_plan_windows`.  ``suggestions``: what the caller can offer
+    beyond windows when the call does not fit."""
+    free = _free_bytes(eng)
+    need = fixed + per_step * (T if block_steps is None else 1)
+    if need > free:
+        raise TrackingError(f"{what}: needs {need / 1e9:.3f} GB of device memory, {free / 1e9:.3f} GB are free", details=details,
+                            suggestions=["Pass block_steps='auto'", "Pass block_steps=<timesteps per window>", *suggestions])
+    B = _plan_windows(eng, T, C, per_step, block_steps, what, details)
+    if block_steps == "auto" and per_step:
+        B = max(1, min(B, (free - free // 16 - fixed) // per_step))
+    return B
 
 
 def walk_windows(T: int, B: int, step):

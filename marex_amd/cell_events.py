@@ -14,8 +14,8 @@ from __future__ import annotations
 import numpy as np
 
 from . import _stream, occurrence as mo
-from ._stream import _I32_MAX, _Windows, _check_block_steps, _plan_windows
-from .exceptions import ConfigurationError, TrackingError, create_data_validation_error
+from ._stream import _I32_MAX, _Windows, _check_block_steps
+from .exceptions import ConfigurationError, create_data_validation_error
 from .track import _tensor_of
 
 
@@ -96,15 +96,8 @@ def _device_pass(p, field, dat_anomaly, return_mask, records, device):
                f"{accumulator_bytes(1, 1, anomalies)} bytes each, {'the mask of ' + str(T) + ' x ' + str(C) + ' bytes, ' if return_mask else ''}"
                f"and the field{' and the anomalies' if anomalies else ''} of {T} timesteps, 1{' + 4' if anomalies else ''} bytes "
                "per cell, as far as they are not on the device already")
-    free = _stream._free_bytes(eng)
-    need = fixed + per_step * (T if p["block_steps"] is None else 1)
-    if need > free:
-        raise TrackingError(f"cell_events: needs {need / 1e9:.3f} GB of device memory, {free / 1e9:.3f} GB are free", details=details,
-                            suggestions=["Pass block_steps='auto'", "Pass block_steps=<timesteps per window>", "Group by fewer labels"]
-                            + (["Pass return_mask=False"] if return_mask else []))
-    B = _plan_windows(eng, T, C, per_step, p["block_steps"], "cell_events", details)
-    if p["block_steps"] == "auto" and per_step:
-        B = max(1, min(B, (free - free // 16 - fixed) // per_step))
+    B = _stream._window_steps(eng, "cell_events", T, C, per_step, fixed, p["block_steps"], details,
+                              ["Group by fewer labels"] + (["Pass return_mask=False"] if return_mask else []))
     kw = dict(min_duration=D, max_gap=gap)
     if p["grp"] is not None:
         kw.update(grp=p["grp"][0], G=G)

@@ -16,8 +16,8 @@ from functools import partial
 import numpy as np
 
 from . import _stream
-from ._stream import _Windows, _check_block_steps, _plan_windows
-from .exceptions import ConfigurationError, TrackingError
+from ._stream import _Windows, _check_block_steps
+from .exceptions import ConfigurationError
 from .occurrence import _ratio, group_labels
 from .track import _tensor_of
 
@@ -100,16 +100,8 @@ def _device_pass(p, field_a, field_b, return_mask, device):
     details = (f"{3 * G + (2 * L + 1 if L else 0) + STATE_ROWS} x {C} uint32 of counts and carried state, {sec_bytes} bytes of "
                f"section counts, {'the joint mask of ' + str(T) + ' x ' + str(C) + ' bytes, ' if return_mask else ''}and both "
                f"fields of {T} timesteps, {wa.w.item} and {wb.w.item} bytes per cell, as far as they are not on the device already")
-    free = _stream._free_bytes(eng)
-    need = fixed + per_step * (T if p["block_steps"] is None else 1)
-    if need > free:
-        raise TrackingError(f"compound_events: needs {need / 1e9:.3f} GB of device memory, {free / 1e9:.3f} GB are free",
-                            details=details,
-                            suggestions=["Pass block_steps='auto'", "Pass block_steps=<timesteps per window>"]
-                            + (["Pass return_mask=False"] if return_mask else []))
-    B = _plan_windows(eng, T, C, per_step, p["block_steps"], "compound_events", details)
-    if p["block_steps"] == "auto" and per_step:
-        B = max(1, min(B, (free - free // 16 - fixed) // per_step))
+    B = _stream._window_steps(eng, "compound_events", T, C, per_step, fixed, p["block_steps"], details,
+                              ["Pass return_mask=False"] if return_mask else [])
     kw = dict(max_lag=L, tolerance=K)
     if p["grp"] is not None:
         kw.update(grp=p["grp"][0], G=G)

@@ -53,7 +53,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
         subprocess.check_call(cmd)
 
     if todo:
-        with ThreadPoolExecutor(max_workers=min(len(todo), os.cpu_count() or 4)) as pool:
+        with ThreadPoolExecutor(max_workers=min(len(todo), os.cpu_count() or 4, int(os.environ.get("MAX_JOBS", 16)))) as pool:
             list(pool.map(compile_one, todo))
     if todo or force or needs_build():
         cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", *[_obj(s) for s in SRC], "-o", OUT]

@@ -27,7 +27,6 @@
 // the int32 planes of the carried state: four always, all ten with anomalies
 enum { CE_RUN, CE_START1, CE_END, CE_CURSOR, CE_EMAX, CE_ETMAX, CE_EINV, CE_TMAX, CE_TTMAX, CE_TINV };
 
-__device__ __forceinline__ bool ce_finite(float v) { return (__float_as_uint(v) & 0x7F800000u) != 0x7F800000u; }
 
 // Rows t0 .. t0 + Tb - 1: x and anom [Tb][C]; mask is the base of the whole [T][C] output.  V: cells per lane (4: C % 4 == 0
 // and x and mask are 4-byte aligned -- the entry point checks, and launches it without anomalies only); ANOM: anom and the
@@ -144,7 +143,7 @@ k_cell_events(const unsigned char* __restrict__ x, const float* __restrict__ ano
                 for (int j = 0; j < V; ++j) {
                     const bool p = cell_value<V>(w[k], j) > 0;
                     const float a = ANOM ? av[k][j] : 0.f;
-                    const bool fin = ANOM && ce_finite(a);
+                    const bool fin = ANOM && finite_bits(a);
                     const unsigned key = ANOM ? ordered_key(a) : 0u;
                     bool to_tail = false;
                     if (p) {

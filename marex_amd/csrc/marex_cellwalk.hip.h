@@ -1,11 +1,10 @@
 #pragma once
-// marex_cellwalk.hip.h -- what the per-cell streaming kernels (marex_occurrence.hip, marex_local_intensity.hip, marex_cell_events.hip) share: a
-// lane owns one cell, or four consecutive uint8 cells through one 32-bit load, for the whole call and walks the rows.
-// The kernels, their unroll depths and what they keep per cell stay in their units (the register
-// budgets differ).
+// marex_cellwalk.hip.h -- what the per-cell streaming kernels (marex_occurrence.hip, marex_local_intensity.hip,
+// marex_cell_events.hip, marex_compound.hip) share: a lane owns one cell, or four consecutive uint8 cells through one 32-bit
+// load, for the whole call and walks the rows.  The kernels, their unroll depths and what they keep per cell stay in their
+// units (the register budgets differ).  The leaf helpers that the event kernels use too -- u64,
+// finite_bits, severity_class, wave_sum, cell_stream_limits -- are in marex_common.hip.h.
 #include "marex_common.hip.h"
-
-typedef unsigned long long u64;
 
 // the word a lane loads per row: T int or unsigned char, V cells per lane
 template <typename T, int V>
@@ -39,13 +38,6 @@ __device__ __forceinline__ void wave_class_partition(int cj, int R, int lane, u6
         }
         todo &= ~same;
     }
-}
-
-// rows and steps are addressed through int: 0 where they fit, else the entry point's failure
-static inline int cell_stream_limits(marex_ctx* ctx, const char* name, int64_t t0, int64_t Tb, int64_t C) {
-    if (C >= 2147483647L || t0 >= 2147483647L || Tb >= 2147483647L || t0 + Tb >= 2147483647L)
-        return fail(ctx, -4, "%s: a row or the time axis has 2^31 - 1 or more entries", name);
-    return 0;
 }
 
 // blocks of 256 lanes with V cells each over a row of C cells

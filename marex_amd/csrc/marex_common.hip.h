@@ -31,6 +31,8 @@
 
 #define NDOY MAREX_NDOY
 
+typedef unsigned long long u64;
+
 // ------------------------------------------------------------------------------------------------
 // context
 // ------------------------------------------------------------------------------------------------
@@ -164,6 +166,46 @@ static inline void drain_timers(marex_ctx* ctx) {
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float nan_f() { return __builtin_nanf(""); }
 __device__ __forceinline__ bool finite_f(float v) { return fabsf(v) <= 3.402823466e+38f; }
+// The same answer on every input (an all-ones exponent is exactly NaN and +-inf) from the bits: what the event and cell
+// statistics were written with; finite_f stays for the anomaly and shifting kernels, whose instructions are pinned.
+__device__ __forceinline__ bool finite_bits(float v) { return (__float_as_uint(v) & 0x7F800000u) != 0x7F800000u; }
+
+// The class of a finite anomaly a under the threshold h: 5 where h is not a positive finite number, else the number of
+// h, 2 h, 3 h, 4 h (float32 products, one rounding each, ascending) that a reaches.
+__device__ __forceinline__ int severity_class(float a, float h) {
+    if (!(h > 0.f) || !finite_bits(h)) return 5;
+    const float h2 = 2.f * h, h3 = 3.f * h, h4 = 4.f * h;
+    return (int)(a >= h) + (int)(a >= h2) + (int)(a >= h3) + (int)(a >= h4);
+}
+
+// index of key v in keys[0 .. n) (ascending, distinct), -1 when absent
+__device__ __forceinline__ int sorted_find(const int* __restrict__ keys, int n, int v) {
+    int lo = 0, hi = n - 1;
+    while (lo <= hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        const int k = keys[mid];
+        if (k == v) return mid;
+        if (k < v) lo = mid + 1; else hi = mid - 1;
+    }
+    return -1;
+}
+
+// splitmix64 finaliser: neighbouring pair keys land far apart in the table
+__device__ __forceinline__ u64 splitmix64(u64 k) {
+    k ^= k >> 30; k *= 0xbf58476d1ce4e5b9ull;
+    k ^= k >> 27; k *= 0x94d049bb133111ebull;
+    return k ^ (k >> 31);
+}
+
+// blocks of 256 threads of a grid-stride loop over n items
+static inline unsigned stride_grid(long n) { return (unsigned)(n < 256L * 8192 ? (n + 255) / 256 : 8192); }
+
+// rows and steps are addressed through int: 0 where they fit, else the entry point's failure
+static inline int cell_stream_limits(marex_ctx* ctx, const char* name, int64_t t0, int64_t Tb, int64_t C) {
+    if (C >= 2147483647L || t0 >= 2147483647L || Tb >= 2147483647L || t0 + Tb >= 2147483647L)
+        return fail(ctx, -4, "%s: a row or the time axis has 2^31 - 1 or more entries", name);
+    return 0;
+}
 
 // Workgroups are dealt round-robin over the 8 XCDs (b % 8).  Map the linear block id so that the
 // `inner` consecutive work items of one `outer` group (which re-read each other's rows) land on the
@@ -264,5 +306,18 @@ __device__ __forceinline__ int wave_min_i32(int m) {
     return m;
 }
 __device__ __forceinline__ int wave_max_i32(int m) { return -wave_min_i32(-m); }
+
+// the sum of v over the 64 lanes of the wave, in every lane (a shuffle butterfly; double, long long or unsigned)
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
+    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// v of lane src, in every lane
+__device__ __forceinline__ u64 wave_shfl_u64(u64 v, int src) {
+    const unsigned lo = __shfl((unsigned)v, src, 64), hi = __shfl((unsigned)(v >> 32), src, 64);
+    return ((u64)hi << 32) | lo;
+}
 
 #define MASK_DOY_CHUNKS 6  // default number of pieces the dayofyear axis is cut into by the doy-grouped streaming kernels

@@ -11,29 +11,12 @@
 // each (compiled with -ffp-contract=off).
 #include "marex_common.hip.h"
 
-typedef unsigned long long u64;
-
 #define CAT_ITERS 16                  // 64-cell pieces per wave
 #define CAT_BATCH 4                   // pieces loaded together (loads in flight per lane); CAT_ITERS is a multiple
 #define CAT_CHUNK (256 * CAT_ITERS)   // cells of a row per workgroup (4 waves)
 #define CAT_TSTRIDE 64                // rows in flight: a workgroup walks every CAT_TSTRIDE-th row
 #define CAT_NCNT 7                    // below, moderate, strong, severe, extreme, undefined, non-finite anomaly
 #define CAT_NAREA 6                   // the classified ones
-
-__device__ __forceinline__ double cat_wave_sum_f64(double v) {
-    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ bool cat_finite(float v) { return (__float_as_uint(v) & 0x7F800000u) != 0x7F800000u; }
-
-// The class of a finite anomaly a under the threshold h: 5 where h is not a positive finite number, else the number of
-// h, 2 h, 3 h, 4 h (float32 products, one rounding each, ascending) that a reaches.
-__device__ __forceinline__ int cat_class(float a, float h) {
-    if (!(h > 0.f) || !cat_finite(h)) return 5;
-    const float h2 = 2.f * h, h3 = 3.f * h, h4 = 4.f * h;
-    return (int)(a >= h) + (int)(a >= h2) + (int)(a >= h3) + (int)(a >= h4);
-}
 
 // Rows t0 .. t0 + Tb - 1 of the field: ids / anom [Tb][C]; a cell of event e = ids[row][c] in 1 .. n_ev at the global step
 // t = t0 + row belongs to the slot s = ev_off[e] + t - ev_tmin[e].  A wave walks CAT_ITERS consecutive 64-cell pieces of a
@@ -125,7 +108,7 @@ k_evt_categories(const int* __restrict__ ids, const float* __restrict__ anom, lo
 #pragma unroll
             for (int k = 0; k < CAT_BATCH; ++k) {
                 const long r = rw + 64 * (b + k) + lane;
-                const bool fin = ev[k] > 0 && cat_finite(av[k]);
+                const bool fin = ev[k] > 0 && finite_bits(av[k]);
                 hv[k] = fin ? hrow[r] : 0.f;
                 wv[k] = (WEIGHTED && fin) ? w[r] : 0.f;
                 cl[k] = fin ? 0 : 6;
@@ -136,7 +119,7 @@ k_evt_categories(const int* __restrict__ ids, const float* __restrict__ anom, lo
                 u64 todo = __ballot(e > 0);
                 unsigned char fv = 0;
                 if (todo) {
-                    const int c = cl[k] ? 6 : cat_class(av[k], hv[k]);
+                    const int c = cl[k] ? 6 : severity_class(av[k], hv[k]);
                     while (todo) {
                         const int lead = __ffsll((long long)todo) - 1;
                         const int el = __shfl(e, lead, 64);
@@ -160,7 +143,7 @@ k_evt_categories(const int* __restrict__ ids, const float* __restrict__ anom, lo
                             const u64 bq = __ballot(me && c == q);
                             if (!bq) continue;  // wave-uniform
                             n[q] += (unsigned)__popcll(bq);
-                            if (WEIGHTED && q < CAT_NAREA) ar[q] += cat_wave_sum_f64((me && c == q) ? (double)wv[k] : 0.0);
+                            if (WEIGHTED && q < CAT_NAREA) ar[q] += wave_sum((me && c == q) ? (double)wv[k] : 0.0);
                         }
                         if (FIELD && me) fv = slot >= 0 ? (unsigned char)(c + 1) : (unsigned char)0;
                     }
@@ -184,8 +167,7 @@ extern "C" int marex_event_categories_f32(marex_ctx* ctx, const int32_t* ids, co
         return fail(ctx, -1, "marex_event_categories_f32: null pointer, empty shape, no event or no slot");
     if (!thr || !doy || n_doy <= 0 || (w == nullptr) != (cat_area == nullptr))
         return fail(ctx, -1, "marex_event_categories_f32: thr or doy missing, n_doy <= 0, or w and cat_area given in part");
-    if (C >= 2147483647L || t0 >= 2147483647L || Tb >= 2147483647L || t0 + Tb >= 2147483647L)
-        return fail(ctx, -4, "marex_event_categories_f32: a row or the time axis has 2^31 - 1 or more entries");
+    if (const int rc = cell_stream_limits(ctx, "marex_event_categories_f32", t0, Tb, C)) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     LaunchTimer lt(ctx, MAREX_K_MORPH);
     const dim3 grid((unsigned)((C + CAT_CHUNK - 1) / CAT_CHUNK), (unsigned)(Tb < CAT_TSTRIDE ? Tb : CAT_TSTRIDE));

@@ -10,17 +10,10 @@
 // marex_event_rename_i32), not the integer contract of the mesh areas.
 #include "marex_common.hip.h"
 
-typedef unsigned long long u64;
-
 #define INT_ITERS 16                  // 64-cell pieces per wave
 #define INT_BATCH 4                   // pieces loaded together (loads in flight per lane); INT_ITERS is a multiple
 #define INT_CHUNK (256 * INT_ITERS)   // cells of a row per workgroup (4 waves)
 #define INT_TSTRIDE 64                // rows in flight: a workgroup walks every INT_TSTRIDE-th row
-
-__device__ __forceinline__ double int_wave_sum_f64(double v) {
-    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 __device__ __forceinline__ unsigned int_wave_max_u32(unsigned v) {
     for (int o = 32; o; o >>= 1) {
@@ -94,6 +87,7 @@ k_evt_intensity(const int* __restrict__ ids, const float* __restrict__ anom, lon
                 u64 todo = __ballot(e > 0);
                 if (!todo) continue;
                 const float a = av[k];
+                // finite_bits(a), written out: behind the function the compiler picks a class test here, other instructions
                 const bool fin = (__float_as_uint(a) & 0x7F800000u) != 0x7F800000u;  // neither NaN nor +-inf
                 while (todo) {
                     const int lead = __ffsll((long long)todo) - 1;
@@ -107,8 +101,8 @@ k_evt_intensity(const int* __restrict__ ids, const float* __restrict__ anom, lon
                     unsigned gk = 0;
                     if (good) {  // wave-uniform
                         const double x = me ? (double)wv[k] : 0.0;
-                        if (WEIGHTED) gw = int_wave_sum_f64(x);
-                        gwa = int_wave_sum_f64(me ? x * (double)a : 0.0);
+                        if (WEIGHTED) gw = wave_sum(x);
+                        gwa = wave_sum(me ? x * (double)a : 0.0);
                         gk = int_wave_max_u32(me ? ordered_key(a) : 0u);
                     }
                     if (el != cur) {
@@ -137,8 +131,7 @@ extern "C" int marex_event_intensity_f32(marex_ctx* ctx, const int32_t* ids, con
     if (!ids || !anom || !ev_tmin || !ev_off || !cnt || !sums || !vmax || !status || t0 < 0 || Tb <= 0 || C <= 0 || n_ev <= 0 ||
         n_slots <= 0)
         return fail(ctx, -1, "marex_event_intensity_f32: null pointer, empty shape, no event or no slot");
-    if (C >= 2147483647L || t0 >= 2147483647L || Tb >= 2147483647L || t0 + Tb >= 2147483647L)
-        return fail(ctx, -4, "marex_event_intensity_f32: a row or the time axis has 2^31 - 1 or more entries");
+    if (const int rc = cell_stream_limits(ctx, "marex_event_intensity_f32", t0, Tb, C)) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     LaunchTimer lt(ctx, MAREX_K_MORPH);
     const dim3 grid((unsigned)((C + INT_CHUNK - 1) / INT_CHUNK), (unsigned)(Tb < INT_TSTRIDE ? Tb : INT_TSTRIDE));

@@ -22,17 +22,7 @@
 #ifndef LI_U4
 #define LI_U4 4
 #endif
-#define LI_NCAT 6  // below, moderate, strong, severe, extreme, undefined
-
-__device__ __forceinline__ bool li_finite(float v) { return (__float_as_uint(v) & 0x7F800000u) != 0x7F800000u; }
-
-// The class of a finite anomaly a under the threshold h: 5 where h is not a positive finite number, else the number of
-// h, 2 h, 3 h, 4 h (float32 products, one rounding each, ascending) that a reaches.
-__device__ __forceinline__ int li_class(float a, float h) {
-    if (!(h > 0.f) || !li_finite(h)) return 5;
-    const float h2 = 2.f * h, h3 = 3.f * h, h4 = 4.f * h;
-    return (int)(a >= h) + (int)(a >= h2) + (int)(a >= h3) + (int)(a >= h4);
-}
+#define LI_NCAT 6  // below, moderate, strong, severe, extreme, undefined (severity_class)
 
 // Rows t0 .. t0 + Tb - 1: x and anom [Tb][C].  V: cells per lane (4: C % 4 == 0 and x is 4-byte aligned -- the entry point
 // checks); CATS: thr, doy and cat_days are given; SECT (only with CATS): sec_cnt, sgrp and cls are given.  Lanes past the
@@ -172,7 +162,7 @@ k_local_intensity(const T* __restrict__ x, const float* __restrict__ anom, long 
                         continue;
                     }
                     const float a = av[k][j];
-                    const bool ok = p && li_finite(a);
+                    const bool ok = p && finite_bits(a);
                     dirty[j] = dirty[j] || p;
                     nd[j] += ok;
                     ni[j] += p && !ok;
@@ -185,7 +175,7 @@ k_local_intensity(const T* __restrict__ x, const float* __restrict__ anom, long 
                         }
                     }
                     if (CATS) {
-                        const int c = ok ? li_class(a, hv[k][j]) : -1;
+                        const int c = ok ? severity_class(a, hv[k][j]) : -1;
 #pragma unroll
                         for (int q = 0; q < NC; ++q) {
                             cat[j][q] += c == q;

@@ -9,22 +9,8 @@
 // is kept by scanning parents in order with a strict comparison.
 #include "marex_common.hip.h"
 
-typedef unsigned long long u64;
-
 #define MRG_NMOM 5  // int64 per event slot: cell count, sum y, sum x, sum of x with x > nx / 2 shifted by -nx, near-edge flags
 #define MRG_NWMOM 4 // float64 per event slot (weighted): area, sum a y, sum a x, sum a x_shifted
-
-// index of key v in keys[0 .. n) (ascending, distinct), -1 when absent
-__device__ __forceinline__ int mrg_find(const int* __restrict__ keys, int n, int v) {
-    int lo = 0, hi = n - 1;
-    while (lo <= hi) {
-        const int mid = lo + ((hi - lo) >> 1);
-        const int k = keys[mid];
-        if (k == v) return mid;
-        if (k < v) lo = mid + 1; else hi = mid - 1;
-    }
-    return -1;
-}
 
 // the x offset of a child cell to a parent point, wrapped by +-nx when |dx| > nx / 2 (wrapped_euclidian_distance_*)
 __device__ __forceinline__ double mrg_dist(double dy, double dx, double nx, bool wrap) {
@@ -43,7 +29,7 @@ k_mrg_relabel(int* __restrict__ ids, long n, const int* __restrict__ keys, const
         const int v = ids[i];
         if (v <= 0) continue;
         if (keys) {
-            const int j = mrg_find(keys, n_keys, v);
+            const int j = sorted_find(keys, n_keys, v);
             if (j >= 0) ids[i] = vals[j];
         } else if (v < n_keys) {
             ids[i] = vals[v];
@@ -62,7 +48,7 @@ k_mrg_part_centroid(int* __restrict__ ids, int ny, int nx, const int* __restrict
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < C; i += (long)gridDim.x * 256) {
         const int v = ids[i];
         if (v <= 0) continue;
-        const int k = mrg_find(child_keys, n_child, v);
+        const int k = sorted_find(child_keys, n_child, v);
         if (k < 0) continue;
         const double y = (double)(i / nx), x = (double)(i % nx);
         int best = off[k];
@@ -93,7 +79,7 @@ k_mrg_nn_buckets(const int* __restrict__ prev, int ny, int nx, const int* __rest
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < C; i += (long)gridDim.x * 256) {
         const int v = prev[i];
         if (v <= 0) continue;
-        const int q = mrg_find(par_keys, n_par, v);
+        const int q = sorted_find(par_keys, n_par, v);
         if (q < 0) continue;
         const int y = (int)(i / nx), x = (int)(i % nx);
         for (int e = poff[q]; e < poff[q + 1]; ++e) {
@@ -149,7 +135,7 @@ k_mrg_part_nn(int* __restrict__ ids, int ny, int nx, const int* __restrict__ chi
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < C; i += (long)gridDim.x * 256) {
         const int v = ids[i];
         if (v <= 0) continue;
-        const int k = mrg_find(child_keys, n_child, v);
+        const int k = sorted_find(child_keys, n_child, v);
         if (k < 0) continue;
         const int y = (int)(i / nx), x = (int)(i % nx);
         const double inf = __builtin_huge_val();
@@ -189,16 +175,6 @@ k_mrg_part_nn(int* __restrict__ ids, int ny, int nx, const int* __restrict__ chi
         }
         ids[i] = lab[best];
     }
-}
-
-__device__ __forceinline__ long long mrg_wave_sum_i64(long long v) {
-    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ double mrg_wave_sum_f64(double v) {
-    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 __device__ __forceinline__ int mrg_wave_max_i32(int v) {
@@ -241,17 +217,17 @@ k_mrg_event_moments(const int* __restrict__ ev, const int* __restrict__ orig, lo
                 todo &= ~same;
                 const bool me = (same >> lane) & 1ull;
                 const long long n = __popcll(same);
-                const long long sy = mrg_wave_sum_i64(me ? y : 0), sx = mrg_wave_sum_i64(me ? x : 0),
-                                sxs = mrg_wave_sum_i64(me ? xs : 0);
+                const long long sy = wave_sum<long long>(me ? y : 0), sx = wave_sum<long long>(me ? x : 0),
+                                sxs = wave_sum<long long>(me ? xs : 0);
                 const u64 bl = __ballot(me && (fl & 1u)), br = __ballot(me && (fl & 2u));
                 const int om = mrg_wave_max_i32(me ? o : 0);
                 double wa = 0, wy = 0, wx = 0, wxs = 0;
                 if (w) {
                     const double a = me ? (double)wc : 0.0;
-                    wa = mrg_wave_sum_f64(a);
-                    wy = mrg_wave_sum_f64(a * (double)y);
-                    wx = mrg_wave_sum_f64(a * (double)x);
-                    wxs = mrg_wave_sum_f64(a * (double)xs);
+                    wa = wave_sum(a);
+                    wy = wave_sum(a * (double)y);
+                    wx = wave_sum(a * (double)x);
+                    wxs = wave_sum(a * (double)xs);
                 }
                 if (lane == 0) {
                     const size_t s = (size_t)t * n_ev + (el - 1);
@@ -362,17 +338,17 @@ k_mrg_event_rename(int* ids, long T, int ny, int nx, const int* __restrict__ lut
                     const u64 same = __ballot(e == el) & todo;
                     todo &= ~same;
                     const bool me = (same >> lane) & 1ull;
-                    const long long gy = mrg_wave_sum_i64(me ? y : 0), gx = mrg_wave_sum_i64(me ? x : 0),
-                                    gxs = mrg_wave_sum_i64(me ? xs : 0);
+                    const long long gy = wave_sum<long long>(me ? y : 0), gx = wave_sum<long long>(me ? x : 0),
+                                    gxs = wave_sum<long long>(me ? xs : 0);
                     const u64 bl = __ballot(me && (fl & 1u)), br = __ballot(me && (fl & 2u));
                     const int gm = mrg_wave_max_i32(me ? v[k] : 0);  // v > 0 wherever e > 0
                     double ga = 0, gwy = 0, gwx = 0, gwxs = 0;
                     if (WEIGHTED) {
                         const double a = me ? (double)wc : 0.0;
-                        ga = mrg_wave_sum_f64(a);
-                        gwy = mrg_wave_sum_f64(a * (double)y);
-                        gwx = mrg_wave_sum_f64(a * (double)x);
-                        gwxs = mrg_wave_sum_f64(a * (double)xs);
+                        ga = wave_sum(a);
+                        gwy = wave_sum(a * (double)y);
+                        gwx = wave_sum(a * (double)x);
+                        gwxs = wave_sum(a * (double)xs);
                     }
                     if (el != cur) {
                         flush();
@@ -401,7 +377,6 @@ k_mrg_event_rename(int* ids, long T, int ny, int nx, const int* __restrict__ lut
     }
 }
 
-static inline unsigned mrg_grid(long n) { return (unsigned)(n < 256L * 8192 ? (n + 255) / 256 : 8192); }
 
 extern "C" int marex_relabel_i32(marex_ctx* ctx, int32_t* ids, int64_t n, const int32_t* keys, const int32_t* vals,
                                  int n_keys) {
@@ -409,7 +384,7 @@ extern "C" int marex_relabel_i32(marex_ctx* ctx, int32_t* ids, int64_t n, const 
     if (!ids || !vals || n <= 0 || n_keys <= 0) return fail(ctx, -1, "marex_relabel_i32: null pointer or empty table");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     LaunchTimer lt(ctx, MAREX_K_MORPH);
-    hipLaunchKernelGGL(k_mrg_relabel, dim3(mrg_grid(n)), dim3(256), 0, ctx->stream, ids, (long)n, keys, vals, n_keys);
+    hipLaunchKernelGGL(k_mrg_relabel, dim3(stride_grid(n)), dim3(256), 0, ctx->stream, ids, (long)n, keys, vals, n_keys);
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }
@@ -423,7 +398,7 @@ extern "C" int marex_partition_centroid_i32(marex_ctx* ctx, int32_t* ids, int ny
     if ((long)ny * nx >= 2147483647L) return fail(ctx, -4, "marex_partition_centroid_i32: a slice has 2^31 - 1 or more cells");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     LaunchTimer lt(ctx, MAREX_K_MORPH);
-    hipLaunchKernelGGL(k_mrg_part_centroid, dim3(mrg_grid((long)ny * nx)), dim3(256), 0, ctx->stream, ids, ny, nx, child_keys,
+    hipLaunchKernelGGL(k_mrg_part_centroid, dim3(stride_grid((long)ny * nx)), dim3(256), 0, ctx->stream, ids, ny, nx, child_keys,
                        n_child, off, pcy, pcx, lab, wrap);
     HIP_TRY(ctx, hipGetLastError());
     return 0;
@@ -441,7 +416,7 @@ extern "C" int marex_nn_bucket_count_i32(marex_ctx* ctx, const int32_t* prev, in
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     LaunchTimer lt(ctx, MAREX_K_MORPH);
     HIP_TRY(ctx, hipMemsetAsync(cnt, 0, (size_t)n_buckets * sizeof(int64_t), ctx->stream));
-    hipLaunchKernelGGL(k_mrg_nn_buckets<false>, dim3(mrg_grid((long)ny * nx)), dim3(256), 0, ctx->stream, prev, ny, nx, par_keys,
+    hipLaunchKernelGGL(k_mrg_nn_buckets<false>, dim3(stride_grid((long)ny * nx)), dim3(256), 0, ctx->stream, prev, ny, nx, par_keys,
                        n_par, poff, pent, gs, ngy, ngx, (const long long*)base, (long long*)cnt, (int*)nullptr, 0LL);
     hipLaunchKernelGGL(k_mrg_scan, dim3(1), dim3(1024), 0, ctx->stream, (const long long*)cnt, (long)n_buckets, (long long*)bstart);
     HIP_TRY(ctx, hipGetLastError());
@@ -463,7 +438,7 @@ extern "C" int marex_partition_nn_i32(marex_ctx* ctx, int32_t* ids, const int32_
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     LaunchTimer lt(ctx, MAREX_K_MORPH);
     HIP_TRY(ctx, hipMemcpyAsync(cursor, bstart, (size_t)n_buckets * sizeof(int64_t), hipMemcpyDeviceToDevice, ctx->stream));
-    const unsigned g = mrg_grid((long)ny * nx);
+    const unsigned g = stride_grid((long)ny * nx);
     hipLaunchKernelGGL(k_mrg_nn_buckets<true>, dim3(g), dim3(256), 0, ctx->stream, prev, ny, nx, par_keys, n_par, poff, pent, gs,
                        ngy, ngx, (const long long*)base, (long long*)cursor, cells, (long long)n_cells);
     hipLaunchKernelGGL(k_mrg_part_nn, dim3(g), dim3(256), 0, ctx->stream, ids, ny, nx, child_keys, n_child, off, pcy, pcx, lab,

@@ -30,20 +30,6 @@
 #define MMRG_CTL_REASON 5     // 1: no child cell unclaimed, 2: a hop claimed no child cell, 3: the hop cap
 #define MMRG_CTL_WORDS 8
 
-static inline unsigned mmrg_grid(long n) { return (unsigned)(n < 256L * 8192 ? (n + 255) / 256 : 8192); }
-
-// index of key v in keys[0 .. n) (ascending, distinct), -1 when absent
-__device__ __forceinline__ int mmrg_find(const int* __restrict__ keys, int n, int v) {
-    int lo = 0, hi = n - 1;
-    while (lo <= hi) {
-        const int mid = lo + ((hi - lo) >> 1);
-        const int k = keys[mid];
-        if (k == v) return mid;
-        if (k < v) lo = mid + 1; else hi = mid - 1;
-    }
-    return -1;
-}
-
 // the entry j in [j0, j1) whose vector pv[.][j] is nearest to the unit vector of cell c (first minimum)
 __device__ __forceinline__ int mmrg_nearest(const double* __restrict__ u, long C, long c, const double* __restrict__ pv, int n_ent,
                                             int j0, int j1) {
@@ -70,7 +56,7 @@ k_mmrg_part_centroid(int* __restrict__ ids, long C, const int* __restrict__ chil
     for (long c = (long)blockIdx.x * 256 + threadIdx.x; c < C; c += (long)gridDim.x * 256) {
         const int v = ids[c];
         if (v <= 0) continue;
-        const int k = mmrg_find(child_keys, n_child, v);
+        const int k = sorted_find(child_keys, n_child, v);
         if (k < 0) continue;
         const int j0 = off[k], j1 = off[k + 1];
         if (j0 < 0 || j1 > n_ent || j0 >= j1) continue;
@@ -166,7 +152,7 @@ extern "C" int marex_mesh_partition_centroid_i32(marex_ctx* ctx, int32_t* ids, i
     if (C >= 2147483647L) return fail(ctx, -4, "marex_mesh_partition_centroid_i32: a slice has 2^31 - 1 or more cells");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     LaunchTimer lt(ctx, MAREX_K_MORPH);
-    hipLaunchKernelGGL(k_mmrg_part_centroid, dim3(mmrg_grid(C)), dim3(256), 0, ctx->stream, ids, (long)C, child_keys, n_child, off, u,
+    hipLaunchKernelGGL(k_mmrg_part_centroid, dim3(stride_grid(C)), dim3(256), 0, ctx->stream, ids, (long)C, child_keys, n_child, off, u,
                        pv, n_ent, lab);
     HIP_TRY(ctx, hipGetLastError());
     return 0;
@@ -182,7 +168,7 @@ extern "C" int marex_mesh_nn_seed_i32(marex_ctx* ctx, const int32_t* cur, const 
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     LaunchTimer lt(ctx, MAREX_K_MORPH);
     HIP_TRY(ctx, hipMemsetAsync(ctl, 0, MMRG_CTL_WORDS * sizeof(int), ctx->stream));
-    hipLaunchKernelGGL(k_mmrg_nn_seed, dim3(mmrg_grid(C)), dim3(256), 0, ctx->stream, cur, prev, (long)C, child, parents, n_par,
+    hipLaunchKernelGGL(k_mmrg_nn_seed, dim3(stride_grid(C)), dim3(256), 0, ctx->stream, cur, prev, (long)C, child, parents, n_par,
                        (unsigned*)word, ctl);
     HIP_TRY(ctx, hipGetLastError());
     return 0;
@@ -201,7 +187,7 @@ extern "C" int marex_mesh_nn_hops_i32(marex_ctx* ctx, const int32_t* cur, const 
                     first_hop, n_hops, max_hops, n_par);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     LaunchTimer lt(ctx, MAREX_K_MORPH);
-    const dim3 grid(mmrg_grid(C));
+    const dim3 grid(stride_grid(C));
     for (int h = first_hop; h < first_hop + n_hops; ++h) {
         hipLaunchKernelGGL(k_mmrg_nn_gate, dim3(1), dim3(64), 0, ctx->stream, ctl, max_hops);
         for (int p = 0; p < n_par; ++p)
@@ -223,7 +209,7 @@ extern "C" int marex_mesh_nn_finish_i32(marex_ctx* ctx, int32_t* cur, int64_t C,
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     LaunchTimer lt(ctx, MAREX_K_MORPH);
     hipLaunchKernelGGL(k_mmrg_nn_gate, dim3(1), dim3(64), 0, ctx->stream, ctl, max_hops);  // names the reason of the stop
-    hipLaunchKernelGGL(k_mmrg_nn_finish, dim3(mmrg_grid(C)), dim3(256), 0, ctx->stream, cur, (long)C, child, u, pv, n_par, lab,
+    hipLaunchKernelGGL(k_mmrg_nn_finish, dim3(stride_grid(C)), dim3(256), 0, ctx->stream, cur, (long)C, child, u, pv, n_par, lab,
                        (const unsigned*)word, ctl);
     HIP_TRY(ctx, hipGetLastError());
     return 0;

@@ -13,8 +13,6 @@
 // wave chunk, not one per cell.  q is read only by lanes that hold an ID.
 #include "marex_common.hip.h"
 
-typedef unsigned long long u64;
-
 #define MOBJ_ITERS 16                     // 64-cell pieces per wave
 #define MOBJ_CHUNK (256 * MOBJ_ITERS)     // cells of a slice per workgroup (4 waves)
 #define MOBJ_MOM 5                        // u64 per slot: cells, sum q0 (area), sum q1, q2, q3 (area * x, y, z)
@@ -31,25 +29,11 @@ __device__ __forceinline__ long long mobj_wave_sum_i64(long long v) {
     return v;
 }
 
-__device__ __forceinline__ u64 mobj_shfl_u64(u64 v, int src) {
-    const unsigned lo = __shfl((unsigned)v, src, 64), hi = __shfl((unsigned)(v >> 32), src, 64);
-    return ((u64)hi << 32) | lo;
-}
-
-// splitmix64 finaliser: neighbouring pair keys land far apart in the table
-__device__ __forceinline__ u64 mobj_mix(u64 k) {
-    k ^= k >> 30; k *= 0xbf58476d1ce4e5b9ull;
-    k ^= k >> 27; k *= 0x94d049bb133111ebull;
-    return k ^ (k >> 31);
-}
-
 __device__ __forceinline__ long mobj_piece0(int wave) { return (long)blockIdx.x * MOBJ_CHUNK + (long)wave * (64 * MOBJ_ITERS); }
 
 static inline dim3 mobj_slice_grid(long T, long C) {
     return dim3((unsigned)((C + MOBJ_CHUNK - 1) / MOBJ_CHUNK), (unsigned)(T < MOBJ_TSTRIDE ? T : MOBJ_TSTRIDE));
 }
-
-static inline unsigned mobj_stride_grid(long n) { return (unsigned)(n < 256L * 8192 ? (n + 255) / 256 : 8192); }
 
 // ------------------------------------------------------------------------------------------------ per-timestep IDs
 // One workgroup per slice: rank[t C + c] = 1 + the number of root cells of slice t below c, for every root cell c
@@ -110,7 +94,7 @@ extern "C" int marex_label_mesh_rank_i32(marex_ctx* ctx, const int32_t* labels, 
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     LaunchTimer lt(ctx, MAREX_K_MORPH);
     hipLaunchKernelGGL(k_mesh_rank_roots, dim3((unsigned)T), dim3(RANK_THREADS), 0, ctx->stream, labels, (long)C, rank, n_t);
-    hipLaunchKernelGGL(k_mesh_rank_gather, dim3(mobj_stride_grid(n)), dim3(256), 0, ctx->stream, labels, n, (const int*)rank, ids);
+    hipLaunchKernelGGL(k_mesh_rank_gather, dim3(stride_grid(n)), dim3(256), 0, ctx->stream, labels, n, (const int*)rank, ids);
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }
@@ -365,7 +349,7 @@ k_mesh_ovl_insert(const int* __restrict__ ids, long T, long C, const long long* 
     auto flush = [&]() {
         if (!cur || lane != 0) return;
         const u64 mask = (u64)cap - 1;
-        u64 h = mobj_mix(cur) & mask;
+        u64 h = splitmix64(cur) & mask;
         for (long p = 0; p < cap; ++p) {
             const u64 prev = atomicCAS(&keys[h], 0ull, cur);
             if (prev == 0ull || prev == cur) {
@@ -395,7 +379,7 @@ k_mesh_ovl_insert(const int* __restrict__ ids, long T, long C, const long long* 
             const long long w = key ? q0[rw + 64 * k + lane] : 0;  // key != 0 implies the cell is inside the slice
             while (todo) {
                 const int lead = __ffsll((long long)todo) - 1;
-                const u64 kl = mobj_shfl_u64(key, lead);
+                const u64 kl = wave_shfl_u64(key, lead);
                 const u64 same = __ballot(key == kl) & todo;
                 todo &= ~same;
                 const u64 g = (u64)mobj_wave_sum_i64(((same >> lane) & 1ull) ? w : 0);  // one slice: below 2^62
@@ -443,7 +427,7 @@ extern "C" int marex_mesh_overlap_pairs_i64(marex_ctx* ctx, const int32_t* ids, 
     HIP_TRY(ctx, hipMemsetAsync(stats + 2, 0, 2 * sizeof(u64), ctx->stream));
     hipLaunchKernelGGL(k_mesh_ovl_insert, mobj_slice_grid(T - 1, C), dim3(256), 0, ctx->stream, ids, (long)T, (long)C,
                        (const long long*)q0, (long)cap, (u64*)keys, (u64*)sums, (u64*)stats);
-    hipLaunchKernelGGL(k_mesh_ovl_compact, dim3(mobj_stride_grid(cap)), dim3(256), 0, ctx->stream, (long)cap, (const u64*)keys,
+    hipLaunchKernelGGL(k_mesh_ovl_compact, dim3(stride_grid(cap)), dim3(256), 0, ctx->stream, (long)cap, (const u64*)keys,
                        (const u64*)sums, (long)out_cap, (u64*)stats, (u64*)out_keys, (u64*)out_sums);
     HIP_TRY(ctx, hipGetLastError());
     return 0;

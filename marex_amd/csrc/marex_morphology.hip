@@ -9,8 +9,6 @@
 // inherits through dask_image, so the contamination that creeps 4R cells in from the padded border is reproduced too.
 #include "marex_common.hip.h"
 
-typedef unsigned long long u64;
-
 // padded packed layout: [T][Hp = ny + 4R][Wp = ceil((nx + 4R) / 64)] words; bit i of word w = cell x = 64 w + i of the
 // padded row; bits past the row end are kept 0.
 // one workgroup per padded row: the source row is resolved once (uniform), a wave packs 64 cells per ballot

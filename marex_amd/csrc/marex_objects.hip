@@ -10,36 +10,12 @@
 // destination does not depend on the slice).
 #include "marex_common.hip.h"
 
-typedef unsigned long long u64;
-
 #define OBJ_ITERS 16                     // 64-cell pieces per wave
 #define OBJ_CHUNK (256 * OBJ_ITERS)      // cells of a slice per workgroup (4 waves)
 #define OBJ_TILE 4096                    // IDs per tile of the span scan (16 per thread)
 #define OBJ_MOM 5                        // u64 per slot: count, sum y, sum x, cells with x > nx / 2, near-edge flags
 
 __device__ __forceinline__ int obj_wave_max_i32(int m) { return ~wave_min_i32(~m); }  // ~ reverses the order, never overflows
-
-__device__ __forceinline__ unsigned obj_wave_sum_u32(unsigned v) {
-    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ long long obj_wave_sum_i64(long long v) {
-    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ u64 obj_shfl_u64(u64 v, int src) {
-    const unsigned lo = __shfl((unsigned)v, src, 64), hi = __shfl((unsigned)(v >> 32), src, 64);
-    return ((u64)hi << 32) | lo;
-}
-
-// splitmix64 finaliser: neighbouring pair keys land far apart in the table
-__device__ __forceinline__ u64 obj_mix(u64 k) {
-    k ^= k >> 30; k *= 0xbf58476d1ce4e5b9ull;
-    k ^= k >> 27; k *= 0x94d049bb133111ebull;
-    return k ^ (k >> 31);
-}
 
 __global__ void __launch_bounds__(256) k_obj_fill_i32(int* __restrict__ p, long n, int v) {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) p[i] = v;
@@ -115,7 +91,7 @@ __device__ __forceinline__ long long obj_span(const int* tmin, const int* tmax, 
 // block sum of a per-thread int64 (256 threads), returned to every thread
 __device__ __forceinline__ long long obj_block_sum_i64(long long s) {
     __shared__ long long part[4];
-    s = obj_wave_sum_i64(s);
+    s = wave_sum(s);
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
     __syncthreads();
     const long long tot = part[0] + part[1] + part[2] + part[3];
@@ -237,7 +213,7 @@ k_obj_moments(const int* __restrict__ ids, long T, int ny, int nx, const int* __
                 const int il = __shfl(id, lead, 64);
                 const u64 same = __ballot(id == il) & todo;
                 todo &= ~same;
-                const unsigned s = obj_wave_sum_u32(((same >> lane) & 1ull) ? packed : 0u);
+                const unsigned s = wave_sum(((same >> lane) & 1ull) ? packed : 0u);
                 const long long c = __popcll(same), sl = s & 0xFFFFu, sdy = s >> 16;
                 if (il != cur) {
                     flush();
@@ -295,7 +271,7 @@ k_ovl_pass(const int* __restrict__ ids, long T, long C, long cap, u64* __restric
         ++runs;
         if (INSERT && lane == 0) {
             const u64 mask = (u64)cap - 1;
-            u64 h = obj_mix(cur) & mask;
+            u64 h = splitmix64(cur) & mask;
             for (long p = 0; p < cap; ++p) {
                 const u64 prev = atomicCAS(&keys[h], 0ull, cur);
                 if (prev == 0ull || prev == cur) {
@@ -324,7 +300,7 @@ k_ovl_pass(const int* __restrict__ ids, long T, long C, long cap, u64* __restric
             cells += __popcll(todo);
             while (todo) {
                 const int lead = __ffsll((long long)todo) - 1;
-                const u64 kl = obj_shfl_u64(key, lead);
+                const u64 kl = wave_shfl_u64(key, lead);
                 const u64 same = __ballot(key == kl) & todo;
                 todo &= ~same;
                 if (kl != cur) {
@@ -367,8 +343,6 @@ k_ovl_compact(long cap, const u64* __restrict__ keys, const u64* __restrict__ cn
     }
 }
 
-static inline unsigned obj_stride_grid(long n) { return (unsigned)(n < 256L * 8192 ? (n + 255) / 256 : 8192); }
-
 // (pieces of a slice) x (up to OBJ_TSTRIDE slices; a workgroup walks every OBJ_TSTRIDE-th slice): few enough
 // workgroups that the runs carried across slices and the per-workgroup counters keep same-address atomics rare, and
 // OBJ_TSTRIDE slices in flight at once spread what remains over as many addresses
@@ -384,7 +358,7 @@ extern "C" int marex_ids_minmax_i32(marex_ctx* ctx, const int32_t* ids, int64_t 
     LaunchTimer lt(ctx, MAREX_K_MORPH);
     hipLaunchKernelGGL(k_obj_fill_i32, dim3(1), dim3(256), 0, ctx->stream, minmax, 1L, 2147483647);
     hipLaunchKernelGGL(k_obj_fill_i32, dim3(1), dim3(256), 0, ctx->stream, minmax + 1, 1L, -2147483647 - 1);
-    hipLaunchKernelGGL(k_obj_minmax, dim3(obj_stride_grid(n)), dim3(256), 0, ctx->stream, ids, (long)n, minmax);
+    hipLaunchKernelGGL(k_obj_minmax, dim3(stride_grid(n)), dim3(256), 0, ctx->stream, ids, (long)n, minmax);
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }
@@ -400,8 +374,8 @@ extern "C" int marex_object_spans_i32(marex_ctx* ctx, const int32_t* ids, int64_
     const long nid = (long)max_id + 1, ntiles = (nid + OBJ_TILE - 1) / OBJ_TILE;
     long long* tile_sum = reinterpret_cast<long long*>(work);
     long long* tile_off = tile_sum + ntiles;
-    hipLaunchKernelGGL(k_obj_fill_i32, dim3(obj_stride_grid(nid)), dim3(256), 0, ctx->stream, tmin, nid, 2147483647);
-    hipLaunchKernelGGL(k_obj_fill_i32, dim3(obj_stride_grid(nid)), dim3(256), 0, ctx->stream, tmax, nid, -1);
+    hipLaunchKernelGGL(k_obj_fill_i32, dim3(stride_grid(nid)), dim3(256), 0, ctx->stream, tmin, nid, 2147483647);
+    hipLaunchKernelGGL(k_obj_fill_i32, dim3(stride_grid(nid)), dim3(256), 0, ctx->stream, tmax, nid, -1);
     hipLaunchKernelGGL(k_obj_spans, obj_slice_grid(T, C), dim3(256), 0, ctx->stream, ids, (long)T, (long)C, tmin, tmax);
     hipLaunchKernelGGL(k_obj_span_tiles, dim3((unsigned)ntiles), dim3(256), 0, ctx->stream, tmin, tmax, nid, tile_sum);
     hipLaunchKernelGGL(k_obj_scan_tiles, dim3(1), dim3(1024), 0, ctx->stream, tile_sum, ntiles, tile_off, (long long*)total);
@@ -435,7 +409,7 @@ extern "C" int marex_object_compact(marex_ctx* ctx, int64_t n_slots, int max_id,
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     LaunchTimer lt(ctx, MAREX_K_MORPH);
     HIP_TRY(ctx, hipMemsetAsync(n_out, 0, sizeof(u64), ctx->stream));
-    hipLaunchKernelGGL(k_obj_compact, dim3(obj_stride_grid(n_slots)), dim3(256), 0, ctx->stream, (long)n_slots, (long)max_id + 1,
+    hipLaunchKernelGGL(k_obj_compact, dim3(stride_grid(n_slots)), dim3(256), 0, ctx->stream, (long)n_slots, (long)max_id + 1,
                        tmin, (const long long*)off, (const u64*)acc, (u64*)n_out, out_tid, (u64*)out_mom);
     HIP_TRY(ctx, hipGetLastError());
     return 0;
@@ -470,7 +444,7 @@ extern "C" int marex_overlap_pairs_i32(marex_ctx* ctx, const int32_t* ids, int64
     HIP_TRY(ctx, hipMemsetAsync(stats + 2, 0, 2 * sizeof(u64), ctx->stream));
     hipLaunchKernelGGL(k_ovl_pass<true>, obj_slice_grid(T - 1, C), dim3(256), 0, ctx->stream, ids, (long)T, (long)C, (long)cap,
                        (u64*)keys, (u64*)counts, (u64*)stats);
-    hipLaunchKernelGGL(k_ovl_compact, dim3(obj_stride_grid(cap)), dim3(256), 0, ctx->stream, (long)cap, (const u64*)keys,
+    hipLaunchKernelGGL(k_ovl_compact, dim3(stride_grid(cap)), dim3(256), 0, ctx->stream, (long)cap, (const u64*)keys,
                        (const u64*)counts, (long)out_cap, (u64*)stats, (u64*)out_keys, (u64*)out_counts);
     HIP_TRY(ctx, hipGetLastError());
     return 0;

@@ -39,8 +39,6 @@
 static_assert(TREND_STATS_LDS_STEPS * 512 <= 65536 && TREND_SELECT_LDS_STEPS * 512 <= 65536,
               "the tile is dynamic LDS without an attribute: at most 64 KiB");
 
-typedef unsigned long long u64;
-
 __device__ __forceinline__ double nan_d() { return __builtin_nan(""); }
 __device__ __forceinline__ double trend_sample(double v) { return fabs(v) <= 1.7976931348623157e308 ? v : nan_d(); }
 

@@ -1419,6 +1419,77 @@ class HotPath:
     def _host(t: Optional[torch.Tensor], dt):
         return None if t is None else t.cpu().numpy().view(dt)
 
+    def _weights_check(self, what: str, weights: Optional[torch.Tensor], Cn: int) -> None:
+        if weights is not None and (weights.dtype != torch.float32 or tuple(weights.shape) != (Cn,) or not weights.is_contiguous()
+                                    or weights.device != self.device):
+            raise ProcessingError(f"{what}: the weights must be a contiguous float32 [{Cn}] tensor on the engine's "
+                                  f"device", details=f"got {weights.dtype} {tuple(weights.shape)} on {weights.device}")
+
+    def _thresholds_check(self, what: str, thr: Optional[torch.Tensor], doy, Cn: int, sentence: str) -> None:
+        """``thr`` is float32 ``[n_doy, Cn]`` and ``doy`` comes with it; ``sentence`` is the refusal."""
+        if thr is None or doy is None or thr.dim() != 2 or thr.dtype != torch.float32 or int(thr.shape[1]) != Cn or \
+                int(thr.shape[0]) <= 0 or not thr.is_contiguous() or thr.device != self.device:
+            raise ProcessingError(f"{what}: {sentence}",
+                                  details="one of thr / doy is missing" if thr is None or doy is None else
+                                  f"got {thr.dtype} {tuple(thr.shape)} on {thr.device}")
+
+    @staticmethod
+    def _sections_check(what: str, sgrp, cls, G2: int, R: int, cats: Optional[bool] = None) -> bool:
+        """Whether the call counts sections: ``sgrp`` and ``cls`` given, together, with ``G2 > 0`` and ``R > 0`` -- and, where
+        the caller says whether it has thresholds (``cats``), with them."""
+        sect = sgrp is not None or cls is not None
+        if sect and (sgrp is None or cls is None or G2 <= 0 or R <= 0 or cats is False):
+            raise ProcessingError(f"{what}: the section counts need step labels, cell classes, G2 > 0"
+                                  f"{' and R > 0' if cats is None else ', R > 0 and thresholds'} together",
+                                  details=f"G2 = {G2}, R = {R}" +
+                                  ("" if cats is None else f", thresholds {'given' if cats else 'missing'}"))
+        return sect
+
+    def _whole_output_check(self, what: str, name: str, out: Optional[torch.Tensor], Cn: int, end: int,
+                            second: Optional[bool] = None) -> None:
+        """``out`` (the ``name`` of the refusal) is the whole uint8 ``[T, Cn]`` output and reaches the window's end -- and, where
+        the caller has two passes, this is not the ``second``."""
+        if out is not None and (second or out.dtype != torch.uint8 or out.dim() != 2 or int(out.shape[1]) != Cn or
+                                int(out.shape[0]) < end or not out.is_contiguous() or out.device != self.device):
+            raise ProcessingError(f"{what}: the {name} must be the whole contiguous uint8 [T, {Cn}] output on the engine's "
+                                  f"device, T >= {end}{'' if second is None else ', and belongs to the summary pass'}",
+                                  details=f"got {out.dtype} {tuple(out.shape)} on {out.device}")
+
+    def _event_slots(self, what: str, ev_tmin, ev_tmax, t0: int) -> tuple:
+        """``(tmin, n_ev, t0, off, n_slots, alloc)`` of the spans ``ev_tmin`` / ``ev_tmax``: the slots of
+        :meth:`event_slot_plan`, and how many to allocate."""
+        tmin_h, tmax_h = np.asarray(ev_tmin, dtype=np.int64), np.asarray(ev_tmax, dtype=np.int64)
+        n_ev = int(tmin_h.size) - 1
+        t0 = int(t0)
+        if n_ev <= 0 or tmin_h.ndim != 1 or tmax_h.shape != tmin_h.shape or t0 < 0:
+            raise ProcessingError(f"{what}: ev_tmin and ev_tmax must have one entry per event 0..n_ev, n_ev > 0, and t0 "
+                                  "must not be negative", details=f"spans {tmin_h.shape} / {tmax_h.shape}, t0 = {t0}")
+        off = self.event_slot_plan(tmin_h, tmax_h)
+        n_slots = int(off[-1])
+        return tmin_h, n_ev, t0, off, n_slots, max(n_slots, 1)  # no event has a step: one slot that nothing addresses
+
+    def _slot_tables(self, tmin_h: np.ndarray, off: np.ndarray) -> dict:
+        """The ``"tmin"``, ``"off"`` and ``"plan"`` entries of the accumulators over event slots."""
+        return {"tmin": self._dev(np.clip(tmin_h, 0, 2**31 - 1).astype(np.int32)), "off": self._dev(off), "plan": off}
+
+    @staticmethod
+    def _table_bytes(tabs: dict) -> int:
+        return sum(4 * v.size for v in tabs.values() if v is not None)
+
+    def _zeros(self, name: str, shape, dtype) -> torch.Tensor:
+        """A zeroed accumulator."""
+        return self._buf(None, name, shape, dtype, self.device).zero_()
+
+    @staticmethod
+    def _key_max(key: np.ndarray) -> np.ndarray:
+        """The float32 maxima of the uint32 keys the device raised; key 0 (none) is NaN."""
+        return np.where(key != 0, key_float(key), np.float32(np.nan))
+
+    @staticmethod
+    def _key_step(key: np.ndarray, tmax: np.ndarray) -> np.ndarray:
+        """The steps of those maxima; -1 where there is none."""
+        return np.where(key != 0, tmax, np.int32(-1))
+
     @staticmethod
     def event_slot_plan(ev_tmin, ev_tmax, T: Optional[int] = None) -> np.ndarray:
         """The compact (timestep, event) slots of :meth:`event_rename` and :meth:`event_intensity`: ``off`` int64
@@ -1449,28 +1520,15 @@ class HotPath:
         written out of range)."""
         Tb, Cn = self._ids_check(ids)
         self._anomaly_window_check("event_intensity", anom, Tb, Cn)
-        if weights is not None and (weights.dtype != torch.float32 or tuple(weights.shape) != (Cn,) or not weights.is_contiguous()
-                                    or weights.device != self.device):
-            raise ProcessingError(f"event_intensity: the weights must be a contiguous float32 [{Cn}] tensor on the engine's "
-                                  f"device", details=f"got {weights.dtype} {tuple(weights.shape)} on {weights.device}")
-        tmin_h, tmax_h = np.asarray(ev_tmin, dtype=np.int64), np.asarray(ev_tmax, dtype=np.int64)
-        n_ev = int(tmin_h.size) - 1
-        t0 = int(t0)
-        if n_ev <= 0 or tmin_h.ndim != 1 or tmax_h.shape != tmin_h.shape or t0 < 0:
-            raise ProcessingError("event_intensity: ev_tmin and ev_tmax must have one entry per event 0..n_ev, n_ev > 0, and t0 "
-                                  "must not be negative", details=f"spans {tmin_h.shape} / {tmax_h.shape}, t0 = {t0}")
-        off = self.event_slot_plan(tmin_h, tmax_h)
-        n_slots = int(off[-1])
-        alloc = max(n_slots, 1)  # no event has a step: one slot that nothing addresses
+        self._weights_check("event_intensity", weights, Cn)
+        tmin_h, n_ev, t0, off, n_slots, alloc = self._event_slots("event_intensity", ev_tmin, ev_tmax, t0)
         if acc is None:
             self._check_fits(36 * n_slots + 12 * (n_ev + 2), "event intensity",
                              f"{n_slots} (timestep, event) slots between each event's first and last timestep, 36 bytes each, "
                              f"and the tables of {n_ev} events")
-            acc = {"cnt": self._buf(None, "int_cnt", (alloc, 2), torch.int64, self.device).zero_(),
-                   "sums": self._buf(None, "int_sums", (alloc, 2), torch.float64, self.device).zero_(),
-                   "vmax": self._buf(None, "int_vmax", (alloc,), torch.int32, self.device).zero_(),
-                   "status": self._buf(None, "int_status", (1,), torch.int64, self.device).zero_(),
-                   "tmin": self._dev(np.clip(tmin_h, 0, 2**31 - 1).astype(np.int32)), "off": self._dev(off), "plan": off}
+            acc = {"cnt": self._zeros("int_cnt", (alloc, 2), torch.int64), "sums": self._zeros("int_sums", (alloc, 2), torch.float64),
+                   "vmax": self._zeros("int_vmax", (alloc,), torch.int32), "status": self._zeros("int_status", (1,), torch.int64),
+                   **self._slot_tables(tmin_h, off)}
         elif tuple(acc["cnt"].shape) != (alloc, 2) or not np.array_equal(acc["plan"], off):
             raise ProcessingError("event_intensity: the accumulators were planned for other spans",
                                   details=f"{tuple(acc['cnt'].shape)[0]} slots there, {alloc} here")
@@ -1502,29 +1560,11 @@ class HotPath:
         outside ``0 .. n_doy - 1``, raises :class:`ProcessingError` (it was counted, nothing was written out of range)."""
         Tb, Cn = self._ids_check(ids)
         self._anomaly_window_check("event_categories", anom, Tb, Cn)
-        if weights is not None and (weights.dtype != torch.float32 or tuple(weights.shape) != (Cn,) or not weights.is_contiguous()
-                                    or weights.device != self.device):
-            raise ProcessingError(f"event_categories: the weights must be a contiguous float32 [{Cn}] tensor on the engine's "
-                                  f"device", details=f"got {weights.dtype} {tuple(weights.shape)} on {weights.device}")
-        if thr is None or doy is None or thr.dim() != 2 or thr.dtype != torch.float32 or int(thr.shape[1]) != Cn or \
-                int(thr.shape[0]) <= 0 or not thr.is_contiguous() or thr.device != self.device:
-            raise ProcessingError(f"event_categories: the thresholds must be a contiguous float32 [n_doy, {Cn}] tensor on the "
-                                  "engine's device, with the row of every step",
-                                  details="one of thr / doy is missing" if thr is None or doy is None else
-                                  f"got {thr.dtype} {tuple(thr.shape)} on {thr.device}")
-        tmin_h, tmax_h = np.asarray(ev_tmin, dtype=np.int64), np.asarray(ev_tmax, dtype=np.int64)
-        n_ev = int(tmin_h.size) - 1
-        t0 = int(t0)
-        if n_ev <= 0 or tmin_h.ndim != 1 or tmax_h.shape != tmin_h.shape or t0 < 0:
-            raise ProcessingError("event_categories: ev_tmin and ev_tmax must have one entry per event 0..n_ev, n_ev > 0, and t0 "
-                                  "must not be negative", details=f"spans {tmin_h.shape} / {tmax_h.shape}, t0 = {t0}")
-        if field is not None and (field.dtype != torch.uint8 or field.dim() != 2 or int(field.shape[1]) != Cn or
-                                  int(field.shape[0]) < t0 + Tb or not field.is_contiguous() or field.device != self.device):
-            raise ProcessingError(f"event_categories: the field must be the whole contiguous uint8 [T, {Cn}] output on the "
-                                  f"engine's device, T >= {t0 + Tb}", details=f"got {field.dtype} {tuple(field.shape)} on {field.device}")
-        off = self.event_slot_plan(tmin_h, tmax_h)
-        n_slots = int(off[-1])
-        alloc = max(n_slots, 1)  # no event has a step: one slot that nothing addresses
+        self._weights_check("event_categories", weights, Cn)
+        self._thresholds_check("event_categories", thr, doy, Cn, f"the thresholds must be a contiguous float32 [n_doy, {Cn}] "
+                               "tensor on the engine's device, with the row of every step")
+        tmin_h, n_ev, t0, off, n_slots, alloc = self._event_slots("event_categories", ev_tmin, ev_tmax, t0)
+        self._whole_output_check("event_categories", "field", field, Cn, t0 + Tb)
         n_doy = int(thr.shape[0])
         weighted = weights is not None
         if acc is None:
@@ -1532,10 +1572,9 @@ class HotPath:
             self._check_fits((56 + (48 if weighted else 0)) * n_slots + 12 * (n_ev + 2) + 4 * tabs["doy"].size + 16, "event categories",
                              f"{n_slots} (timestep, event) slots between each event's first and last timestep, "
                              f"{56 + (48 if weighted else 0)} bytes each, the tables of {n_ev} events and the row of every step")
-            acc = {"cnt": self._buf(None, "cat_cnt", (alloc, 7), torch.int64, self.device).zero_(),
-                   "area": self._buf(None, "cat_area", (alloc, 6), torch.float64, self.device).zero_() if weighted else None,
-                   "status": self._buf(None, "cat_status", (2,), torch.int64, self.device).zero_(),
-                   "tmin": self._dev(np.clip(tmin_h, 0, 2**31 - 1).astype(np.int32)), "off": self._dev(off), "plan": off,
+            acc = {"cnt": self._zeros("cat_cnt", (alloc, 7), torch.int64),
+                   "area": self._zeros("cat_area", (alloc, 6), torch.float64) if weighted else None,
+                   "status": self._zeros("cat_status", (2,), torch.int64), **self._slot_tables(tmin_h, off),
                    "n_doy": n_doy, **self._upload_tables(tabs)}
         elif tuple(acc["cnt"].shape) != (alloc, 7) or not np.array_equal(acc["plan"], off) or acc["n_doy"] != n_doy or \
                 (acc["area"] is not None) != weighted:
@@ -1577,30 +1616,25 @@ class HotPath:
         x, Tb, Cn = self._presence_window("occurrence", x)
         t0, G, G2, R = int(t0), int(G), int(G2), int(R)
         ids = [int(k) for k in event_ids]
-        sect = sgrp is not None or cls is not None
         if t0 < 0 or G <= 0 or (grp is None and G != 1) or any(k <= 0 or k > 2**31 - 1 for k in ids):
             raise ProcessingError("occurrence: t0 must not be negative, G and the event IDs must be positive, and G > 1 needs labels",
                                   details=f"t0 = {t0}, G = {G}, labels {'given' if grp is not None else 'missing'}, event_ids {ids[:8]}")
-        if sect and (sgrp is None or cls is None or G2 <= 0 or R <= 0):
-            raise ProcessingError("occurrence: the section counts need step labels, cell classes, G2 > 0 and R > 0 together",
-                                  details=f"G2 = {G2}, R = {R}")
+        sect = self._sections_check("occurrence", sgrp, cls, G2, R)
         plan = (G, Cn, G2 if sect else 0, R if sect else 0, bool(runs), tuple(ids))
         if acc is None:
             tabs = label_tables("occurrence", (("grp", grp, None), ("sgrp", sgrp if sect else None, None),
                                                ("cls", cls if sect else None, Cn)))
             K = len(ids)
-            need = 4 * G * Cn + (12 * Cn if runs else 0) + (8 * G2 * R if sect else 0) + 4 * K * Cn + 16 + \
-                sum(4 * v.size for v in tabs.values() if v is not None)
+            need = 4 * G * Cn + (12 * Cn if runs else 0) + (8 * G2 * R if sect else 0) + 4 * K * Cn + 16 + self._table_bytes(tabs)
             self._check_fits(need, "occurrence",
                              f"{G} x {Cn} uint32 counts, {'3 x ' + str(Cn) + ' uint32 run statistics, ' if runs else ''}"
                              f"{G2 if sect else 0} x {R if sect else 0} uint64 section counts, {K} x {Cn} uint32 counts of "
                              f"selected events, and the label tables")
-            acc = {"cell_cnt": self._buf(None, "occ_cnt", (G, Cn), torch.int32, self.device).zero_(),
-                   "runs": self._buf(None, "occ_runs", (3, Cn), torch.int32, self.device).zero_() if runs else None,
-                   "sec_cnt": self._buf(None, "occ_sec", (G2, R), torch.int64, self.device).zero_() if sect else None,
-                   "dur": self._buf(None, "occ_dur", (K, Cn), torch.int32, self.device).zero_() if K else None,
-                   "status": self._buf(None, "occ_status", (2,), torch.int64, self.device).zero_(),
-                   "plan": plan, **self._upload_tables(tabs)}
+            acc = {"cell_cnt": self._zeros("occ_cnt", (G, Cn), torch.int32),
+                   "runs": self._zeros("occ_runs", (3, Cn), torch.int32) if runs else None,
+                   "sec_cnt": self._zeros("occ_sec", (G2, R), torch.int64) if sect else None,
+                   "dur": self._zeros("occ_dur", (K, Cn), torch.int32) if K else None,
+                   "status": self._zeros("occ_status", (2,), torch.int64), "plan": plan, **self._upload_tables(tabs)}
         self._window_check("occurrence", acc, plan, ("grp", "sgrp"), t0, Tb, Cn)
         fn = "marex_occurrence_i32" if x.dtype == torch.int32 else "marex_occurrence_u8"
         tb = acc["tabs"]
@@ -1647,36 +1681,28 @@ class HotPath:
         if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in ints):
             raise ProcessingError("compound: t0, max_lag, tolerance, G, G2 and R must be integers", details=f"got {ints}")
         t0, L, K, G, G2, R = (int(v) for v in ints)
-        sect = sgrp is not None or cls is not None
         if t0 < 0 or G <= 0 or (grp is None and G != 1) or not 0 <= L <= self.COMPOUND_MAX_LAG or not 0 <= K <= self.COMPOUND_MAX_LAG:
             raise ProcessingError(f"compound: t0 must not be negative, G must be positive, G > 1 needs labels, and max_lag and "
                                   f"tolerance must lie in 0 .. {self.COMPOUND_MAX_LAG}",
                                   details=f"t0 = {t0}, G = {G}, labels {'given' if grp is not None else 'missing'}, max_lag = {L}, "
                                           f"tolerance = {K}")
-        if sect and (sgrp is None or cls is None or G2 <= 0 or R <= 0):
-            raise ProcessingError("compound: the section counts need step labels, cell classes, G2 > 0 and R > 0 together",
-                                  details=f"G2 = {G2}, R = {R}")
-        if mask is not None and (mask.dtype != torch.uint8 or mask.dim() != 2 or int(mask.shape[1]) != Cn or
-                                 int(mask.shape[0]) < t0 + Tb or not mask.is_contiguous() or mask.device != self.device):
-            raise ProcessingError(f"compound: the mask must be the whole contiguous uint8 [T, {Cn}] output on the engine's "
-                                  f"device, T >= {t0 + Tb}", details=f"got {mask.dtype} {tuple(mask.shape)} on {mask.device}")
+        sect = self._sections_check("compound", sgrp, cls, G2, R)
+        self._whole_output_check("compound", "mask", mask, Cn, t0 + Tb)
         S = self.COMPOUND_STATE_ROWS
         plan = (G, Cn, G2 if sect else 0, R if sect else 0, L, K)
         if acc is None:
             tabs = label_tables("compound", (("grp", grp, None), ("sgrp", sgrp if sect else None, None),
                                              ("cls", cls if sect else None, Cn)))
             rows = 3 * G + S + (2 * L + 1 if L else 0)
-            need = 4 * rows * Cn + (24 * G2 * R if sect else 0) + 16 + sum(4 * v.size for v in tabs.values() if v is not None)
+            need = 4 * rows * Cn + (24 * G2 * R if sect else 0) + 16 + self._table_bytes(tabs)
             self._check_fits(need, "compound",
                              f"3 x {G} x {Cn} uint32 counts, {S} x {Cn} uint32 of carried state, {2 * L + 1 if L else 0} x {Cn} "
                              f"uint32 lag counts, 3 x {G2 if sect else 0} x {R if sect else 0} uint64 section counts, and the "
                              f"label tables")
-            acc = {"cell_cnt": self._buf(None, "cmp_cnt", (3, G, Cn), torch.int32, self.device).zero_(),
-                   "state": self._buf(None, "cmp_state", (S, Cn), torch.int32, self.device).zero_(),
-                   "lag": self._buf(None, "cmp_lag", (2 * L + 1, Cn), torch.int32, self.device).zero_() if L else None,
-                   "sec_cnt": self._buf(None, "cmp_sec", (3, G2, R), torch.int64, self.device).zero_() if sect else None,
-                   "status": self._buf(None, "cmp_status", (2,), torch.int64, self.device).zero_(),
-                   "plan": plan, **self._upload_tables(tabs)}
+            acc = {"cell_cnt": self._zeros("cmp_cnt", (3, G, Cn), torch.int32), "state": self._zeros("cmp_state", (S, Cn), torch.int32),
+                   "lag": self._zeros("cmp_lag", (2 * L + 1, Cn), torch.int32) if L else None,
+                   "sec_cnt": self._zeros("cmp_sec", (3, G2, R), torch.int64) if sect else None,
+                   "status": self._zeros("cmp_status", (2,), torch.int64), "plan": plan, **self._upload_tables(tabs)}
         self._window_check("compound", acc, plan, ("grp", "sgrp"), t0, Tb, Cn)
         tb = acc["tabs"]
         self.call("marex_compound_u8", a, b, t0, Tb, Cn, L, K, tb["grp"], G, tb["sgrp"], G2 if sect else 0, tb["cls"],
@@ -1768,39 +1794,29 @@ class HotPath:
         self._anomaly_window_check("local_intensity", anom, Tb, Cn)
         t0, G, G2, R, match = int(t0), int(G), int(G2), int(R), int(match)
         cats = thr is not None or doy is not None
-        sect = sgrp is not None or cls is not None
         if t0 < 0 or G <= 0 or (grp is None and G != 1) or match < 0 or match > 2**31 - 1:
             raise ProcessingError("local_intensity: t0 and match must not be negative, G must be positive, and G > 1 needs labels",
                                   details=f"t0 = {t0}, G = {G}, labels {'given' if grp is not None else 'missing'}, match = {match}")
-        if cats and (thr is None or doy is None or thr.dim() != 2 or thr.dtype != torch.float32 or int(thr.shape[1]) != Cn or
-                     int(thr.shape[0]) <= 0 or not thr.is_contiguous() or thr.device != self.device):
-            raise ProcessingError(f"local_intensity: the categories need thresholds, a contiguous float32 [n_doy, {Cn}] tensor on "
-                                  "the engine's device, and the row of every step",
-                                  details="one of thr / doy is missing" if thr is None or doy is None else
-                                  f"got {thr.dtype} {tuple(thr.shape)} on {thr.device}")
-        if sect and (sgrp is None or cls is None or G2 <= 0 or R <= 0 or not cats):
-            raise ProcessingError("local_intensity: the section counts need step labels, cell classes, G2 > 0, R > 0 and "
-                                  "thresholds together", details=f"G2 = {G2}, R = {R}, thresholds {'given' if cats else 'missing'}")
+        if cats:
+            self._thresholds_check("local_intensity", thr, doy, Cn, f"the categories need thresholds, a contiguous float32 "
+                                   f"[n_doy, {Cn}] tensor on the engine's device, and the row of every step")
+        sect = self._sections_check("local_intensity", sgrp, cls, G2, R, cats)
         n_doy = int(thr.shape[0]) if cats else 0
         plan = (G, Cn, n_doy, G2 if sect else 0, R if sect else 0, match)
         if acc is None:
             tabs = label_tables("local_intensity", (("grp", grp, None), ("doy", doy if cats else None, None),
                                                     ("sgrp", sgrp if sect else None, None), ("cls", cls if sect else None, Cn)))
-            need = G * Cn * (24 + (24 if cats else 0)) + (48 * G2 * R if sect else 0) + 16 + \
-                sum(4 * v.size for v in tabs.values() if v is not None)
+            need = G * Cn * (24 + (24 if cats else 0)) + (48 * G2 * R if sect else 0) + 16 + self._table_bytes(tabs)
             self._check_fits(need, "local intensity",
                              f"{G} x {Cn} cells of {24 + (24 if cats else 0)} bytes (days, invalid, sum, maximum, its step"
                              f"{', six category counts' if cats else ''}), {G2 if sect else 0} x {R if sect else 0} x 6 uint64 "
                              f"section counts, and the label tables")
-            acc = {"days": self._buf(None, "li_days", (G, Cn), torch.int32, self.device).zero_(),
-                   "invalid": self._buf(None, "li_invalid", (G, Cn), torch.int32, self.device).zero_(),
-                   "sum": self._buf(None, "li_sum", (G, Cn), torch.float64, self.device).zero_(),
-                   "vmax": self._buf(None, "li_vmax", (G, Cn), torch.int32, self.device).zero_(),
-                   "tmax": self._buf(None, "li_tmax", (G, Cn), torch.int32, self.device).zero_(),
-                   "cat_days": self._buf(None, "li_cat", (G, 6, Cn), torch.int32, self.device).zero_() if cats else None,
-                   "sec_cnt": self._buf(None, "li_sec", (G2, R, 6), torch.int64, self.device).zero_() if sect else None,
-                   "status": self._buf(None, "li_status", (2,), torch.int64, self.device).zero_(),
-                   "plan": plan, **self._upload_tables(tabs)}
+            acc = {"days": self._zeros("li_days", (G, Cn), torch.int32), "invalid": self._zeros("li_invalid", (G, Cn), torch.int32),
+                   "sum": self._zeros("li_sum", (G, Cn), torch.float64), "vmax": self._zeros("li_vmax", (G, Cn), torch.int32),
+                   "tmax": self._zeros("li_tmax", (G, Cn), torch.int32),
+                   "cat_days": self._zeros("li_cat", (G, 6, Cn), torch.int32) if cats else None,
+                   "sec_cnt": self._zeros("li_sec", (G2, R, 6), torch.int64) if sect else None,
+                   "status": self._zeros("li_status", (2,), torch.int64), "plan": plan, **self._upload_tables(tabs)}
         self._window_check("local_intensity", acc, plan, ("grp", "doy", "sgrp"), t0, Tb, Cn)
         fn = "marex_local_intensity_i32" if x.dtype == torch.int32 else "marex_local_intensity_u8"
         tb = acc["tabs"]
@@ -1814,8 +1830,7 @@ class HotPath:
         host = self._host
         key = host(acc["vmax"], np.uint32)
         out.update(days=host(acc["days"], np.uint32), invalid=host(acc["invalid"], np.uint32), sum=host(acc["sum"], np.float64),
-                   vmax=np.where(key != 0, key_float(key), np.float32(np.nan)),  # key 0: none
-                   tmax=np.where(key != 0, host(acc["tmax"], np.int32), np.int32(-1)),
+                   vmax=self._key_max(key), tmax=self._key_step(key, host(acc["tmax"], np.int32)),
                    cat_days=host(acc["cat_days"], np.uint32), sec_cnt=host(acc["sec_cnt"], np.uint64))
         return out
 
@@ -1867,33 +1882,27 @@ class HotPath:
             raise ProcessingError("cell_events: t0 and max_gap must not be negative, G and min_duration must be positive, and "
                                   "G > 1 needs labels", details=f"t0 = {t0}, G = {G}, labels {'given' if grp is not None else 'missing'}, "
                                                                 f"min_duration = {D}, max_gap = {gap}")
-        if mask is not None and (records is not None or mask.dtype != torch.uint8 or mask.dim() != 2 or int(mask.shape[1]) != Cn or
-                                 int(mask.shape[0]) < t0 + Tb or not mask.is_contiguous() or mask.device != self.device):
-            raise ProcessingError(f"cell_events: the mask must be the whole contiguous uint8 [T, {Cn}] output on the engine's "
-                                  f"device, T >= {t0 + Tb}, and belongs to the summary pass",
-                                  details=f"got {mask.dtype} {tuple(mask.shape)} on {mask.device}")
         anomalies, second = anom is not None, records is not None
+        self._whole_output_check("cell_events", "mask", mask, Cn, t0 + Tb, second)
         plan = (G, Cn, anomalies, D, gap, second)
         if acc is None:
             tabs = label_tables("cell_events", (("grp", grp, None),))
             planes = 10 if anomalies else 4
             per_acc = 0 if second else 12 + (16 if anomalies else 0)
-            need = Cn * (4 * planes + (16 if anomalies else 0)) + G * Cn * per_acc + 16 + \
-                sum(4 * v.size for v in tabs.values() if v is not None)
+            need = Cn * (4 * planes + (16 if anomalies else 0)) + G * Cn * per_acc + 16 + self._table_bytes(tabs)
             self._check_fits(need, "cell events",
                              f"{Cn} cells of carried state, {4 * planes + (16 if anomalies else 0)} bytes each, {G} x {Cn} cells "
                              f"of accumulators, {per_acc} bytes each, and the label table")
-            dev = self.device
-            acc = {"state_i32": self._buf(None, "ce_sti", (planes, Cn), torch.int32, dev).zero_(),
-                   "state_f64": self._buf(None, "ce_stf", (2, Cn), torch.float64, dev).zero_() if anomalies else None,
-                   "status": self._buf(None, "ce_status", (2,), torch.int64, dev).zero_(), "plan": plan,
+            acc = {"state_i32": self._zeros("ce_sti", (planes, Cn), torch.int32),
+                   "state_f64": self._zeros("ce_stf", (2, Cn), torch.float64) if anomalies else None,
+                   "status": self._zeros("ce_status", (2,), torch.int64), "plan": plan,
                    **{k: None for k in ("events", "event_days", "duration_max", "sum", "vmax", "invalid")},
                    **self._upload_tables(tabs)}
             if not second:
                 for k in ("events", "event_days", "duration_max") + (("vmax", "invalid") if anomalies else ()):
-                    acc[k] = self._buf(None, "ce_" + k, (G, Cn), torch.int32, dev).zero_()
+                    acc[k] = self._zeros("ce_" + k, (G, Cn), torch.int32)
                 if anomalies:
-                    acc["sum"] = self._buf(None, "ce_sum", (G, Cn), torch.float64, dev).zero_()
+                    acc["sum"] = self._zeros("ce_sum", (G, Cn), torch.float64)
         self._window_check("cell_events", acc, plan, ("grp",), t0, Tb, Cn)
         if second and (int(records["off"].numel()) != Cn + 1 or ("sum" in records) != anomalies):
             raise ProcessingError("cell_events: the record buffers were planned for another call",
@@ -1920,8 +1929,7 @@ class HotPath:
                  "end": host(records["end"][:n], np.int32)}
             if anomalies:
                 key = host(records["vmax"][:n], np.uint32)
-                r.update(vmax=np.where(key != 0, key_float(key), np.float32(np.nan)),
-                         tmax=np.where(key != 0, host(records["tmax"][:n], np.int32), np.int32(-1)),
+                r.update(vmax=self._key_max(key), tmax=self._key_step(key, host(records["tmax"][:n], np.int32)),
                          sum=host(records["sum"][:n], np.float64), invalid=host(records["invalid"][:n], np.uint32))
             out.update(rec=r, records=records)
             return out
@@ -1929,7 +1937,7 @@ class HotPath:
                    duration_max=host(acc["duration_max"], np.uint32))
         if anomalies:
             key = host(acc["vmax"], np.uint32)
-            out.update(sum=host(acc["sum"], np.float64), vmax=np.where(key != 0, key_float(key), np.float32(np.nan)),
+            out.update(sum=host(acc["sum"], np.float64), vmax=self._key_max(key),
                        invalid=host(acc["invalid"], np.uint32))
         return out
 

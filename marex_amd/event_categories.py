@@ -15,10 +15,10 @@ from typing import Optional
 import numpy as np
 
 from . import _stream, calendar, occurrence as mo
-from ._stream import _I32_MAX, _Windows, _check_block_steps, _plan_windows
+from ._stream import _I32_MAX, _Windows, _check_block_steps
 from .exceptions import ProcessingError, TrackingError
 from .intensity import _event_spans, _time_of_max_values, _validate
-from .local_intensity import CATEGORIES, _device_thresholds, _threshold_layout
+from .local_intensity import CATEGORIES, _device_thresholds, _threshold_layout, _thresholds_copied
 from .track import _tensor_of
 
 #: bytes of the device accumulators per (timestep, event) slot: seven uint64 counts and six float64 areas
@@ -62,36 +62,26 @@ def _device_pass(p, ID_field, dat_anomaly, thresholds, return_field: bool, devic
     ids_w = _Windows(eng, ID_field, T, C, np.int32, True)
     an_w = _Windows(eng, dat_anomaly, T, C, np.float32, False)
     per_step = ids_w.upload_bytes_per_step + an_w.upload_bytes_per_step
-    t_thr = _tensor_of(thresholds)
-    thr_copy = not (t_thr is not None and t_thr.device == eng.device and p["kind"] != "doy_last"
-                    and "float32" in str(t_thr.dtype) and t_thr.is_contiguous())
+    thr_copy = _thresholds_copied(eng, thresholds, p["kind"])
     fixed = (4 * n_doy * C if thr_copy else 0) + (T * C if return_field else 0)
 
-    def check(slots: int):
-        free = _stream._free_bytes(eng)
-        need = fixed + SLOT_BYTES * slots + per_step * (T if p["block_steps"] is None else 1)
-        if need > free:
-            raise TrackingError(
-                f"event_categories: needs {need / 1e9:.3f} GB of device memory, {free / 1e9:.3f} GB are free",
-                details=f"{n_doy} x {C} float32 thresholds{'' if thr_copy else ' (resident already)'}, {slots} (timestep, event) "
-                        f"slots of {SLOT_BYTES} bytes, {'the category field of ' + str(T) + ' x ' + str(C) + ' bytes, ' if return_field else ''}"
-                        f"and the ID field and the anomalies of {T} timesteps, 4 bytes per cell each, as far as they are not on "
-                        "the device already",
-                suggestions=["Pass block_steps='auto'", "Pass block_steps=<timesteps per window>"]
-                + (["Pass return_field=False"] if return_field else []))
-        return free
+    def plan(slots: int) -> int:
+        """The steps per window beside ``slots`` slots; :class:`TrackingError` when not even one fits."""
+        return _stream._window_steps(
+            eng, "event_categories", T, C, per_step, fixed + SLOT_BYTES * slots, p["block_steps"],
+            f"{n_doy} x {C} float32 thresholds{'' if thr_copy else ' (resident already)'}, {slots} (timestep, event) "
+            f"slots of {SLOT_BYTES} bytes, {'the category field of ' + str(T) + ' x ' + str(C) + ' bytes, ' if return_field else ''}"
+            f"and the ID field and the anomalies of {T} timesteps, 4 bytes per cell each, as far as they are not on "
+            "the device already", ["Pass return_field=False"] if return_field else [])
 
-    free = check(0)  # before anything is uploaded; once more when the slots are known
-    B = _plan_windows(eng, T, C, per_step, p["block_steps"], "event_categories")
-    if p["block_steps"] == "auto" and per_step:
-        B = max(1, min(B, (free - free // 16 - fixed) // per_step))
+    B = plan(0)  # before anything is uploaded: the windows of both passes
     wins = [(a, min(T, a + B)) for a in range(0, T, B)]
     tmin, tmax, kept = _event_spans(eng, ids_w, wins)
     N = int(tmin.size) - 1
     if N <= 0:
         field = torch.zeros((T, C), dtype=torch.uint8, device=eng.device) if return_field else None
         return 0, tmin, np.zeros(2, np.int64), np.zeros((0, 7), np.int64), None, field
-    check(int(HotPath.event_slot_plan(tmin, tmax)[-1]))
+    plan(int(HotPath.event_slot_plan(tmin, tmax)[-1]))  # once more now that the slots are known, for its refusal alone
     thr = _device_thresholds(eng, thresholds, p["kind"], n_doy, C)
     wd = None if w is None else torch.from_numpy(w).to(eng.device)
     field = HotPath._buf(None, "cat_field", (T, C), torch.uint8, eng.device) if return_field else None

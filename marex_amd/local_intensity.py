@@ -16,8 +16,8 @@ from __future__ import annotations
 import numpy as np
 
 from . import _stream, calendar, occurrence as mo
-from ._stream import _I32_MAX, _Windows, _check_block_steps, _dtype_name, _kind, _plan_windows
-from .exceptions import TrackingError, create_data_validation_error
+from ._stream import _I32_MAX, _Windows, _check_block_steps, _dtype_name, _kind
+from .exceptions import create_data_validation_error
 from .track import _tensor_of
 
 CATEGORIES = ("below", "moderate", "strong", "severe", "extreme", "undefined")
@@ -109,18 +109,12 @@ def _device_thresholds(eng, thresholds, kind: str, n_doy: int, C: int):
     return t.reshape(n_doy, C).to(torch.float32).contiguous()
 
 
-def _window_steps(eng, T: int, C: int, per_step: int, fixed: int, block_steps, details: str) -> int:
-    """Steps per window; ``fixed``: the bytes that stay for the whole call (accumulators, thresholds)."""
-    free = _stream._free_bytes(eng)
-    need = fixed + per_step * (T if block_steps is None else 1)
-    if need > free:
-        raise TrackingError(f"local_intensity: needs {need / 1e9:.3f} GB of device memory, {free / 1e9:.3f} GB are free",
-                            details=details, suggestions=["Pass block_steps='auto'", "Pass block_steps=<timesteps per window>",
-                                                          "Group by fewer labels"])
-    B = _plan_windows(eng, T, C, per_step, block_steps, "local_intensity", details)
-    if block_steps == "auto" and per_step:
-        B = max(1, min(B, (free - free // 16 - fixed) // per_step))
-    return B
+def _thresholds_copied(eng, thresholds, kind: str) -> bool:
+    """Whether :func:`_device_thresholds` makes a copy: not of a contiguous float32 tensor on the engine's device whose
+    layout needs no transpose, which is resident as it is."""
+    t = _tensor_of(thresholds)
+    return not (t is not None and t.device == eng.device and kind != "doy_last" and "float32" in str(t.dtype)
+                and t.is_contiguous())
 
 
 def _device_pass(p, field, dat_anomaly, thresholds, device):
@@ -139,16 +133,15 @@ def _device_pass(p, field, dat_anomaly, thresholds, device):
     x_w = _Windows(eng, field, T, C, np.uint8 if p["kind"] == "m" else np.int32, p["kind"] == "i")
     a_w = _Windows(eng, dat_anomaly, T, C, np.float32, False)
     n_doy = p["thr"][2] if cats else 0
-    t_thr = _tensor_of(thresholds) if cats else None
-    thr_copy = cats and not (t_thr is not None and t_thr.device == eng.device and p["thr"][0] != "doy_last"
-                             and "float32" in str(t_thr.dtype) and t_thr.is_contiguous())
+    thr_copy = cats and _thresholds_copied(eng, thresholds, p["thr"][0])
     fixed = accumulator_bytes(G, C, cats) + (4 * n_doy * C if thr_copy else 0) + \
         (48 * sec[0][1] * sec[2] if sec is not None else 0)
     per_step = x_w.upload_bytes_per_step + a_w.upload_bytes_per_step
-    B = _window_steps(eng, T, C, per_step, fixed, p["block_steps"],
-                      f"{G} x {C} cells of accumulators, {24 + (24 if cats else 0)} bytes each, {n_doy} x {C} float32 thresholds, "
-                      f"and the field and the anomalies of {T} timesteps, {x_w.item} + 4 bytes per cell, as far as they are not "
-                      "on the device already")
+    B = _stream._window_steps(
+        eng, "local_intensity", T, C, per_step, fixed, p["block_steps"],
+        f"{G} x {C} cells of accumulators, {24 + (24 if cats else 0)} bytes each, {n_doy} x {C} float32 thresholds, "
+        f"and the field and the anomalies of {T} timesteps, {x_w.item} + 4 bytes per cell, as far as they are not "
+        "on the device already", ["Group by fewer labels"])
     kw = {"match": p["match"]}
     if p["grp"] is not None:
         kw.update(grp=p["grp"][0], G=G)

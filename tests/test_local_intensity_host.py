@@ -178,17 +178,21 @@ def test_memory_need_arithmetic(monkeypatch):
     M = 10**6
     monkeypatch.setattr(mi, "_free_bytes", lambda e: 10_000 * M)
     d = "the details"
+
+    def steps(*args):
+        return mi._window_steps(eng, "local_intensity", *args, ["Group by fewer labels"])
+
     # whole: fixed + T x per_step must fit
-    assert ml._window_steps(eng, 10, 100, 500 * M, 5_000 * M, None, d) == 10
+    assert steps(10, 100, 500 * M, 5_000 * M, None, d) == 10
     with pytest.raises(marex_amd.TrackingError, match=r"local_intensity: needs 10\.001 GB of device memory, 10\.000 GB are free"):
-        ml._window_steps(eng, 10, 100, 500 * M, 5_001 * M, None, d)
+        steps(10, 100, 500 * M, 5_001 * M, None, d)
     # windows: fixed + one step must fit; "auto" takes what the accumulators leave of 15/16 of the free memory
-    assert ml._window_steps(eng, 10, 100, 500 * M, 9_500 * M, 4, d) == 4
+    assert steps(10, 100, 500 * M, 9_500 * M, 4, d) == 4
     with pytest.raises(marex_amd.TrackingError, match=r"local_intensity: needs 10\.001 GB"):
-        ml._window_steps(eng, 10, 100, 500 * M, 9_501 * M, 4, d)
-    assert ml._window_steps(eng, 10, 100, 500 * M, 5_000 * M, "auto", d) == (10_000 - 625 - 5_000) // 500 == 8
-    assert ml._window_steps(eng, 10, 100, 500 * M, 9_400 * M, "auto", d) == 1
-    assert ml._window_steps(eng, 10, 100, 0, 9_400 * M, "auto", d) == 10  # resident inputs: nothing to upload
+        steps(10, 100, 500 * M, 9_501 * M, 4, d)
+    assert steps(10, 100, 500 * M, 5_000 * M, "auto", d) == (10_000 - 625 - 5_000) // 500 == 8
+    assert steps(10, 100, 500 * M, 9_400 * M, "auto", d) == 1
+    assert steps(10, 100, 0, 9_400 * M, "auto", d) == 10  # resident inputs: nothing to upload
 
 
 @pytest.fixture
