@@ -843,6 +843,54 @@ int marex_trend_stats_f64(marex_ctx* ctx, const double* y, const double* x, int 
 int marex_trend_select_f64(marex_ctx* ctx, const double* y, const double* x, int G, int64_t C, const int32_t* ranks, int K,
                            double* out, int64_t* status);
 
+/* Per-(timestep, region) series of an event mask or a tracked ID field: the area in an extreme state, its cells, the
+ * weighted anomaly sums, the largest anomaly and the severity categories of every region at every step (the reference
+ * leaves them to notebook code: (extreme_events * cell_area).where(basin).sum over space; Hobday et al. 2018, Fig. 3).
+ *
+ * marex_regional_series_u8 / marex_regional_series_i32: x uint8 / int32 [Tb][C] are the rows t0 .. t0 + Tb - 1 of a [T][C]
+ *   field, T = T_slots >= t0 + Tb.  A cell is present when x > 0 (match == 0) or when x == match (match > 0); a negative
+ *   int32 cell is never present and adds one to status[0].  reg int32 [C]: the region of every cell; a value outside
+ *   0 .. R - 1 belongs to no region and adds nothing anywhere.  Slot (t, r) of the global step t = t0 + row is t * R + r.
+ *   q int64 [C], or NULL: the fixed-point areas (row 0 of the mesh tracker's weight tables: rint(a 2^e), their sum below
+ *   2^62); NULL means 1 per cell, and no weights are loaded.  wf float32 [C], or NULL for 1: the weights of the anomaly
+ *   sums (needs anom).  anom float32 [Tb][C] with sums and vmax, or all three NULL.  thr float32 [n_doy][C] with doy int32
+ *   [T] (the row of thr of every global step, must reach t0 + Tb) and cat_cnt, or all three NULL (they need anom);
+ *   cat_area exactly with thr and q.
+ *   Per present cell c of region r at step t:
+ *     without anom: area[t][r] += q[c] (int64 [T][R]), cnt[t][r][0] += 1 (uint64 [T][R][2]);
+ *     with a finite anomaly a: the same two, sums[t][r][0] += (double)wf[c], sums[t][r][1] += (double)wf[c] * (double)a (an
+ *     exact product; float64 [T][R][2]), vmax[t][r] = max(vmax[t][r], key(a)) (uint32 [T][R]; the key of
+ *     marex_event_intensity_f32, 0: no finite cell), and with thr the class k of marex_local_intensity_* under h =
+ *     thr[doy[t]][c]: cat_cnt[t][r][k] += 1 (uint64 [T][R][6]), cat_area[t][r][k] += q[c] (int64 [T][R][6]);
+ *     with an anomaly that is NaN or +-inf: cnt[t][r][1] += 1 and nothing else -- area and cnt[0] count the same cells.
+ *   Under a row whose doy label lies outside 0 .. n_doy - 1 nothing is addressed: its present cells of a region add to
+ *   status[1] and to nothing else.  status uint64 [2].  The functions only add: the caller zeroes area, cnt, sums, vmax,
+ *   cat_cnt, cat_area and status before the first window, and walks a record in any sequence of windows into them.
+ *   anom is fetched only under present cells of a region, thr, wf and q only under those of them with a finite anomaly.
+ *   Arithmetic: every count and every area is an integer, exact and independent of the order of execution, of the windows
+ *   and of the layout below.  sums follows the contract of marex_event_intensity_f32: exact terms, summed in registers,
+ *   over the wave, through LDS and by atomic adds in no fixed order; bit for bit reproducible whenever the partial sums are
+ *   exactly representable, otherwise within 2 n u sum|w a| of the exact sum (n the finite cells of the slot, u = 2^-53).
+ *   Layout: a workgroup of 256 lanes takes 4096 consecutive cells (four per lane and pass; uint8 without thr, with C % 4 == 0, x 4-byte
+ *   and anom, wf and q 16-byte aligned) or 2048 (one per lane and pass), a wave a quarter of them, and every 32nd
+ *   row; same results either way.
+ *   -1: null x, reg, area, cnt or status, empty shape, t0 < 0, T_slots < t0 + Tb, match < 0, R <= 0, anom / sums / vmax or
+ *   thr / doy / cat_cnt given in part, wf or thr without anom, n_doy <= 0 with thr, cat_area without thr and q or missing
+ *   with both; -4: C or t0 + Tb of 2^31 - 1 or more (the field itself may hold any number of cells: it is addressed with
+ *   64-bit offsets).  Asynchronous on the context's stream. */
+int marex_regional_series_u8(marex_ctx* ctx, const uint8_t* x, int64_t t0, int64_t Tb, int64_t C, int64_t T_slots, int match,
+                             const int32_t* reg, int R, const int64_t* q, const float* wf, const float* anom, const float* thr,
+                             const int32_t* doy, int n_doy, int64_t* area, uint64_t* cnt, double* sums, uint32_t* vmax,
+                             uint64_t* cat_cnt, int64_t* cat_area, uint64_t* status);
+int marex_regional_series_i32(marex_ctx* ctx, const int32_t* x, int64_t t0, int64_t Tb, int64_t C, int64_t T_slots, int match,
+                              const int32_t* reg, int R, const int64_t* q, const float* wf, const float* anom, const float* thr,
+                              const int32_t* doy, int n_doy, int64_t* area, uint64_t* cnt, double* sums, uint32_t* vmax,
+                              uint64_t* cat_cnt, int64_t* cat_area, uint64_t* status);
+/* marex_regional_layout: what the kernels of marex_regional_series_* are compiled with, for cells_per_lane 4 or 1: out
+ *   int32 [3] (host) = cells of a wave per row, cells of a workgroup per row, rows between two of a workgroup's.  -1: null
+ *   out or another cells_per_lane.  Needs no context and no device. */
+int marex_regional_layout(int cells_per_lane, int32_t* out);
+
 /* The partition kernels of the split-and-merge stage on an unstructured mesh (tracker.split_and_merge_objects_parallel,
  * marEx/track.py:3804-4814, 5246-5419).  A slice is int32 [C], values <= 0 are background, C below 2^31 - 1.  u: float64
  * [3][C], the unit vectors of the cells; pv: float64 [3][n], the unit vectors of the parents' centroids.  "Nearest" is the

@@ -11,6 +11,8 @@ categories (Hobday et al. 2018) of every tracked event and the category map of e
 ``dat_anomaly`` and ``thresholds`` on the device.  ``compound_events`` joins two presence fields in one pass on the device:
 joint, lagged and run-level coincidence per cell, by time group and by latitude class.  ``cell_trends`` gives the per-cell
 trend of a series of annual maps -- Theil-Sen slope with confidence bounds, Mann-Kendall test, least squares -- on the device.
+``regional_series`` gives, per timestep and region of any integer region map, the area in an extreme state as an exact
+integer sum of fixed-point cell areas, its share of the region, the area-weighted intensity and the severity categories.
 """
 from .detect import (
     compute_normalised_anomaly,
@@ -36,6 +38,7 @@ from .local_intensity import local_intensity
 from .cell_events import cell_events
 from .compound import compound_events
 from .trends import cell_trends
+from .regional import regional_series
 from .track import tracker
 from .xr_compat import DataArray, Dataset
 
@@ -44,6 +47,6 @@ __all__ = [
     "smoothed_rolling_climatology", "MarExError", "DataValidationError", "ConfigurationError",
     "ProcessingError", "DependencyError", "create_data_validation_error", "DataArray", "Dataset",
     "tracker", "TrackingError", "event_intensity", "event_occurrence", "local_intensity",
-    "cell_events", "event_categories", "compound_events", "cell_trends",
+    "cell_events", "event_categories", "compound_events", "cell_trends", "regional_series",
 ]
 __version__ = "0.1.0"

@@ -1834,6 +1834,113 @@ class HotPath:
                    cat_days=host(acc["cat_days"], np.uint32), sec_cnt=host(acc["sec_cnt"], np.uint64))
         return out
 
+    #: the most regions of :meth:`regional_series`
+    REGIONAL_MAX_REGIONS = 32767
+
+    @staticmethod
+    def regional_layout(cells_per_lane: int) -> Tuple[int, int, int]:
+        """``(cells of a wave per row, cells of a workgroup per row, rows between two of a workgroup's)`` of the kernels of
+        ``marex_regional_series_*``, as the library was compiled (``marex_regional_layout``): at four cells per lane (a
+        uint8 field without thresholds, ``C % 4 == 0``, aligned arrays) and at one.  Needs no device."""
+        out = (C.c_int32 * 3)()
+        if _lib.load().marex_regional_layout(int(cells_per_lane), out) != 0:
+            raise ProcessingError(f"regional_layout: cells_per_lane must be 1 or 4, got {cells_per_lane}")
+        return int(out[0]), int(out[1]), int(out[2])
+
+    @staticmethod
+    def regional_slot_bytes(T: int, R: int, anomalies: bool, categories: bool, areas: bool) -> int:
+        """The bytes of the ``T x R`` slots of :meth:`regional_series` and of their spare row: area and two counts (24 per
+        slot), with anomalies two sums and the maximum's key (24, the key padded to 8), with thresholds six counts (48)
+        and, with areas, six areas (48)."""
+        per = 24 + (24 if anomalies else 0) + (48 if categories else 0) + (48 if categories and areas else 0)
+        return (int(T) + 1) * int(R) * per
+
+    def regional_series(self, x: torch.Tensor, reg, R: int, T: int, t0: int = 0, q=None, wf=None,
+                        anom: Optional[torch.Tensor] = None, thr: Optional[torch.Tensor] = None, doy=None, match: int = 0,
+                        acc: Optional[dict] = None, finish: bool = True) -> Dict[str, object]:
+        """Per (timestep, region) series of the rows ``t0 .. t0 + Tb - 1`` of a ``[T, C]`` mask or ID field
+        (``marex_regional_series_u8`` / ``marex_regional_series_i32``): ``x`` uint8, bool (read as uint8) or int32
+        ``[Tb, C]`` (present where ``x > 0``, or where ``x == match``).  ``reg`` (int ``[C]``): the region of every cell,
+        outside ``0 .. R - 1``: none.  ``q`` (int64 ``[C]``, the fixed-point areas of ``track_mesh.mesh_weight_tables`` row
+        0; None: 1 per cell) and ``wf`` (float32 ``[C]``, the weights of the anomaly sums, needs ``anom``; None: 1) are host
+        arrays.  ``anom`` float32 ``[Tb, C]`` adds the sums and the maximum; ``thr`` (float32 ``[n_doy, C]`` on the device)
+        with ``doy`` (int ``[T]``, the row of ``thr`` of every global step) the categories, which need ``anom``.  The first
+        window allocates the ``T x R`` slots (and one spare row of them that nothing addresses), zeroes them and uploads
+        the tables; a later window passes the ``"acc"`` entry of the previous result -- the window lengths do not matter.
+        Returns ``acc`` and -- unless ``finish`` is False, which defers them and the one host read -- ``area`` int64
+        ``[T, R]`` (the sum of ``q``, or the cells), ``cnt`` int64 ``[T, R, 2]`` (cells counted in ``area``; present cells
+        with a non-finite anomaly, which count for nothing else), ``sums`` float64 ``[T, R, 2]`` (sum of ``wf``, sum of
+        ``wf`` x anomaly), ``vmax`` float32 ``[T, R]`` (NaN: none), ``cat_cnt`` int64 ``[T, R, 6]`` and ``cat_area`` int64
+        ``[T, R, 6]`` (None without anomalies / thresholds / ``q``).  A negative ID raises the trackers' "Object IDs must be
+        non-negative" error, a ``doy`` label outside its range a :class:`ProcessingError`; both were counted, nothing was
+        written out of range."""
+        x, Tb, Cn = self._presence_window("regional_series", x)
+        t0, R, T, match = int(t0), int(R), int(T), int(match)
+        cats = thr is not None or doy is not None
+        if t0 < 0 or T < t0 + Tb or R <= 0 or R > self.REGIONAL_MAX_REGIONS or match < 0 or match > 2**31 - 1:
+            raise ProcessingError(f"regional_series: t0 and match must not be negative, the window must end inside the {T} steps "
+                                  f"of the slots, and R must lie in 1 .. {self.REGIONAL_MAX_REGIONS}",
+                                  details=f"t0 = {t0}, Tb = {Tb}, R = {R}, match = {match}")
+        if anom is None and (wf is not None or cats):
+            raise ProcessingError("regional_series: weights and thresholds need the anomalies")
+        if anom is not None:
+            self._anomaly_window_check("regional_series", anom, Tb, Cn)
+        if cats:
+            self._thresholds_check("regional_series", thr, doy, Cn, f"the categories need thresholds, a contiguous float32 "
+                                   f"[n_doy, {Cn}] tensor on the engine's device, and the row of every step")
+        n_doy = int(thr.shape[0]) if cats else 0
+        plan = (T, R, Cn, n_doy, match, q is not None, wf is not None, anom is not None)
+        if acc is None:
+            tabs = label_tables("regional_series", (("reg", reg, Cn), ("doy", doy if cats else None, None)))
+            qh = wh = None
+            if q is not None:
+                qh = np.ascontiguousarray(q)
+                if qh.dtype != np.int64 or qh.shape != (Cn,) or (qh < 0).any() or int(qh.max()) >= 2**62 or \
+                        (int((qh >> 32).sum()) << 32) + int((qh & 0xFFFFFFFF).sum()) >= 2**62:  # the exact sum, in halves
+                    raise ProcessingError(f"regional_series: q must be {Cn} non-negative int64 areas whose sum stays below 2^62",
+                                          details=f"got {qh.dtype} {qh.shape}")
+            if wf is not None:
+                wh = np.ascontiguousarray(wf)
+                if wh.dtype != np.float32 or wh.shape != (Cn,):
+                    raise ProcessingError(f"regional_series: wf must be {Cn} float32 weights", details=f"got {wh.dtype} {wh.shape}")
+            slots_b = self.regional_slot_bytes(T, R, anom is not None, cats, q is not None)
+            self._check_fits(slots_b + 16 + self._table_bytes(tabs) + (8 * Cn if q is not None else 0) +
+                             (4 * Cn if wf is not None else 0), "regional series",
+                             f"{T} x {R} (timestep, region) slots of {slots_b // ((T + 1) * R)} bytes, the region of every cell"
+                             f"{', its area' if q is not None else ''}{', its weight' if wf is not None else ''} and the label tables")
+
+            def slots(name, tail, dtype):  # T rows that the kernel adds into, one more that it must leave alone
+                b = self._buf(None, name, (T + 1, R) + tail, dtype, self.device)
+                b[:T].zero_()
+                return b
+
+            acc = {"area": slots("reg_area", (), torch.int64), "cnt": slots("reg_cnt", (2,), torch.int64),
+                   "sums": slots("reg_sums", (2,), torch.float64) if anom is not None else None,
+                   "vmax": slots("reg_vmax", (), torch.int32) if anom is not None else None,
+                   "cat_cnt": slots("reg_cat_cnt", (6,), torch.int64) if cats else None,
+                   "cat_area": slots("reg_cat_area", (6,), torch.int64) if cats and q is not None else None,
+                   "status": self._zeros("reg_status", (2,), torch.int64), "plan": plan,
+                   "q": None if qh is None else self._dev(qh), "wf": None if wh is None else self._dev(wh),
+                   **self._upload_tables(tabs)}
+        self._window_check("regional_series", acc, plan, ("doy",), t0, Tb, Cn)
+        fn = "marex_regional_series_i32" if x.dtype == torch.int32 else "marex_regional_series_u8"
+        tb = acc["tabs"]
+        self.call(fn, x, t0, Tb, Cn, T, match, tb["reg"], R, acc["q"], acc["wf"], anom, thr if cats else None, tb["doy"], n_doy,
+                  acc["area"], acc["cnt"], acc["sums"], acc["vmax"], acc["cat_cnt"], acc["cat_area"], acc["status"])
+        out: Dict[str, object] = {"acc": acc}
+        if not finish:
+            return out
+        self._stream_status("regional_series", acc, 1, f"doy must hold 0 .. {n_doy - 1}")
+
+        def host(name, dt):
+            return None if acc[name] is None else acc[name][:T].cpu().numpy().view(dt)
+
+        key = host("vmax", np.uint32)
+        out.update(area=host("area", np.int64), cnt=host("cnt", np.int64), sums=host("sums", np.float64),
+                   vmax=None if key is None else self._key_max(key), cat_cnt=host("cat_cnt", np.int64),
+                   cat_area=host("cat_area", np.int64))
+        return out
+
     def cell_event_records(self, acc: dict) -> Dict[str, object]:
         """The record buffers of a second pass of :meth:`cell_events`, from the accumulators of a finished summary pass:
         ``off`` int64 ``[C + 1]`` (the exclusive scan of the events per cell, summed over the groups, on the device), ``n``

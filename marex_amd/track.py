@@ -983,6 +983,36 @@ class tracker(_MeshStages):  # noqa: N801 -- the reference's public name (marEx.
         field = events_or_field["ID_field"] if hasattr(events_or_field, "data_vars") else events_or_field
         return local_intensity(field, extremes_ds["dat_anomaly"], **kw)
 
+    def regional_series(self, events_or_field, extremes_ds=None, regions=None, **kw):
+        """Area, intensity and severity categories per region and timestep
+        (:func:`marex_amd.regional.regional_series` has the arguments and the variables) on this tracker's device:
+        ``events_or_field`` is the events Dataset of :meth:`run` (its ``ID_field`` is taken) or a presence field such as
+        ``extremes_ds["extreme_events"]``.  With ``extremes_ds``, the Dataset of ``preprocess_data``, ``dat_anomaly`` and,
+        unless ``thresholds`` is passed, ``thresholds`` come from it.  The time dimension and coordinate of the result are
+        the tracker's.  Unless passed, ``mask`` is the tracker's mask and ``cell_areas`` its areas: on a mesh its
+        ``cell_areas``; on a grid the float32 cell areas of the merge tracker's area pass, which exist only with
+        ``allow_merging=True`` and ``cell_areas`` or ``grid_resolution`` -- a grid tracker built with
+        ``allow_merging=False``, like one built without areas, gives ``area`` in cells (as :meth:`event_intensity`
+        weighs by cells then): pass ``cell_areas=`` here for areas."""
+        from .regional import _regional_series
+
+        kw.setdefault("device", self.device)
+        if extremes_ds is not None:
+            kw.setdefault("dat_anomaly", extremes_ds["dat_anomaly"])
+            if "thresholds" not in kw and "thresholds" in extremes_ds:
+                kw["thresholds"] = extremes_ds["thresholds"]
+        if "mask" not in kw:
+            m = getattr(self, "_mask_host", None)
+            kw["mask"] = m if m is not None else getattr(self, "mask", None)
+        if "cell_areas" not in kw:
+            kw["cell_areas"] = np.asarray(_host(self.cell_area)) if self.unstructured_grid else getattr(self, "_cell_weights", None)
+        field = events_or_field["ID_field"] if hasattr(events_or_field, "data_vars") else events_or_field
+        args = {k: kw.pop(k, None) for k in ("cell_areas", "dat_anomaly", "thresholds", "mask", "by", "event_id", "block_steps",
+                                             "device")}
+        if kw:
+            raise TypeError(f"regional_series() got an unexpected keyword argument {next(iter(kw))!r}")
+        return _regional_series(field, regions, time=(self.timedim, self.timecoord, self.time_values), **args)
+
     def _latlon_coords(self) -> dict:
         """The input's lat / lon as coordinate entries ``name -> (dims, host values)``."""
         ydim = self.xdim if self.unstructured_grid else self.ydim  # on a mesh lat runs over the cells too
