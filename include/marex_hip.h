@@ -815,6 +815,38 @@ int marex_compound_u8(marex_ctx* ctx, const uint8_t* a, const uint8_t* b, int64_
                       uint32_t* state, uint32_t* cell_cnt, uint32_t* lag_cnt, uint64_t* sec_cnt, uint8_t* mask,
                       uint64_t* status);
 
+/* Lagged composites (superposed-epoch analysis) of a float field around the onsets or the ends of the events of a presence
+ * field: what another variable did before, during and after the events of a cell (the driver studies that follow Hobday et
+ * al. 2016, 2018; the reference leaves it to host loops over cells).
+ *
+ * marex_event_composites_u8: x uint8 and v float32, both [Tr][C], are the rows r0 .. r0 + Tr - 1 of a record of T steps; a
+ *   cell is present where the byte of x is not 0.  An event of a cell is a maximal run of consecutive present steps.  With
+ *   anchor == 0 the anchors of a cell are its onsets, the steps s > 0 with x[s] and not x[s - 1]; with anchor == 1 its ends,
+ *   the steps e < T - 1 with x[e] and not x[e + 1].  A run that touches step 0 has no onset and one that touches step T - 1
+ *   no end: its true date is unknown, so it is censored.  The call handles the anchors at the steps a .. b - 1; with
+ *   L = max_lag (0 .. 30) and H = max(L, 1) the rows must cover max(0, a - H) .. min(T, b + H) - 1.  The rows outside
+ *   a .. b - 1 are read but own no anchors: they stand in the place of a carried state, and the accumulators are the only
+ *   thing a call continues.  a == b does nothing (and needs no rows).
+ *   Per anchor t of cell c under the label g = grp[t] (grp int32 [T], indexed by the global step; NULL with G == 1: every
+ *   step is group 0): anchors[g][c] += 1 (uint32 [G][C]), and for every lag l = -L .. L whose step t + l lies in 0 .. T - 1
+ *   and whose value a = v[t + l][c] is finite (neither NaN nor +-inf), at j = l + L: cnt[g][c][j] += 1,
+ *   sum[g][c][j] += (double)a, sumsq[g][c][j] += (double)a * (double)a.  cnt uint32, sum and sumsq float64, all
+ *   [G][C][2 L + 1]: cell-major, the lags of a cell are contiguous.  An anchor under a label outside 0 .. G - 1 addresses
+ *   nothing and adds 1 to status[0] (uint64 [1]).  The function only continues anchors, sum, sumsq, cnt and status: the
+ *   caller zeroes them before the first window.
+ *   Arithmetic: for each (group, cell, lag) the terms are added in ascending anchor step by sequential float64 additions;
+ *   the product of two float32 values is exact in float64, so the square carries no rounding of its own.  The counts are
+ *   exact integers.  No result depends on the windows or on the layout: a wave owns 64 consecutive cells, finds their
+ *   anchors row by row with a ballot, and for every anchor its lanes become the lags (one plain read-modify-write per lane);
+ *   only the owning wave touches a cell's accumulators, in time order.  No atomic touches a per-cell output.
+ *   -1, with nothing launched: null x, v, anchors, sum, sumsq, cnt or status, C <= 0, G <= 0, NULL grp with G != 1, max_lag
+ *   outside 0 .. 30, anchor outside 0 .. 1, not (0 <= r0, 0 <= Tr, r0 + Tr <= T and 0 <= a <= b <= T), rows that do not cover
+ *   the halo, a pointer not aligned to its element; -4: C or T of 2^31 - 1 or more (the fields themselves may hold any
+ *   number of cells: rows are addressed with 64-bit offsets).  Asynchronous on the context's stream. */
+int marex_event_composites_u8(marex_ctx* ctx, const uint8_t* x, const float* v, int64_t r0, int64_t Tr, int64_t a, int64_t b,
+                              int64_t T, int64_t C, int max_lag, int anchor, const int32_t* grp, int G, uint32_t* anchors,
+                              double* sum, double* sumsq, uint32_t* cnt, uint64_t* status);
+
 /* Per-cell trends of a short series of maps: y float64 [G][C], the G maps of C cells (2 <= G <= 256, C below 2^31 - 1),
  * x float64 [G] their finite, strictly increasing abscissae (the caller checks that).  A sample that is not finite is a
  * missing sample of its cell; n is the number of valid ones and P = n (n - 1) / 2 the number of pairs i < j of them.  The

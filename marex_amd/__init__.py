@@ -13,6 +13,8 @@ joint, lagged and run-level coincidence per cell, by time group and by latitude 
 trend of a series of annual maps -- Theil-Sen slope with confidence bounds, Mann-Kendall test, least squares -- on the device.
 ``regional_series`` gives, per timestep and region of any integer region map, the area in an extreme state as an exact
 integer sum of fixed-point cell areas, its share of the region, the area-weighted intensity and the severity categories.
+``event_composites`` gives the lagged composites (superposed-epoch analysis) of any float field around the onsets or the ends
+of every cell's events: count, sum, sum of squares, mean, standard deviation and t statistic per lag, on the device.
 """
 from .detect import (
     compute_normalised_anomaly,
@@ -37,6 +39,7 @@ from .occurrence import event_occurrence
 from .local_intensity import local_intensity
 from .cell_events import cell_events
 from .compound import compound_events
+from .composites import event_composites
 from .trends import cell_trends
 from .regional import regional_series
 from .track import tracker
@@ -48,5 +51,6 @@ __all__ = [
     "ProcessingError", "DependencyError", "create_data_validation_error", "DataArray", "Dataset",
     "tracker", "TrackingError", "event_intensity", "event_occurrence", "local_intensity",
     "cell_events", "event_categories", "compound_events", "cell_trends", "regional_series",
+    "event_composites",
 ]
 __version__ = "0.1.0"

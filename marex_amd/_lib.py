@@ -125,6 +125,7 @@ PROTOTYPES = {
     "marex_occurrence_u8": (_i32, [_p, _p, _i64, _i64, _i64, _i32, _p, _i32, _p, _i32, _p, _i32, _p, _p, _p, _p]),
     "marex_occurrence_i32": (_i32, [_p, _p, _i64, _i64, _i64, _i32, _p, _i32, _p, _i32, _p, _i32, _p, _p, _p, _p]),
     "marex_compound_u8": (_i32, [_p, _p, _p, _i64, _i64, _i64, _i32, _i32, _p, _i32, _p, _i32, _p, _i32, _p, _p, _p, _p, _p, _p]),
+    "marex_event_composites_u8": (_i32, [_p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _p, _i32, _p, _p, _p, _p, _p]),
     "marex_trend_stats_f64": (_i32, [_p, _p, _p, _i32, _i64, _p, _p, _p, _p, _p, _p]),
     "marex_trend_select_f64": (_i32, [_p, _p, _p, _i32, _i64, _p, _i32, _p, _p]),
     "marex_local_intensity_u8": (_i32, [_p, _p, _p, _i64, _i64, _i64, _i32, _p, _i32, _p, _p, _i32, _p, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _p]),

@@ -93,7 +93,7 @@ def plan_field(field, what: str, partner=None, names=("field", "dat_anomaly"), p
     kind = _field_kind(field)
     kind_b = _field_kind(partner) if presence_partner and partner is not None else None
     if partner is not None and not presence_partner and _kind(partner) != "f":
-        raise create_data_validation_error("dat_anomaly must be a floating-point field",
+        raise create_data_validation_error(f"{pname} must be a floating-point field",
                                            details=f"Found dtype {_dtype_name(partner)}",
                                            data_info={"actual_dtype": _dtype_name(partner)})
     T, C = shape[0], int(np.prod(shape[1:]))

@@ -1717,6 +1717,77 @@ class HotPath:
                    sec_cnt=host(acc["sec_cnt"], np.uint64))
         return out
 
+    #: the largest ``max_lag`` of :meth:`event_composites`: the ``2 L + 1`` lags of an anchor are the lanes of one wave
+    COMPOSITES_MAX_LAG = 30
+    #: ``anchor`` of :meth:`event_composites` as the library takes it
+    COMPOSITES_ANCHORS = {"onset": 0, "end": 1}
+
+    @staticmethod
+    def composites_rows(a: int, b: int, T: int, max_lag: int) -> Tuple[int, int]:
+        """``(first, end)`` of the rows that the anchors at the steps ``a .. b - 1`` need: ``H = max(max_lag, 1)`` steps of
+        halo on both sides, inside the record."""
+        H = max(int(max_lag), 1)
+        return max(0, a - H), min(T, b + H)
+
+    def event_composites(self, x: torch.Tensor, v: torch.Tensor, r0: int, a: int, b: int, T: int, max_lag: int = 10,
+                         anchor: str = "onset", grp=None, G: int = 1, acc: Optional[dict] = None,
+                         finish: bool = True) -> Dict[str, object]:
+        """Lagged composites of ``v`` around the anchors at the steps ``a .. b - 1`` (``marex_event_composites_u8``): ``x``
+        uint8 or bool (read as uint8) and ``v`` float32, both ``[Tr, C]``, are the rows ``r0 .. r0 + Tr - 1`` of a record of
+        ``T`` steps and must cover :meth:`composites_rows` -- the halo is read but owns no anchors, nothing else is carried
+        between windows.  ``anchor``: ``"onset"`` (a step ``s > 0`` with ``x[s]`` and not ``x[s - 1]``) or ``"end"`` (a step
+        ``e < T - 1`` with ``x[e]`` and not ``x[e + 1]``); ``max_lag``: ``0 .. 30``; ``grp`` (int ``[T]``, global steps, or
+        None with ``G == 1``) labels the anchors by their own step.  The first window allocates zeroed accumulators and
+        uploads the labels; a later window passes the ``"acc"`` entry of the previous result -- the windows do not matter,
+        not even to the last bit of the sums.  Returns ``acc`` and -- unless ``finish`` is False, which defers them and the
+        one host read -- ``anchors`` uint32 ``[G, C]``, ``count`` uint32, ``sum`` and ``sumsq`` float64 ``[G, 2 L + 1, C]``
+        (the device holds them cell-major, ``[G, C, 2 L + 1]``).  An anchor under a label outside ``0 .. G - 1`` raises
+        :class:`ProcessingError`; it was counted, nothing was written out of range."""
+        what = "event_composites"
+        x, Tr, Cn = self._presence_window(what, x)
+        if x.dtype != torch.uint8:
+            raise ProcessingError(f"{what}: the field must be a uint8 or bool window", details=f"got {x.dtype} {tuple(x.shape)}")
+        self._anomaly_window_check(what, v, Tr, Cn)
+        ints = (r0, a, b, T, max_lag, G)
+        if any(isinstance(k, bool) or not isinstance(k, (int, np.integer)) for k in ints):
+            raise ProcessingError(f"{what}: r0, a, b, T, max_lag and G must be integers", details=f"got {ints}")
+        r0, a, b, T, L, G = (int(k) for k in ints)
+        if not isinstance(anchor, str) or anchor not in self.COMPOSITES_ANCHORS or not 0 <= L <= self.COMPOSITES_MAX_LAG or G <= 0 or (grp is None and G != 1):
+            raise ProcessingError(f"{what}: anchor must be 'onset' or 'end', max_lag must lie in 0 .. {self.COMPOSITES_MAX_LAG}, "
+                                  "G must be positive, and G > 1 needs labels",
+                                  details=f"anchor = {anchor!r}, max_lag = {L}, G = {G}, labels {'given' if grp is not None else 'missing'}")
+        if not (0 <= r0 and r0 + Tr <= T and 0 <= a < b <= T):
+            raise ProcessingError(f"{what}: needs 0 <= r0, r0 + Tr <= T and 0 <= a < b <= T",
+                                  details=f"r0 = {r0}, Tr = {Tr}, a = {a}, b = {b}, T = {T}")
+        lo, hi = self.composites_rows(a, b, T, L)
+        if r0 > lo or r0 + Tr < hi:
+            raise ProcessingError(f"{what}: the rows {r0} .. {r0 + Tr - 1} do not cover the halo of the steps {a} .. {b - 1}",
+                                  details=f"with max_lag = {L} they must cover {lo} .. {hi - 1}")
+        W = 2 * L + 1
+        plan = (G, Cn, L, anchor, T)
+        if acc is None:
+            tabs = label_tables(what, (("grp", grp, None),))
+            need = G * Cn * (4 + 20 * W) + 8 + self._table_bytes(tabs)
+            self._check_fits(need, what, f"{G} x {Cn} cells of 4 + 20 x {W} bytes (anchors; count, sum and sum of squares of "
+                                         f"{W} lags), and the label table")
+            acc = {"anchors": self._zeros("cps_anchors", (G, Cn), torch.int32), "cnt": self._zeros("cps_cnt", (G, Cn, W), torch.int32),
+                   "sum": self._zeros("cps_sum", (G, Cn, W), torch.float64), "sumsq": self._zeros("cps_sumsq", (G, Cn, W), torch.float64),
+                   "status": self._zeros("cps_status", (1,), torch.int64), "plan": plan, **self._upload_tables(tabs)}
+        self._window_check(what, acc, plan, ("grp",), 0, T, Cn)
+        self.call("marex_event_composites_u8", x, v, r0, Tr, a, b, T, Cn, L, self.COMPOSITES_ANCHORS[anchor], acc["tabs"]["grp"],
+                  G, acc["anchors"], acc["sum"], acc["sumsq"], acc["cnt"], acc["status"])
+        out: Dict[str, object] = {"acc": acc}
+        if not finish:
+            return out
+        lost = int(acc["status"].cpu().numpy()[0])
+        if lost:
+            raise ProcessingError(f"{what}: {lost} anchors lie under a step label outside its range",
+                                  details=f"grp must hold 0 .. {G - 1}; the anchors were counted, nothing was written out of range")
+        lags_first = lambda t, dt: np.ascontiguousarray(self._host(t, dt).transpose(0, 2, 1))  # noqa: E731
+        out.update(anchors=self._host(acc["anchors"], np.uint32), count=lags_first(acc["cnt"], np.uint32),
+                   sum=lags_first(acc["sum"], np.float64), sumsq=lags_first(acc["sumsq"], np.float64))
+        return out
+
     #: the longest series :meth:`trend_stats` and :meth:`trend_select` take (include/marex_hip.h)
     TREND_MAX_STEPS = 256
 

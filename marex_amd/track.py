@@ -983,6 +983,17 @@ class tracker(_MeshStages):  # noqa: N801 -- the reference's public name (marEx.
         field = events_or_field["ID_field"] if hasattr(events_or_field, "data_vars") else events_or_field
         return local_intensity(field, extremes_ds["dat_anomaly"], **kw)
 
+    def event_composites(self, events_or_field, values, **kw):
+        """Lagged composites of ``values`` around event onsets or ends
+        (:func:`marex_amd.composites.event_composites` has the arguments and the variables) on this tracker's device:
+        ``events_or_field`` is the events Dataset of :meth:`run` (its ``ID_field`` is taken) or a presence field such as
+        ``extremes_ds["extreme_events"]``."""
+        from .composites import event_composites
+
+        kw.setdefault("device", self.device)
+        field = events_or_field["ID_field"] if hasattr(events_or_field, "data_vars") else events_or_field
+        return event_composites(field, values, **kw)
+
     def regional_series(self, events_or_field, extremes_ds=None, regions=None, **kw):
         """Area, intensity and severity categories per region and timestep
         (:func:`marex_amd.regional.regional_series` has the arguments and the variables) on this tracker's device:
