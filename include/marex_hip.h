@@ -629,6 +629,40 @@ int marex_event_intensity_f32(marex_ctx* ctx, const int32_t* ids, const float* a
                               int n_ev, const int32_t* ev_tmin, const int64_t* ev_off, int64_t n_slots, const float* w,
                               uint64_t* cnt, double* sums, uint32_t* vmax, uint64_t* status);
 
+/* Shape of tracked events on a grid: per (timestep, event) the integer sums behind extent, perimeter, axes and centroid paths
+ * (the reference hands such properties to regionprops_table; the side-count perimeter and the orientation convention are
+ * this project's own).
+ *
+ * marex_event_shapes_i32: ids int32 [Tb][ny * nx] are the rows t0 .. t0 + Tb - 1 of a gridded field, cell (y, x) at y * nx + x;
+ *   values outside 1 .. n_ev are background.  n_ev, ev_tmin, ev_off, n_slots and the slot s of a cell as in
+ *   marex_event_intensity_f32.  regional != 0: the columns left of 0 and right of nx - 1 are domain border; otherwise x is
+ *   periodic (with nx = 1 a cell is its own east and west neighbour).  The rows above 0 and below ny - 1 are always border.
+ *   A side of an event cell is exposed when the neighbour across it holds a different value (0 included) or lies outside the
+ *   domain; each of the four sides is tested on its own.
+ *   mom uint64 [n_slots][16], per cell of the slot:
+ *     0 cells   1 sum y   2 sum x   3 cells with x > nx / 2   4 flags, OR-ed (1: a cell with x < 100, 2: one with x >= nx - 100)
+ *     5 sum y^2   6 sum x^2   7 sum x y   8 sum x over the cells with x > nx / 2   9 sum y over them
+ *     10 exposed sides facing north or south   11 facing east or west   12 exposed sides on the domain border
+ *     13 exposed sides whose neighbour is inside the domain and 0 in mask (uint8 [ny * nx], or NULL: none)
+ *     14 sum of the lengths of the exposed sides: ns_q[y] for a north side, ns_q[y + 1] for a south side, ew_q[y] for an
+ *        east or west side (ns_q int64 [ny + 1] and ew_q int64 [ny], given together, or both NULL: 0)
+ *     15 sum of area_q[y * nx + x] (int64 [ny * nx], or NULL: 0)
+ *   box int32 [n_slots][6]: min y, max y, min x and max x over the cells with x <= nx / 2, min x and max x over those with
+ *   x > nx / 2 (atomic minima and maxima; the caller fills the minima with INT_MAX and the maxima with -1 first).
+ *   status uint64 [1].  The function only accumulates: the caller prepares mom (zero), box and status before the first block,
+ *   so a field is walked in time blocks into the same slots; the stencil stays inside a slice, so blocks need no halo.  A cell
+ *   whose event lies outside its declared span adds one to status[0] and nothing else: no slot index that was not
+ *   range-checked addresses mom or box.  The four neighbours, the mask bytes and the table rows are fetched only under cells
+ *   of an event.  Every sum is an integer: exact, and independent of any order and of the blocks.
+ *   Bounds: with ny, nx <= 65536 and a slice below 2^31 cells, sum x^2 <= nx^2 n < 2^63 (sum y^2 likewise) and sum x y <
+ *   2^62; the caller scales the tables so that no sum of them reaches 2^62.
+ *   -1: null pointer, empty shape, t0 < 0, n_ev <= 0, n_slots <= 0, or ns_q / ew_q given in part; -4: ny or nx above 65536, or
+ *   ny * nx or t0 + Tb of 2^31 - 1 or more.  Asynchronous on the context's stream. */
+int marex_event_shapes_i32(marex_ctx* ctx, const int32_t* ids, int64_t t0, int64_t Tb, int ny, int nx, int regional, int n_ev,
+                           const int32_t* ev_tmin, const int64_t* ev_off, int64_t n_slots, const uint8_t* mask,
+                           const int64_t* area_q, const int64_t* ns_q, const int64_t* ew_q, uint64_t* mom, int32_t* box,
+                           uint64_t* status);
+
 /* Severity categories of tracked events (Hobday et al. 2018: moderate, strong, severe, extreme as multiples of the
  * threshold): the event field joined with the anomaly field and the day-of-year thresholds, per (timestep, event).
  *

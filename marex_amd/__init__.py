@@ -15,6 +15,10 @@ trend of a series of annual maps -- Theil-Sen slope with confidence bounds, Mann
 integer sum of fixed-point cell areas, its share of the region, the area-weighted intensity and the severity categories.
 ``event_composites`` gives the lagged composites (superposed-epoch analysis) of any float field around the onsets or the ends
 of every cell's events: count, sum, sum of squares, mean, standard deviation and t statistic per lag, on the device.
+``event_shapes`` and ``tracker.event_shapes`` give the shape and the movement of every tracked event on a grid: bounding box
+and extent, exposed sides, perimeter and coastal contact, the axes, eccentricity and orientation of its second moments, and
+the path, displacement and speed of its centroid -- integer sums on the device, float64 on the host; ``grid_edge_lengths``
+gives the side lengths of a regular lat-lon grid for perimeters in km.
 """
 from .detect import (
     compute_normalised_anomaly,
@@ -42,6 +46,7 @@ from .compound import compound_events
 from .composites import event_composites
 from .trends import cell_trends
 from .regional import regional_series
+from .shapes import event_shapes, grid_edge_lengths
 from .track import tracker
 from .xr_compat import DataArray, Dataset
 
@@ -51,6 +56,6 @@ __all__ = [
     "ProcessingError", "DependencyError", "create_data_validation_error", "DataArray", "Dataset",
     "tracker", "TrackingError", "event_intensity", "event_occurrence", "local_intensity",
     "cell_events", "event_categories", "compound_events", "cell_trends", "regional_series",
-    "event_composites",
+    "event_composites", "event_shapes", "grid_edge_lengths",
 ]
 __version__ = "0.1.0"

@@ -1545,6 +1545,54 @@ class HotPath:
                    vmax=key_float(acc["vmax"][:n_slots].cpu().numpy().view(np.uint32)))  # key 0: a NaN
         return out
 
+    def event_shapes(self, ids: torch.Tensor, ny: int, nx: int, ev_tmin, ev_tmax, regional: bool = False,
+                     mask: Optional[torch.Tensor] = None, area_q: Optional[torch.Tensor] = None,
+                     ns_q: Optional[torch.Tensor] = None, ew_q: Optional[torch.Tensor] = None, t0: int = 0,
+                     acc: Optional[dict] = None, finish: bool = True) -> Dict[str, object]:
+        """Per (timestep, event) shape sums of the rows ``t0 .. t0 + Tb - 1`` of a tracked, gridded field
+        (``marex_event_shapes_i32``): ``ids`` int32 ``[Tb, ny * nx]`` (events 1..n_ev, anything else background), the slots
+        declared by ``ev_tmin`` / ``ev_tmax`` as in :meth:`event_intensity`.  ``regional``: x is not periodic.  ``mask``:
+        uint8 ``[ny * nx]`` (0: land) or None; ``area_q``: int64 ``[ny * nx]`` fixed-point areas or None; ``ns_q`` int64
+        ``[ny + 1]`` and ``ew_q`` int64 ``[ny]``: fixed-point side lengths, together or None.  The first block allocates the
+        accumulators; a later block passes the ``"acc"`` entry of the previous result, whatever the block length.  Returns
+        ``off``, ``acc`` and -- unless ``finish`` is False -- ``mom`` int64 ``[n, 16]`` and ``box`` int32 ``[n, 6]`` (the
+        layout of include/marex_hip.h).  A cell of an event outside its declared span raises :class:`ProcessingError`."""
+        Tb, Cn = self._ids_check(ids)
+        ny, nx = int(ny), int(nx)
+        if Cn != ny * nx or ny <= 0 or nx <= 0:
+            raise ProcessingError(f"event_shapes: {Cn} cells per slice, ny * nx = {ny * nx}")
+        for name, v, dt, n in (("mask", mask, torch.uint8, Cn), ("area_q", area_q, torch.int64, Cn),
+                               ("ns_q", ns_q, torch.int64, ny + 1), ("ew_q", ew_q, torch.int64, ny)):
+            if v is not None and (v.dtype != dt or tuple(v.shape) != (n,) or not v.is_contiguous() or v.device != self.device):
+                raise ProcessingError(f"event_shapes: {name} must be a contiguous {dt} [{n}] tensor on the engine's device",
+                                      details=f"got {v.dtype} {tuple(v.shape)} on {v.device}")
+        if (ns_q is None) != (ew_q is None):
+            raise ProcessingError("event_shapes: ns_q and ew_q come together")
+        tmin_h, n_ev, t0, off, n_slots, alloc = self._event_slots("event_shapes", ev_tmin, ev_tmax, t0)
+        if acc is None:
+            self._check_fits(152 * n_slots + 12 * (n_ev + 2), "event shapes",
+                             f"{n_slots} (timestep, event) slots between each event's first and last timestep, 152 bytes each, "
+                             f"and the tables of {n_ev} events")
+            box = self._buf(None, "shp_box", (alloc, 6), torch.int32, self.device)
+            box[:, 0::2] = 2**31 - 1
+            box[:, 1::2] = -1
+            acc = {"mom": self._zeros("shp_mom", (alloc, 16), torch.int64), "box": box,
+                   "status": self._zeros("shp_status", (1,), torch.int64), **self._slot_tables(tmin_h, off)}
+        elif tuple(acc["mom"].shape) != (alloc, 16) or not np.array_equal(acc["plan"], off):
+            raise ProcessingError("event_shapes: the accumulators were planned for other spans",
+                                  details=f"{tuple(acc['mom'].shape)[0]} slots there, {alloc} here")
+        self.call("marex_event_shapes_i32", ids, t0, Tb, ny, nx, int(bool(regional)), n_ev, acc["tmin"], acc["off"], alloc,
+                  mask, area_q, ns_q, ew_q, acc["mom"], acc["box"], acc["status"])
+        out = {"off": off, "acc": acc}
+        if not finish:
+            return out
+        bad = int(acc["status"].item())
+        if bad:
+            raise ProcessingError(f"event_shapes: {bad} cells belong to an event outside its declared span of timesteps",
+                                  details="ev_tmin / ev_tmax do not cover the field; the cells were counted, not accumulated")
+        out.update(mom=acc["mom"][:n_slots].cpu().numpy(), box=acc["box"][:n_slots].cpu().numpy())
+        return out
+
     def event_categories(self, ids: torch.Tensor, anom: torch.Tensor, ev_tmin, ev_tmax, thr: torch.Tensor, doy,
                          weights: Optional[torch.Tensor] = None, t0: int = 0, field: Optional[torch.Tensor] = None,
                          acc: Optional[dict] = None, finish: bool = False) -> Dict[str, object]:

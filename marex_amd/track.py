@@ -994,6 +994,38 @@ class tracker(_MeshStages):  # noqa: N801 -- the reference's public name (marEx.
         field = events_or_field["ID_field"] if hasattr(events_or_field, "data_vars") else events_or_field
         return event_composites(field, values, **kw)
 
+    def event_shapes(self, events_ds, **kw):
+        """Shape and movement of the events of :meth:`run` (:func:`marex_amd.shapes.event_shapes` has the arguments and the
+        variables) from ``events_ds["ID_field"]``, on this tracker's device and under its time names.  Unless passed:
+        ``mask`` is the tracker's mask, ``regional_mode`` its own, ``cell_areas`` the float32 cell areas of the merge
+        tracker's area pass (cells without them) and ``lat`` / ``lon`` the 1-D coordinates of the tracked field in degrees,
+        so that the path of the centroid comes in km.  Gridded trackers only (:class:`ConfigurationError` on a mesh).  The
+        ``ID`` axis of a merge tracker's Dataset is checked against what the pass found (:class:`ProcessingError`)."""
+        from .shapes import _event_shapes
+
+        field = events_ds["ID_field"] if hasattr(events_ds, "data_vars") else events_ds
+        if self.unstructured_grid:
+            raise ConfigurationError("event_shapes: shapes are gridded only", details="this tracker works on an unstructured mesh")
+        if "mask" not in kw:
+            m = getattr(self, "_mask_host", None)
+            kw["mask"] = m if m is not None else getattr(self, "mask", None)
+        kw.setdefault("regional_mode", bool(self.regional_mode))
+        if "cell_areas" not in kw:
+            kw["cell_areas"] = getattr(self, "_cell_weights", None)
+        if "lat" not in kw and "lon" not in kw and len(field.shape) == 3:
+            la, lo = np.asarray(_host(self.lat_init)), np.asarray(_host(self.lon_init))
+            if la.shape == (int(field.shape[1]),) and lo.shape == (int(field.shape[2]),):
+                kw["lat"], kw["lon"] = la, lo
+        args = {k: kw.pop(k, d) for k, d in (("mask", None), ("cell_areas", None), ("edge_lengths", None), ("lat", None),
+                                             ("lon", None), ("regional_mode", False), ("per_timestep", True),
+                                             ("block_steps", None), ("device", self.device))}
+        if kw:
+            raise TypeError(f"event_shapes() got an unexpected keyword argument {next(iter(kw))!r}")
+        n = int(np.asarray(events_ds["ID"].values).size) if hasattr(events_ds, "data_vars") and "ID" in events_ds else None
+        return _event_shapes(field, args["mask"], args["cell_areas"], args["edge_lengths"], args["lat"], args["lon"],
+                             args["regional_mode"], args["per_timestep"], args["block_steps"], args["device"], n_events=n,
+                             time=(self.timedim, self.timecoord, self.time_values))
+
     def regional_series(self, events_or_field, extremes_ds=None, regions=None, **kw):
         """Area, intensity and severity categories per region and timestep
         (:func:`marex_amd.regional.regional_series` has the arguments and the variables) on this tracker's device:
