@@ -957,6 +957,41 @@ int marex_regional_series_i32(marex_ctx* ctx, const int32_t* x, int64_t t0, int6
  *   out or another cells_per_lane.  Needs no context and no device. */
 int marex_regional_layout(int cells_per_lane, int32_t* out);
 
+/* The join of tracked events with regions: per (timestep, region, event) the cells of the event in the region, their area,
+ * the weighted anomaly sums and the largest anomaly.  The result is sparse, so it is a keyed accumulation in an
+ * open-addressing table (the scheme of marex_overlap_count_i32 / marex_overlap_pairs_i32), not a dense slot array.
+ *
+ * Both functions take ids int32 [Tb][C], one window of a tracked field (a cell belongs to event ids > 0; a negative cell
+ * belongs to none), and reg int32 [C], the region rank of every cell: a value outside 0 .. R - 1 is "no region", which is
+ * accumulated under rank R.  The key of a cell is id << 33 | rank << 17 | row (31, 16 and 17 bits): as integers the keys
+ * sort by (id, rank, row).  Equal keys of consecutive cells of a row form a run.
+ *
+ * marex_event_exposure_count_i32: status uint64 [8] is zeroed, then status[0] = negative cells, status[2] = runs (an upper
+ *   bound of the distinct keys), status[4] = event cells.
+ * marex_event_exposure_i32: every run is added to the entry of its key in a table of cap entries (a power of two >= 64; the
+ *   caller chooses cap >= 2 runs), which the function zeroes: keys uint64 [cap] (0 = empty), cnt uint64 [cap] (the cells in
+ *   the low and the cells with a finite anomaly in the high 32 bits; without anom every cell is finite), area int64 [cap]
+ *   with q int64 [C] (the sum of the fixed-point areas q of the cells, all of them; NULL together: the area is the cells),
+ *   and with anom float32 [Tb][C]: sums double [cap][2] (the sum of w and of w * anom over the cells with a finite anomaly,
+ *   w = wf float32 [C] or 1 with wf NULL; exact products of doubles, added in no fixed order) and vmax uint32 [cap] (the
+ *   largest finite anomaly as an order-preserving key, 0: none).  anom, sums, vmax, out_sums and out_vmax come together or
+ *   not at all, q, area and out_area likewise.  A run that finds no entry within cap probes sets status[1] and is dropped:
+ *   nothing spins, nothing is written outside the table.  Then the occupied entries are copied, in no particular order, to
+ *   out_keys, out_cnt, out_area, out_sums [.][2] and out_vmax (out_cap entries each); status[3] = the occupied entries, of
+ *   which only the first out_cap are written.  status[0], [2] and [4] are left as the count pass set them.
+ * marex_event_exposure_layout: out int32 [7] (host) = the cells of a piece, of a wave and of a workgroup per row, the rows
+ *   between two of a workgroup's, and the bits of the id, the rank and the row in the key.  Needs no context and no device.
+ *
+ * -1: null pointer, empty shape, R outside 1 .. 32767, cap no power of two >= 64, out_cap <= 0, arguments given in part;
+ * -4: Tb above 2^17 or C of 2^31 - 1 or more.  Asynchronous on the context's stream. */
+int marex_event_exposure_count_i32(marex_ctx* ctx, const int32_t* ids, int64_t Tb, int64_t C, const int32_t* reg, int R,
+                                   uint64_t* status);
+int marex_event_exposure_i32(marex_ctx* ctx, const int32_t* ids, int64_t Tb, int64_t C, const int32_t* reg, int R,
+                             const int64_t* q, const float* wf, const float* anom, int64_t cap, uint64_t* keys, uint64_t* cnt,
+                             int64_t* area, double* sums, uint32_t* vmax, uint64_t* status, int64_t out_cap, uint64_t* out_keys,
+                             uint64_t* out_cnt, int64_t* out_area, double* out_sums, uint32_t* out_vmax);
+int marex_event_exposure_layout(int32_t* out);
+
 /* The partition kernels of the split-and-merge stage on an unstructured mesh (tracker.split_and_merge_objects_parallel,
  * marEx/track.py:3804-4814, 5246-5419).  A slice is int32 [C], values <= 0 are background, C below 2^31 - 1.  u: float64
  * [3][C], the unit vectors of the cells; pv: float64 [3][n], the unit vectors of the parents' centroids.  "Nearest" is the

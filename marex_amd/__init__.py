@@ -19,6 +19,9 @@ of every cell's events: count, sum, sum of squares, mean, standard deviation and
 and extent, exposed sides, perimeter and coastal contact, the axes, eccentricity and orientation of its second moments, and
 the path, displacement and speed of its centroid -- integer sums on the device, float64 on the host; ``grid_edge_lengths``
 gives the side lengths of a regular lat-lon grid for perimeters in km.
+``event_exposure`` and ``tracker.event_exposure`` join the tracked events with any integer region map: per (event, region)
+pair the steps, the cell-steps and area-steps, the largest extent and the intensity of the event inside the region, per
+event its main region and the share outside every region, per region the events it saw -- a keyed accumulation on the device.
 """
 from .detect import (
     compute_normalised_anomaly,
@@ -46,6 +49,7 @@ from .compound import compound_events
 from .composites import event_composites
 from .trends import cell_trends
 from .regional import regional_series
+from .exposure import event_exposure
 from .shapes import event_shapes, grid_edge_lengths
 from .track import tracker
 from .xr_compat import DataArray, Dataset
@@ -56,6 +60,6 @@ __all__ = [
     "ProcessingError", "DependencyError", "create_data_validation_error", "DataArray", "Dataset",
     "tracker", "TrackingError", "event_intensity", "event_occurrence", "local_intensity",
     "cell_events", "event_categories", "compound_events", "cell_trends", "regional_series",
-    "event_composites", "event_shapes", "grid_edge_lengths",
+    "event_composites", "event_shapes", "grid_edge_lengths", "event_exposure",
 ]
 __version__ = "0.1.0"

@@ -314,6 +314,48 @@ __device__ __forceinline__ T wave_sum(T v) {
     return v;
 }
 
+// The same sum, and a maximum, for kernels that reduce often (marex_regional.hip, marex_event_exposure.hip): inside the rows
+// of 16 lanes by DPP rotations (row_ror 8 / 4 / 2 / 1: after them every lane holds its row's result), across the four rows
+// by two shuffles, as wave_min_i32 does -- two LDS permutes per word where the butterfly takes six.  CTRL: the DPP control
+// word, 0x120 + n = row_ror n.  Every lane of the wave must be active.
+template <int CTRL, typename T>
+__device__ __forceinline__ T dpp_row_ror(T v) {
+    if constexpr (sizeof(T) == 4) {
+        const int u = __builtin_bit_cast(int, v);
+        return __builtin_bit_cast(T, __builtin_amdgcn_update_dpp(u, u, CTRL, 0xF, 0xF, false));
+    } else {
+        static_assert(sizeof(T) == 8, "32- or 64-bit values");
+        const u64 u = __builtin_bit_cast(u64, v);
+        const int lo = (int)(unsigned)u, hi = (int)(unsigned)(u >> 32);
+        const unsigned l2 = (unsigned)__builtin_amdgcn_update_dpp(lo, lo, CTRL, 0xF, 0xF, false);
+        const unsigned h2 = (unsigned)__builtin_amdgcn_update_dpp(hi, hi, CTRL, 0xF, 0xF, false);
+        return __builtin_bit_cast(T, ((u64)h2 << 32) | l2);
+    }
+}
+
+// the sum of v over the 64 lanes, in every lane (unsigned, u64, long long or double)
+template <typename T>
+__device__ __forceinline__ T dpp_wave_sum(T v) {
+    v += dpp_row_ror<0x128>(v);
+    v += dpp_row_ror<0x124>(v);
+    v += dpp_row_ror<0x122>(v);
+    v += dpp_row_ror<0x121>(v);
+    v += __shfl_xor(v, 16, 64);
+    v += __shfl_xor(v, 32, 64);
+    return v;
+}
+
+__device__ __forceinline__ unsigned dpp_wave_max_u32(unsigned v) {
+    unsigned o;
+    o = dpp_row_ror<0x128>(v); v = o > v ? o : v;
+    o = dpp_row_ror<0x124>(v); v = o > v ? o : v;
+    o = dpp_row_ror<0x122>(v); v = o > v ? o : v;
+    o = dpp_row_ror<0x121>(v); v = o > v ? o : v;
+    o = (unsigned)__shfl_xor((int)v, 16, 64); v = o > v ? o : v;
+    o = (unsigned)__shfl_xor((int)v, 32, 64); v = o > v ? o : v;
+    return v;
+}
+
 // v of lane src, in every lane
 __device__ __forceinline__ u64 wave_shfl_u64(u64 v, int src) {
     const unsigned lo = __shfl((unsigned)v, src, 64), hi = __shfl((unsigned)(v >> 32), src, 64);

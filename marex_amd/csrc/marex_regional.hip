@@ -10,7 +10,7 @@
 // 64-lane pieces of V cells per lane.  Before the row loop a wave tests each piece once: all its cells of one region
 // (the common case: regions are spatially coherent), of none, or mixed.  In the row loop the lanes add their cells into
 // their own registers for as long as consecutive pieces share the region; only when the region changes, and at the end of
-// the row, the run is reduced over the wave (reg_wave_sum) and flushed.  Where all four waves hold one and the same
+// the row, the run is reduced over the wave (dpp_wave_sum) and flushed.  Where all four waves hold one and the same
 // region (R = 1; the interior of a basin) the four wave sums are combined through LDS and one wave issues the global
 // atomics: one set per workgroup and row instead of one per wave.  A mixed piece takes the general path: per distinct
 // region of its present lanes one reduction and one flush.
@@ -57,47 +57,9 @@ __device__ __forceinline__ void reg_load_q(const long long* p, long long (&o)[V]
     }
 }
 
-// The wave reductions of this unit: inside the rows of 16 lanes by DPP rotations (row_ror 8 / 4 / 2 / 1: after them every
-// lane holds its row's result), across the four rows by two shuffles, as wave_min_i32 does.  The flushes are many -- one per
-// wave, row and run -- and a shuffle butterfly of six LDS permutes per word made them the kernel's bound (DESIGN.md
-// section 4); this one takes two.  CTRL: the DPP control word, 0x120 + n = row_ror n.
-template <int CTRL, typename T>
-__device__ __forceinline__ T reg_row_ror(T v) {
-    if constexpr (sizeof(T) == 4) {
-        const int u = __builtin_bit_cast(int, v);
-        return __builtin_bit_cast(T, __builtin_amdgcn_update_dpp(u, u, CTRL, 0xF, 0xF, false));
-    } else {
-        static_assert(sizeof(T) == 8, "32- or 64-bit values");
-        const u64 u = __builtin_bit_cast(u64, v);
-        const int lo = (int)(unsigned)u, hi = (int)(unsigned)(u >> 32);
-        const unsigned l2 = (unsigned)__builtin_amdgcn_update_dpp(lo, lo, CTRL, 0xF, 0xF, false);
-        const unsigned h2 = (unsigned)__builtin_amdgcn_update_dpp(hi, hi, CTRL, 0xF, 0xF, false);
-        return __builtin_bit_cast(T, ((u64)h2 << 32) | l2);
-    }
-}
-
-// the sum of v over the 64 lanes, in every lane (unsigned, u64, long long or double)
-template <typename T>
-__device__ __forceinline__ T reg_wave_sum(T v) {
-    v += reg_row_ror<0x128>(v);
-    v += reg_row_ror<0x124>(v);
-    v += reg_row_ror<0x122>(v);
-    v += reg_row_ror<0x121>(v);
-    v += __shfl_xor(v, 16, 64);
-    v += __shfl_xor(v, 32, 64);
-    return v;
-}
-
-__device__ __forceinline__ unsigned reg_wave_max_u32(unsigned v) {
-    unsigned o;
-    o = reg_row_ror<0x128>(v); v = o > v ? o : v;
-    o = reg_row_ror<0x124>(v); v = o > v ? o : v;
-    o = reg_row_ror<0x122>(v); v = o > v ? o : v;
-    o = reg_row_ror<0x121>(v); v = o > v ? o : v;
-    o = (unsigned)__shfl_xor((int)v, 16, 64); v = o > v ? o : v;
-    o = (unsigned)__shfl_xor((int)v, 32, 64); v = o > v ? o : v;
-    return v;
-}
+// The wave reductions of this unit are dpp_wave_sum and dpp_wave_max_u32 (marex_common.hip.h).  The flushes are many -- one
+// per wave, row and run -- and a shuffle butterfly of six LDS permutes per word made them the kernel's bound (DESIGN.md
+// section 4); those take two.
 
 // the merge of two "one region" summaries: -1 nothing, -2 more than one region, else the region
 __device__ __forceinline__ int reg_merge(int a, int b) {
@@ -176,25 +138,25 @@ k_regional_series(const T* __restrict__ x, long t0, long Tb, long C, int match, 
     auto reduce = [&]() -> bool {
         if (!__ballot((nf | nb) != 0)) return false;
         // a wave's run holds at most 64 * IT * V <= 1024 cells: both counts in one word
-        const unsigned both = reg_wave_sum(nf | (nb << 16));
+        const unsigned both = dpp_wave_sum(nf | (nb << 16));
         nf = both & 0xFFFFu;
         nb = both >> 16;
-        ar = q ? reg_wave_sum(ar) : (long long)nf;
+        ar = q ? dpp_wave_sum(ar) : (long long)nf;
         if (ANOM && nf) {  // wave-uniform
-            sw = wf ? reg_wave_sum(sw) : (double)nf;
-            swa = reg_wave_sum(swa);
-            key = reg_wave_max_u32(key);
+            sw = wf ? dpp_wave_sum(sw) : (double)nf;
+            swa = dpp_wave_sum(swa);
+            key = dpp_wave_max_u32(key);
         }
         if (CATS && nf) {
             static_assert(!CATS || 64 * IT * V < 1024, "the six class counts of a run share one word, ten bits each");
             u64 six = 0;
 #pragma unroll
             for (int n = 0; n < NC; ++n) six |= (u64)cc[n] << (10 * n);
-            six = reg_wave_sum(six);
+            six = dpp_wave_sum(six);
 #pragma unroll
             for (int n = 0; n < NC; ++n) {
                 cc[n] = (unsigned)(six >> (10 * n)) & 1023u;
-                if (cat_area && cc[n]) ca[n] = reg_wave_sum(ca[n]);  // wave-uniform; a class without a cell holds 0 in every lane
+                if (cat_area && cc[n]) ca[n] = dpp_wave_sum(ca[n]);  // wave-uniform; a class without a cell holds 0 in every lane
             }
         }
         return true;

@@ -2060,6 +2060,153 @@ class HotPath:
                    cat_area=host("cat_area", np.int64))
         return out
 
+    @staticmethod
+    def exposure_layout() -> Dict[str, int]:
+        """What the kernels of ``marex_event_exposure_*`` were compiled with (``marex_event_exposure_layout``): the cells of
+        a ``piece``, a ``wave`` and a workgroup (``wg``) per row, the rows between two of a workgroup's (``row_stride``) and
+        the ``id_bits``, ``rank_bits`` and ``step_bits`` of the key.  Needs no device."""
+        out = (C.c_int32 * 7)()
+        if _lib.load().marex_event_exposure_layout(out) != 0:
+            raise ProcessingError("exposure_layout: the library refused the call")
+        return dict(zip(("piece", "wave", "wg", "row_stride", "id_bits", "rank_bits", "step_bits"), (int(v) for v in out)))
+
+    @staticmethod
+    def exposure_key(step, rank, ident) -> np.ndarray:
+        """The uint64 keys of ``(step within the window, region rank, ID)``: ``id << 33 | rank << 17 | step``."""
+        L = HotPath.exposure_layout()
+        s, r, i = (np.asarray(v).astype(np.uint64) for v in (step, rank, ident))
+        return (i << np.uint64(L["rank_bits"] + L["step_bits"])) | (r << np.uint64(L["step_bits"])) | s
+
+    @staticmethod
+    def exposure_home(key, cap: int) -> np.ndarray:
+        """The entry at which the probes of ``key`` begin in a table of ``cap`` entries: the splitmix64 finaliser of the
+        kernels (marex_common.hip.h), for tests that place keys in the table."""
+        with np.errstate(over="ignore"):
+            k = np.asarray(key, dtype=np.uint64).copy()
+            k ^= k >> np.uint64(30)
+            k *= np.uint64(0xbf58476d1ce4e5b9)
+            k ^= k >> np.uint64(27)
+            k *= np.uint64(0x94d049bb133111eb)
+            k ^= k >> np.uint64(31)
+        return (k & np.uint64(int(cap) - 1)).astype(np.int64)
+
+    @staticmethod
+    def exposure_entry_bytes(areas: bool, anomalies: bool) -> int:
+        """The bytes of one table entry of :meth:`event_exposure`: key and counts (16), the area (8), two sums and the
+        maximum's key (20)."""
+        return 16 + (8 if areas else 0) + (20 if anomalies else 0)
+
+    @staticmethod
+    def exposure_cap(runs: int) -> int:
+        """The table of :meth:`event_exposure` for ``runs`` runs: a power of two, at least 64, load factor <= 1/2 even if
+        every run were a key of its own."""
+        return max(64, 1 << max(2 * int(runs) - 1, 1).bit_length())
+
+    def event_exposure(self, ids: torch.Tensor, rank, R: int, t0: int = 0, q=None, wf=None, anom: Optional[torch.Tensor] = None,
+                       cap: Optional[int] = None) -> Dict[str, object]:
+        """The (timestep, region, event) records of one window of a tracked field (``marex_event_exposure_count_i32`` /
+        ``marex_event_exposure_i32``): ``ids`` int32 ``[Tb, C]`` (a cell belongs to event ``ids > 0``), the rows
+        ``t0 .. t0 + Tb - 1``; ``rank`` int32 ``[C]``, the region rank of every cell, outside ``0 .. R - 1``: no region, which
+        is kept under rank ``R``.  ``q`` (int64 ``[C]``, the fixed-point areas of ``regional.area_weight_table``; None: 1 per
+        cell), ``wf`` (float32 ``[C]``, the weights of the anomaly sums, needs ``anom``; None: 1) and ``rank`` are host arrays
+        or tensors on the engine's device (a caller with many windows uploads them once).  ``anom`` float32 ``[Tb, C]`` adds
+        the sums and the maximum.  ``cap`` overrides the planned table size (tests).
+
+        Returns host arrays sorted by ``(id, rank, t)``: ``t`` int64 (global steps), ``rank`` and ``id`` int32, ``cells`` and
+        ``finite`` int64 (all cells; those with a finite anomaly -- all of them without ``anom``), ``area`` int64 (the sum of
+        ``q`` over all cells, or the cells), ``sums`` float64 ``[n, 2]`` (sum of ``wf``, sum of ``wf`` x anomaly over the
+        finite cells) and ``vmax`` float32 (NaN: none), both None without ``anom``; and ``runs``, ``cap`` and
+        ``table_bytes``, what the count pass found and the table took.  A negative ID raises the trackers' "Object IDs must
+        be non-negative" error; a table that the keys do not fit raises :class:`ProcessingError` and leaves the engine as
+        it was."""
+        Tb, Cn = self._ids_check(ids)
+        L = self.exposure_layout()
+        t0, R = int(t0), int(R)
+        if t0 < 0 or R <= 0 or R > self.REGIONAL_MAX_REGIONS or Tb > 1 << L["step_bits"] or Tb == 0 or Cn == 0:
+            raise ProcessingError(f"event_exposure: t0 must not be negative, R must lie in 1 .. {self.REGIONAL_MAX_REGIONS} and a "
+                                  f"window must hold 1 .. {1 << L['step_bits']} steps of at least one cell",
+                                  details=f"t0 = {t0}, Tb = {Tb}, C = {Cn}, R = {R}")
+        if anom is None and wf is not None:
+            raise ProcessingError("event_exposure: weights need the anomalies")
+        if anom is not None:
+            self._anomaly_window_check("event_exposure", anom, Tb, Cn)
+
+        def table(name, v, dt, tdt):  # a host vector is checked and uploaded, a tensor is checked
+            if v is None:
+                return None
+            if isinstance(v, torch.Tensor):
+                if v.dtype != tdt or tuple(v.shape) != (Cn,) or not v.is_contiguous() or v.device != self.device:
+                    raise ProcessingError(f"event_exposure: {name} must be a contiguous {tdt} [{Cn}] tensor on the engine's device",
+                                          details=f"got {v.dtype} {tuple(v.shape)} on {v.device}")
+                return v
+            h = np.ascontiguousarray(v)
+            if h.dtype != dt or h.shape != (Cn,):
+                raise ProcessingError(f"event_exposure: {name} must be {Cn} {np.dtype(dt).name} values", details=f"got {h.dtype} {h.shape}")
+            if name == "q" and ((h < 0).any() or int(h.max()) >= 2**62 or
+                                (int((h >> 32).sum()) << 32) + int((h & 0xFFFFFFFF).sum()) >= 2**62):  # the exact sum, in halves
+                raise ProcessingError(f"event_exposure: q must be {Cn} non-negative int64 areas whose sum stays below 2^62")
+            return self._dev(h)
+
+        reg_d = table("rank", rank, np.int32, torch.int32)
+        q_d = table("q", q, np.int64, torch.int64)
+        w_d = table("wf", wf, np.float32, torch.float32)
+        an, ar = anom is not None, q_d is not None
+        empty = {"t": np.zeros(0, np.int64), "rank": np.zeros(0, np.int32), "id": np.zeros(0, np.int32),
+                 "cells": np.zeros(0, np.int64), "finite": np.zeros(0, np.int64), "area": np.zeros(0, np.int64),
+                 "sums": np.zeros((0, 2), np.float64) if an else None, "vmax": np.zeros(0, np.float32) if an else None,
+                 "runs": 0, "cap": 0, "table_bytes": 0}
+        status = self._buf(None, "exp_status", (8,), torch.int64, self.device)
+        self.call("marex_event_exposure_count_i32", ids, Tb, Cn, reg_d, R, status)
+        s = status.cpu().numpy()
+        neg, runs = int(s[0]), int(s[2])
+        if neg:
+            raise create_data_validation_error("Object IDs must be non-negative", details=f"{neg} negative cells; 0 is background",
+                                               data_info={"negative_cells": neg})
+        if runs == 0:
+            return empty
+        planned = self.exposure_cap(runs)
+        cap = planned if cap is None else int(cap)
+        if cap < 64 or cap & (cap - 1):
+            raise ProcessingError(f"event_exposure: cap={cap} is not a power of two >= 64")
+        per = self.exposure_entry_bytes(ar, an)
+        n_out = min(runs, cap)
+        nbytes = per * (cap + n_out)
+        self._check_fits(nbytes, "event exposure", f"a hash table of {cap} entries of {per} bytes for {runs} runs of equal "
+                         f"(timestep, region, event) keys, and {n_out} compacted entries")
+        dev = self.device
+
+        def pair(name, tail, dtype, on=True):
+            if not on:
+                return None, None
+            return self._buf(None, "exp_" + name, (cap,) + tail, dtype, dev), self._buf(None, "exp_out_" + name, (n_out,) + tail, dtype, dev)
+
+        keys, out_k = pair("keys", (), torch.int64)
+        cnt, out_c = pair("cnt", (), torch.int64)
+        area, out_a = pair("area", (), torch.int64, ar)
+        sums, out_s = pair("sums", (2,), torch.float64, an)
+        vmax, out_v = pair("vmax", (), torch.int32, an)
+        self.call("marex_event_exposure_i32", ids, Tb, Cn, reg_d, R, q_d, w_d, anom, cap, keys, cnt, area, sums, vmax, status,
+                  n_out, out_k, out_c, out_a, out_s, out_v)
+        s = status.cpu().numpy()
+        n = int(s[3])
+        if s[1] != 0 or not 0 < n <= n_out:
+            raise ProcessingError(f"event_exposure: the table of {cap} entries does not hold the keys of {runs} runs",
+                                  details=f"{n} entries were taken; a table planned by the engine holds {planned}")
+        k = out_k[:n].cpu().numpy().view(np.uint64)
+        order = np.argsort(k, kind="stable")
+        k = k[order]
+        c = out_c[:n].cpu().numpy().view(np.uint64)[order]
+        sb, rb = np.uint64(L["step_bits"]), np.uint64(L["rank_bits"])
+        cells = (c & np.uint64(0xFFFFFFFF)).astype(np.int64)
+        out = dict(empty, runs=runs, cap=cap, table_bytes=nbytes,
+                   t=(k & np.uint64((1 << L["step_bits"]) - 1)).astype(np.int64) + t0,
+                   rank=((k >> sb) & np.uint64((1 << L["rank_bits"]) - 1)).astype(np.int32), id=(k >> (sb + rb)).astype(np.int32),
+                   cells=cells, finite=(c >> np.uint64(32)).astype(np.int64),
+                   area=out_a[:n].cpu().numpy()[order] if ar else cells.copy())
+        if an:
+            out.update(sums=out_s[:n].cpu().numpy()[order], vmax=self._key_max(out_v[:n].cpu().numpy().view(np.uint32)[order]))
+        return out
+
     def cell_event_records(self, acc: dict) -> Dict[str, object]:
         """The record buffers of a second pass of :meth:`cell_events`, from the accumulators of a finished summary pass:
         ``off`` int64 ``[C + 1]`` (the exclusive scan of the events per cell, summed over the groups, on the device), ``n``

@@ -58,22 +58,11 @@ def _spatial(v, p: dict, name: str, row_vector: bool = False):
                                        details=f"{name} {a.shape}, a timestep {sp}")
 
 
-def _plan(field, regions, cell_areas, dat_anomaly, thresholds, mask, by, event_id, block_steps, time=None):
-    """Everything that can be refused or derived without a device.  ``time``: the tracker's ``(time dimension, time
-    coordinate, values)``; its values stand in where the fields carry no time coordinate."""
-    p = {"block_steps": _check_block_steps(block_steps), **_stream.plan_field(field, "regional_series", dat_anomaly)}
-    if time is not None and p["tv"] is None and len(time[2]) == p["T"]:
-        p["tv"] = np.asarray(time[2])
-    T, C, tv = p["T"], p["C"], p["tv"]
-    p["match"] = 0
-    if event_id is not None:
-        if p["kind"] == "m":
-            raise create_data_validation_error("event_id needs an ID field, not a mask")
-        k = event_id.item() if isinstance(event_id, np.generic) else event_id
-        if isinstance(k, bool) or not isinstance(k, int) or k <= 0 or k > _I32_MAX:
-            raise create_data_validation_error("event_id must be a positive int32 ID", details=f"got {event_id!r}")
-        p["match"] = int(k)
-    # regions: the distinct values >= 0, ascending, are the coordinate; the kernel gets their ranks, -1 for none
+def region_ranks(regions, mask, p: dict):
+    """``(rvals, rank)`` of a region map over the spatial shape of the planned field ``p``: the distinct values ``>= 0``,
+    ascending -- the ``region`` coordinate -- and the rank int32 ``[C]`` of every cell among them, -1 for a cell of no region
+    (a value below 0, or a cell that ``mask`` removes).  ``regions`` None: one region 0 that holds every cell."""
+    C = p["C"]
     if regions is None:
         rvals, rank = np.zeros(1, np.int64), np.zeros(C, np.int32)
     else:
@@ -92,6 +81,25 @@ def _plan(field, regions, cell_areas, dat_anomaly, thresholds, mask, by, event_i
         if m.dtype.kind not in "biu":
             raise create_data_validation_error("mask must be boolean or integer", details=f"Found dtype {m.dtype}")
         rank = np.where(m != 0, rank, np.int32(-1)).astype(np.int32)
+    return rvals, rank
+
+
+def _plan(field, regions, cell_areas, dat_anomaly, thresholds, mask, by, event_id, block_steps, time=None):
+    """Everything that can be refused or derived without a device.  ``time``: the tracker's ``(time dimension, time
+    coordinate, values)``; its values stand in where the fields carry no time coordinate."""
+    p = {"block_steps": _check_block_steps(block_steps), **_stream.plan_field(field, "regional_series", dat_anomaly)}
+    if time is not None and p["tv"] is None and len(time[2]) == p["T"]:
+        p["tv"] = np.asarray(time[2])
+    T, C, tv = p["T"], p["C"], p["tv"]
+    p["match"] = 0
+    if event_id is not None:
+        if p["kind"] == "m":
+            raise create_data_validation_error("event_id needs an ID field, not a mask")
+        k = event_id.item() if isinstance(event_id, np.generic) else event_id
+        if isinstance(k, bool) or not isinstance(k, int) or k <= 0 or k > _I32_MAX:
+            raise create_data_validation_error("event_id must be a positive int32 ID", details=f"got {event_id!r}")
+        p["match"] = int(k)
+    rvals, rank = region_ranks(regions, mask, p)  # the kernel gets the ranks, -1 for none
     R = max(int(rvals.size), 1)  # a map without a region: one that holds no cell
     if rvals.size == 0:
         rvals = np.zeros(1, np.int64)

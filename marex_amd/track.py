@@ -1056,6 +1056,35 @@ class tracker(_MeshStages):  # noqa: N801 -- the reference's public name (marEx.
             raise TypeError(f"regional_series() got an unexpected keyword argument {next(iter(kw))!r}")
         return _regional_series(field, regions, time=(self.timedim, self.timecoord, self.time_values), **args)
 
+    def event_exposure(self, events_ds, regions, extremes_ds=None, **kw):
+        """Which events of :meth:`run` touched which region, when and how
+        (:func:`marex_amd.exposure.event_exposure` has the arguments and the variables) from ``events_ds["ID_field"]``, on
+        this tracker's device and with its time values.  With ``extremes_ds``, the Dataset of ``preprocess_data``,
+        ``dat_anomaly`` comes from it.  Unless passed, ``mask`` is the tracker's mask and ``cell_areas`` its areas, as in
+        :meth:`regional_series`.  The ``ID`` axis of a merge tracker's Dataset is checked against what the pass found
+        (:class:`ProcessingError`)."""
+        from .exposure import _event_exposure
+
+        kw.setdefault("device", self.device)
+        if extremes_ds is not None:
+            kw.setdefault("dat_anomaly", extremes_ds["dat_anomaly"])
+        if "mask" not in kw:
+            m = getattr(self, "_mask_host", None)
+            kw["mask"] = m if m is not None else getattr(self, "mask", None)
+        if "cell_areas" not in kw:
+            kw["cell_areas"] = np.asarray(_host(self.cell_area)) if self.unstructured_grid else getattr(self, "_cell_weights", None)
+        is_ds = hasattr(events_ds, "data_vars")
+        field = events_ds["ID_field"] if is_ds else events_ds
+        args = {k: kw.pop(k, d) for k, d in (("cell_areas", None), ("dat_anomaly", None), ("mask", None), ("per_timestep", False),
+                                             ("block_steps", None), ("device", None))}
+        if kw:
+            raise TypeError(f"event_exposure() got an unexpected keyword argument {next(iter(kw))!r}")
+        n = int(np.asarray(events_ds["ID"].values).size) if is_ds and "ID" in events_ds else None
+        if n is not None and not np.array_equal(np.asarray(events_ds["ID"].values), np.arange(1, n + 1)):
+            raise ProcessingError("event_exposure: the ID axis of the events Dataset is not 1 .. N",
+                                  details=f"{n} IDs from {np.asarray(events_ds['ID'].values)[:1]}")
+        return _event_exposure(field, regions, time=(self.timedim, self.timecoord, self.time_values), n_events=n, **args)
+
     def _latlon_coords(self) -> dict:
         """The input's lat / lon as coordinate entries ``name -> (dims, host values)``."""
         ydim = self.xdim if self.unstructured_grid else self.ydim  # on a mesh lat runs over the cells too
