@@ -366,7 +366,8 @@ int marex_div_doy_f32(marex_ctx* ctx, const float* anom, const float* std_roll, 
 /* Tracker pre-processing, gridded data (marEx/track.py:1520-1676): per timestep, pad the binary image by 2 R cells on
  * every side (regional_mode 0: np.pad "wrap" in both dimensions, 1: "edge"), binary closing then binary opening with the
  * disk x^2 + y^2 < R^2 + 1 (scipy.ndimage semantics, border_value 0), trim the padding, AND with the ocean mask.
- * data / out: uint8 [T, ny, nx] (0 / 1); mask: uint8 [ny, nx].  R = 0: only the mask is applied. */
+ * data / out: uint8 [T, ny, nx] (0 / 1); mask: uint8 [ny, nx].  R = 0: only the mask is applied.  R in 0..63.  No pointer
+ * needs more than byte alignment (the 8-byte stores are taken for nx % 8 == 0 with mask and out 8-byte aligned only). */
 int marex_fill_holes_u8(marex_ctx* ctx, const uint8_t* data, const uint8_t* mask, int64_t T, int ny, int nx, int R,
                         int regional_mode, uint8_t* out);
 

@@ -93,10 +93,11 @@ k_morph_pass(const u64* __restrict__ in, u64* __restrict__ out, long T, int Hp, 
 }
 
 // eight consecutive cells of a row per thread: 8 bits taken from one or two packed words, spread to bytes, ANDed with
-// the ocean mask, one 8-byte store
+// the ocean mask, one 8-byte store where `wide` says so (the host's decision: nx a multiple of 8 AND mask and out 8-byte
+// aligned, so that every group of every row is), byte by byte otherwise
 __global__ void __launch_bounds__(256)
 k_morph_unpack(const u64* __restrict__ packed, const unsigned char* __restrict__ mask, long T, int ny, int nx, int R,
-               int Hp, int Wp, unsigned char* __restrict__ out) {
+               int Hp, int Wp, int wide, unsigned char* __restrict__ out) {
     const int ng = (nx + 7) >> 3;  // groups of 8 cells per row
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= T * ny * (long)ng) return;
@@ -111,7 +112,7 @@ k_morph_unpack(const u64* __restrict__ packed, const unsigned char* __restrict__
     if (sh > 56 && w + 1 < Wp) bits |= row[w + 1] << (64 - sh);
     const unsigned char* mrow = mask + (size_t)y * nx + x;
     unsigned char* orow = out + ((size_t)t * ny + y) * nx + x;
-    if (x + 8 <= nx && (nx & 7) == 0) {
+    if (wide) {  // nx % 8 == 0: every group is whole
         u64 spread = 0;  // byte i = bit i
 #pragma unroll
         for (int i = 0; i < 8; ++i) spread |= ((bits >> i) & 1ull) << (8 * i);
@@ -218,8 +219,10 @@ extern "C" int marex_fill_holes_u8(marex_ctx* ctx, const uint8_t* data, const ui
     hipLaunchKernelGGL(k_morph_pass, dim3(gw), dim3(256), 0, ctx->stream, b, a, (long)T, Hp, Wp, nxp, R, hw_dev, 1);  //   dilate, erode
     hipLaunchKernelGGL(k_morph_pass, dim3(gw), dim3(256), 0, ctx->stream, a, b, (long)T, Hp, Wp, nxp, R, hw_dev, 1);  // opening:
     hipLaunchKernelGGL(k_morph_pass, dim3(gw), dim3(256), 0, ctx->stream, b, a, (long)T, Hp, Wp, nxp, R, hw_dev, 0);  //   erode, dilate
+    // a view at an odd offset is a valid mask or output: the 8-byte accesses are taken on pointer alignment too
+    const int wide = (nx & 7) == 0 && (((uintptr_t)mask | (uintptr_t)out) & 7) == 0;
     hipLaunchKernelGGL(k_morph_unpack, dim3((unsigned)((T * ny * (long)((nx + 7) / 8) + 255) / 256)), dim3(256), 0, ctx->stream, a,
-                       mask, (long)T, ny, nx, R, Hp, Wp, out);
+                       mask, (long)T, ny, nx, R, Hp, Wp, wide, out);
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }
