@@ -1,14 +1,16 @@
-"""What the streaming statistics (``intensity``, ``event_categories``, ``occurrence``, ``local_intensity``, ``cell_events``,
-``compound``; ``trends`` for the free memory) share in front of the engine: what a ``[time, space]`` field says without a
-device, the windows it is walked in -- with or without a part that stays for the whole call -- and the way back to its
-spatial dimensions."""
+"""What the streaming statistics (``intensity``, ``event_categories``, ``shapes``, ``regional``, ``exposure``, ``occurrence``,
+``local_intensity``, ``cell_events``, ``compound``, ``composites``; ``trends`` for the free memory) share in front of the
+engine: what a ``[time, space]`` field says without a device, the windows it is walked in -- with or without a part that
+stays for the whole call -- and the way back to its spatial dimensions.  For the first five also the parser of a map or of
+``cell_areas`` over space, the area table, the regions' denominators and the tracker's ``time`` triple; for the statistics over
+(timestep, event) slots (the first three, ``track`` and ``exposure`` in part) the two-pass walk, the slot index and the padding."""
 from __future__ import annotations
 
 from typing import Optional
 
 import numpy as np
 
-from .exceptions import ConfigurationError, TrackingError, create_data_validation_error
+from .exceptions import ConfigurationError, ProcessingError, TrackingError, create_data_validation_error
 from .track import _BLOCK_CELLS, PINNED_ID_FIELD_BYTES, _host, _tensor_of
 from .xr_compat import DataArray
 
@@ -258,3 +260,140 @@ def walk_windows(T: int, B: int, step):
         r = step(a, min(T, a + B), acc, a + B >= T)
         acc = r["acc"]
     return r
+
+
+def spatial(v, p: dict, name: str, row_vector: bool = False, mismatch: Optional[str] = None, numbers: bool = False):
+    """``v`` flat over the cells of a timestep of the planned field ``p`` (``shape``, ``labelled``, ``sdims``): given in the
+    spatial shape, flat, transposed under the field's own dimension names, or -- ``row_vector`` -- as a ``[y]`` vector
+    broadcast along x.  ``mismatch``: the caller's wording of the refusal; ``numbers``: anything but numbers is refused too."""
+    a = np.asarray(_host(v))
+    if numbers and a.dtype.kind not in "fiu":
+        raise create_data_validation_error(f"{name} must be numbers", details=f"Found dtype {a.dtype}")
+    sp = tuple(p["shape"][1:])
+    d = tuple(getattr(v, "dims", ()) or ())
+    if len(sp) == 2 and a.ndim == 2 and d and p["labelled"] and d == (p["sdims"][1], p["sdims"][0]):
+        a = a.T
+    if a.shape == sp or a.shape == (int(np.prod(sp)),):
+        return np.ascontiguousarray(a).reshape(-1)
+    if row_vector and len(sp) == 2 and a.shape == (sp[0],):
+        return np.ascontiguousarray(np.broadcast_to(a[:, None], sp)).reshape(-1)
+    raise create_data_validation_error(mismatch or f"{name} does not match the spatial shape of the field",
+                                       details=f"{name} {a.shape}, a timestep {sp}")
+
+
+def area_weight_table(cell_areas):
+    """``(e, q)``: the fixed-point areas of the cells, ``q = rint(a * 2^e)`` int64 in the shape of ``cell_areas`` with
+    ``a = float64(cell_areas)`` and ``e = 61 - ceil(log2(sum(a)))`` -- the rule, and the bits, of row 0 of
+    ``track_mesh.mesh_weight_tables``: the sum of ``q`` over any set of cells stays below 2^62, so 64-bit integer sums
+    cannot overflow, and an area is ``ldexp(float64(S), -e)`` of its integer sum ``S``.  :class:`DataValidationError` for
+    an area that is negative or not finite, or areas that sum to zero.  Needs no GPU."""
+    a = np.ascontiguousarray(np.asarray(_host(cell_areas), dtype=np.float64))
+    flat = a.reshape(-1)
+    if flat.size == 0 or not np.isfinite(flat).all() or (flat < 0).any():
+        raise create_data_validation_error("cell_areas must be finite and non-negative",
+                                           details=f"{int((~np.isfinite(flat)).sum())} non-finite and {int((flat < 0).sum())} "
+                                                   f"negative of {flat.size} values")
+    total = float(flat.sum())
+    if not (total > 0 and np.isfinite(total)):
+        raise create_data_validation_error("cell_areas must have a positive, finite sum", details=f"sum {total}")
+    e = 61 - int(np.ceil(np.log2(total)))
+    return e, np.rint(np.ldexp(flat, e)).astype(np.int64).reshape(a.shape)
+
+
+def area_tables(cell_areas, p: dict):
+    """``(e, q, wf)`` of the ``cell_areas`` of a region statistic: the exponent and the int64 ``[C]`` areas of
+    :func:`area_weight_table`, and the float32 weights of the anomaly sums; ``(0, None, None)`` without areas or cells."""
+    a = None if cell_areas is None else spatial(cell_areas, p, "cell_areas", row_vector=True, numbers=True)
+    if a is None or not p["C"]:
+        return 0, None, None
+    return (*area_weight_table(a), np.ascontiguousarray(a, dtype=np.float32))
+
+
+def region_denominators(rank, q, R: int):
+    """``(region_cells, region_q)`` int64 ``[R]``: the cells of every region and their fixed-point area (the cells again
+    without ``q``), exact host integers, over the cells with ``rank >= 0``."""
+    ok = rank >= 0
+    cells = np.bincount(rank[ok], minlength=R).astype(np.int64)
+    if q is None:
+        return cells, cells
+    ra = np.zeros(R, np.int64)
+    np.add.at(ra, rank[ok], q[ok])
+    return cells, ra
+
+
+def tracker_time(p: dict, time, names: bool = True, fitting: bool = False) -> None:
+    """Applies a tracker's ``time`` triple ``(time dimension, time coordinate, values)`` to the plan ``p`` (``T``, ``tname``,
+    ``tv``; adds ``tcoord``, None without a tracker): its names and values replace the field's -- with ``fitting`` the values
+    only if they have the field's length.  Without ``names`` only its values, where they fit and the field has no time coordinate."""
+    p.setdefault("tcoord", None)
+    if time is None:
+        return
+    if names:
+        p["tname"], p["tcoord"] = time[0], time[1]
+    fits = len(time[2]) == p["T"]
+    if (names and not fitting) or (fits and (names or p["tv"] is None)):
+        p["tv"] = np.asarray(time[2])
+
+
+def weighted_mean(some, W, SA):
+    """``SA / W`` where ``some`` holds and ``W`` is not 0, NaN elsewhere."""
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(some & (W != 0), SA / np.where(W != 0, W, 1.0), np.nan)
+
+
+def event_spans(eng, ids_w, T: int, B: int):
+    """The first pass of a slot statistic over an ID field in windows of ``B`` steps: ``(N, tmin, tmax, wins, kept)`` -- the
+    largest event number, the first and last step of the events 0..N (int64, entry 0 unused), the windows ``(a, b)`` and the
+    window itself where the field is taken whole."""
+    wins = [(a, min(T, a + B)) for a in range(0, T, B)]
+    kept = None
+    tmin, tmax = np.full(1, _I32_MAX, np.int64), np.full(1, -1, np.int64)
+    for a, b in wins:
+        x = ids_w.get(a, b)
+        sp = eng.id_spans(x)
+        if len(wins) == 1:
+            kept = x
+        if sp is None:
+            continue
+        lo, hi = sp[0].astype(np.int64), sp[1].astype(np.int64)
+        if lo.size > tmin.size:
+            grow = lo.size - tmin.size
+            tmin = np.concatenate([tmin, np.full(grow, _I32_MAX, np.int64)])
+            tmax = np.concatenate([tmax, np.full(grow, -1, np.int64)])
+        seen = hi >= 0
+        n = lo.size
+        tmin[:n] = np.where(seen, np.minimum(tmin[:n], lo + a), tmin[:n])
+        tmax[:n] = np.where(seen, np.maximum(tmax[:n], hi + a), tmax[:n])
+        del x
+    tmin[0], tmax[0] = _I32_MAX, -1
+    return int(tmin.size) - 1, tmin, tmax, wins, kept
+
+
+def walk_event_slots(ids_w, wins, kept, step):
+    """The second pass: the last result of ``step(x, a, b, acc, finish)`` over the windows of :func:`event_spans`, each given
+    its rows ``x`` (``kept``, or fetched again), the ``"acc"`` of the result before it, and ``finish`` on the last."""
+    acc = r = None
+    for i, (a, b) in enumerate(wins):
+        r = step(kept if kept is not None else ids_w.get(a, b), a, b, acc, i == len(wins) - 1)
+        acc = r["acc"]
+    return r
+
+
+def slot_index(off, tmin, N: int):
+    """``(e_of, t_of)``: the event and the timestep of every (timestep, event) slot -- event ``e`` of 1..N owns the slots
+    ``off[e] .. off[e + 1] - 1``, one per step from ``tmin[e]`` on."""
+    e_of = np.repeat(np.arange(N + 1), np.diff(off)[:N + 1])
+    return e_of, np.arange(e_of.size) - off[e_of] + tmin[e_of]
+
+
+def pad_events(what: str, N: int, n_events: Optional[int], tmin=None, off=None):
+    """``(N, tmin, off)`` stretched to the ``n_events`` of the events Dataset (None: as they are): trailing events without
+    a cell get no slot.  :class:`ProcessingError` where the field holds an event beyond them."""
+    if n_events is None:
+        return N, tmin, off
+    if N > n_events:
+        raise ProcessingError(f"{what}: the ID field holds event {N}, the events Dataset ends at {n_events}")
+    if N < n_events and tmin is not None:
+        tmin = np.concatenate([tmin, np.full(n_events - N, _I32_MAX, np.int64)])
+        off = np.concatenate([off[:N + 2], np.full(n_events - N, off[N + 1], np.int64)])
+    return int(n_events), tmin, off

@@ -200,6 +200,20 @@ __device__ __forceinline__ u64 splitmix64(u64 k) {
 // blocks of 256 threads of a grid-stride loop over n items
 static inline unsigned stride_grid(long n) { return (unsigned)(n < 256L * 8192 ? (n + 255) / 256 : 8192); }
 
+// The strided-row grid over a [T][C] field: a column of workgroups per `chunk` cells of a row, min(T, tstride) of them per
+// column, each striding over the rows by gridDim.y.  The chunk (a register budget) and the row stride are the unit's own.
+static inline dim3 slice_grid(long T, long C, long chunk, int tstride) {
+    return dim3((unsigned)((C + chunk - 1) / chunk), (unsigned)(T < tstride ? T : tstride));
+}
+
+// What the (timestep, event) slot entry points refuse alike (`ptrs`: the entry point's own are there); `tail` ends the sentence.
+static inline int evt_slot_args(marex_ctx* ctx, const char* name, bool ptrs, const void* ev_tmin, const void* ev_off, int64_t t0,
+                                int64_t Tb, int64_t C, int n_ev, int64_t n_slots, const char* tail = " or no slot") {
+    if (!ptrs || !ev_tmin || !ev_off || t0 < 0 || Tb <= 0 || C <= 0 || n_ev <= 0 || n_slots <= 0)
+        return fail(ctx, -1, "%s: null pointer, empty shape, no event%s", name, tail);
+    return 0;
+}
+
 // rows and steps are addressed through int: 0 where they fit, else the entry point's failure
 static inline int cell_stream_limits(marex_ctx* ctx, const char* name, int64_t t0, int64_t Tb, int64_t C) {
     if (C >= 2147483647L || t0 >= 2147483647L || Tb >= 2147483647L || t0 + Tb >= 2147483647L)

@@ -163,14 +163,15 @@ extern "C" int marex_event_categories_f32(marex_ctx* ctx, const int32_t* ids, co
                                           const float* thr, const int32_t* doy, int n_doy, const float* w, uint64_t* cat_cnt,
                                           double* cat_area, uint8_t* field, uint64_t* status) {
     if (!ctx) return -1;
-    if (!ids || !anom || !ev_tmin || !ev_off || !cat_cnt || !status || t0 < 0 || Tb <= 0 || C <= 0 || n_ev <= 0 || n_slots <= 0)
-        return fail(ctx, -1, "marex_event_categories_f32: null pointer, empty shape, no event or no slot");
+    if (const int rc = evt_slot_args(ctx, "marex_event_categories_f32", ids && anom && cat_cnt && status, ev_tmin, ev_off, t0, Tb, C,
+                                     n_ev, n_slots))
+        return rc;
     if (!thr || !doy || n_doy <= 0 || (w == nullptr) != (cat_area == nullptr))
         return fail(ctx, -1, "marex_event_categories_f32: thr or doy missing, n_doy <= 0, or w and cat_area given in part");
     if (const int rc = cell_stream_limits(ctx, "marex_event_categories_f32", t0, Tb, C)) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     LaunchTimer lt(ctx, MAREX_K_MORPH);
-    const dim3 grid((unsigned)((C + CAT_CHUNK - 1) / CAT_CHUNK), (unsigned)(Tb < CAT_TSTRIDE ? Tb : CAT_TSTRIDE));
+    const dim3 grid = slice_grid(Tb, C, CAT_CHUNK, CAT_TSTRIDE);
 #define CAT_LAUNCH(WT, FD)                                                                                                  \
     hipLaunchKernelGGL((k_evt_categories<WT, FD>), grid, dim3(256), 0, ctx->stream, ids, anom, (long)t0, (long)Tb, (long)C,  \
                        n_ev, ev_tmin, (const long long*)ev_off, (long long)n_slots, thr, doy, n_doy, w, (u64*)cat_cnt,       \

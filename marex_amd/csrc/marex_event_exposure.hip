@@ -195,7 +195,7 @@ k_exp_compact(long cap, const u64* __restrict__ keys, const u64* __restrict__ cn
 }
 
 static inline dim3 exp_grid(long Tb, long C) {
-    return dim3((unsigned)((C + EXP_WG_CELLS - 1) / EXP_WG_CELLS), (unsigned)(Tb < EXP_TSTRIDE ? Tb : EXP_TSTRIDE));
+    return slice_grid(Tb, C, EXP_WG_CELLS, EXP_TSTRIDE);
 }
 
 static int exp_limits(marex_ctx* ctx, const char* name, int64_t Tb, int64_t C, int R) {

@@ -299,16 +299,18 @@ extern "C" int marex_event_shapes_i32(marex_ctx* ctx, const int32_t* ids, int64_
                                       const uint8_t* mask, const int64_t* area_q, const int64_t* ns_q, const int64_t* ew_q,
                                       uint64_t* mom, int32_t* box, uint64_t* status) {
     if (!ctx) return -1;
-    if (!ids || !ev_tmin || !ev_off || !mom || !box || !status || t0 < 0 || Tb <= 0 || ny <= 0 || nx <= 0 || n_ev <= 0 ||
-        n_slots <= 0 || (ns_q == nullptr) != (ew_q == nullptr))
-        return fail(ctx, -1, "marex_event_shapes_i32: null pointer, empty shape, no event, no slot, or half a pair of edge tables");
+    // the edge tables come as a pair or not at all, which counts with the pointers; the cells of a row are given by two sides
+    if (const int rc = evt_slot_args(ctx, "marex_event_shapes_i32", ids && mom && box && status && (ns_q == nullptr) == (ew_q == nullptr),
+                                     ev_tmin, ev_off, t0, Tb, /* C > 0 */ ny > 0 && nx > 0 ? 1 : 0, n_ev, n_slots,
+                                     ", no slot, or half a pair of edge tables"))
+        return rc;
     if (ny > SHP_MAX_SIDE || nx > SHP_MAX_SIDE)
         return fail(ctx, -4, "marex_event_shapes_i32: a grid side above %d (the second moments are 64-bit sums)", SHP_MAX_SIDE);
     const int64_t C = (int64_t)ny * nx;
     if (const int rc = cell_stream_limits(ctx, "marex_event_shapes_i32", t0, Tb, C)) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     LaunchTimer lt(ctx, MAREX_K_MORPH);
-    const dim3 grid((unsigned)((C + SHP_CHUNK - 1) / SHP_CHUNK), (unsigned)(Tb < SHP_TSTRIDE ? Tb : SHP_TSTRIDE));
+    const dim3 grid = slice_grid(Tb, C, SHP_CHUNK, SHP_TSTRIDE);
     const bool tables = area_q || ns_q;
 #define SHP_LAUNCH(M, W)                                                                                                    \
     hipLaunchKernelGGL((k_evt_shapes<M, W>), grid, dim3(256), 0, ctx->stream, ids, (long)t0, (long)Tb, ny, nx, regional, n_ev, \

@@ -128,13 +128,13 @@ extern "C" int marex_event_intensity_f32(marex_ctx* ctx, const int32_t* ids, con
                                          int64_t C, int n_ev, const int32_t* ev_tmin, const int64_t* ev_off, int64_t n_slots,
                                          const float* w, uint64_t* cnt, double* sums, uint32_t* vmax, uint64_t* status) {
     if (!ctx) return -1;
-    if (!ids || !anom || !ev_tmin || !ev_off || !cnt || !sums || !vmax || !status || t0 < 0 || Tb <= 0 || C <= 0 || n_ev <= 0 ||
-        n_slots <= 0)
-        return fail(ctx, -1, "marex_event_intensity_f32: null pointer, empty shape, no event or no slot");
+    if (const int rc = evt_slot_args(ctx, "marex_event_intensity_f32", ids && anom && cnt && sums && vmax && status, ev_tmin, ev_off,
+                                     t0, Tb, C, n_ev, n_slots))
+        return rc;
     if (const int rc = cell_stream_limits(ctx, "marex_event_intensity_f32", t0, Tb, C)) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     LaunchTimer lt(ctx, MAREX_K_MORPH);
-    const dim3 grid((unsigned)((C + INT_CHUNK - 1) / INT_CHUNK), (unsigned)(Tb < INT_TSTRIDE ? Tb : INT_TSTRIDE));
+    const dim3 grid = slice_grid(Tb, C, INT_CHUNK, INT_TSTRIDE);
     if (w)
         hipLaunchKernelGGL(k_evt_intensity<true>, grid, dim3(256), 0, ctx->stream, ids, anom, (long)t0, (long)Tb, (long)C, n_ev,
                            ev_tmin, (const long long*)ev_off, (long long)n_slots, w, (u64*)cnt, sums, (unsigned*)vmax,

@@ -485,7 +485,7 @@ extern "C" int marex_event_rename_i32(marex_ctx* ctx, int32_t* ids, int64_t T, i
     HIP_TRY(ctx, hipMemsetAsync(gid, 0, (size_t)n_slots * sizeof(int32_t), ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(status, 0, sizeof(u64), ctx->stream));
     if (w) HIP_TRY(ctx, hipMemsetAsync(wacc, 0, (size_t)n_slots * MRG_NWMOM * sizeof(double), ctx->stream));
-    const dim3 grid((unsigned)((C + MRG_CHUNK - 1) / MRG_CHUNK), (unsigned)(T < MRG_TSTRIDE ? T : MRG_TSTRIDE));
+    const dim3 grid = slice_grid(T, C, MRG_CHUNK, MRG_TSTRIDE);
     if (w)
         hipLaunchKernelGGL(k_mrg_event_rename<true>, grid, dim3(256), 0, ctx->stream, ids, (long)T, ny, nx, lut, (long)lut_len, n_ev,
                            ev_tmin, (const long long*)ev_off, (long long)n_slots, w, (u64*)acc, wacc, gid, (u64*)status);

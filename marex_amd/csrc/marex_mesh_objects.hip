@@ -32,7 +32,7 @@ __device__ __forceinline__ long long mobj_wave_sum_i64(long long v) {
 __device__ __forceinline__ long mobj_piece0(int wave) { return (long)blockIdx.x * MOBJ_CHUNK + (long)wave * (64 * MOBJ_ITERS); }
 
 static inline dim3 mobj_slice_grid(long T, long C) {
-    return dim3((unsigned)((C + MOBJ_CHUNK - 1) / MOBJ_CHUNK), (unsigned)(T < MOBJ_TSTRIDE ? T : MOBJ_TSTRIDE));
+    return slice_grid(T, C, MOBJ_CHUNK, MOBJ_TSTRIDE);
 }
 
 // ------------------------------------------------------------------------------------------------ per-timestep IDs
@@ -465,8 +465,8 @@ extern "C" int marex_mesh_area_i64(marex_ctx* ctx, const uint8_t* data, int64_t 
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     LaunchTimer lt(ctx, MAREX_K_MORPH);
     HIP_TRY(ctx, hipMemsetAsync(out, 0, (size_t)T * sizeof(u64), ctx->stream));
-    hipLaunchKernelGGL(k_mesh_area, dim3((unsigned)((C + MOBJ_CHUNK - 1) / MOBJ_CHUNK), (unsigned)(T < 65535 ? T : 65535)), dim3(256), 0,
-                       ctx->stream, data, (long)T, (long)C, (const long long*)q0, (u64*)out);
+    hipLaunchKernelGGL(k_mesh_area, slice_grid(T, C, MOBJ_CHUNK, 65535), dim3(256), 0, ctx->stream, data, (long)T, (long)C,
+                       (const long long*)q0, (u64*)out);
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }

@@ -348,7 +348,7 @@ k_ovl_compact(long cap, const u64* __restrict__ keys, const u64* __restrict__ cn
 // OBJ_TSTRIDE slices in flight at once spread what remains over as many addresses
 #define OBJ_TSTRIDE 64
 static inline dim3 obj_slice_grid(long T, long C) {
-    return dim3((unsigned)((C + OBJ_CHUNK - 1) / OBJ_CHUNK), (unsigned)(T < OBJ_TSTRIDE ? T : OBJ_TSTRIDE));
+    return slice_grid(T, C, OBJ_CHUNK, OBJ_TSTRIDE);
 }
 
 extern "C" int marex_ids_minmax_i32(marex_ctx* ctx, const int32_t* ids, int64_t n, int32_t* minmax) {

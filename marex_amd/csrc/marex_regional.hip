@@ -341,7 +341,7 @@ static void reg_launch(marex_ctx* ctx, const T* x, long t0, long Tb, long C, int
                        const float* wf, const float* anom, const float* thr, const int* doy, int n_doy, long long* area, u64* cnt,
                        double* sums, unsigned* vmax, u64* cat_cnt, long long* cat_area, u64* status) {
     const long wg = 4L * 64 * V * reg_iters<V>::n;
-    const dim3 grid((unsigned)((C + wg - 1) / wg), (unsigned)(Tb < REG_TSTRIDE ? Tb : REG_TSTRIDE)), block(256);
+    const dim3 grid = slice_grid(Tb, C, wg, REG_TSTRIDE), block(256);
 #define REG_GO(LEVEL)                                                                                                         \
     hipLaunchKernelGGL((k_regional_series<T, V, LEVEL>), grid, block, 0, ctx->stream, x, t0, Tb, C, match, reg, R, q, wf, anom, \
                        thr, doy, n_doy, area, cnt, sums, vmax, cat_cnt, cat_area, status)

@@ -1419,11 +1419,35 @@ class HotPath:
     def _host(t: Optional[torch.Tensor], dt):
         return None if t is None else t.cpu().numpy().view(dt)
 
+    def _cell_vector(self, what: str, name: str, v, torch_dtype, n: int, upload=False, typ: Optional[str] = None, noun: str = "values"):
+        """``v`` (None stays None) as the contiguous ``torch_dtype`` ``[n]`` tensor on the engine's device that a kernel reads:
+        another dtype (``typ`` in the refusal), shape, layout or device is refused.  ``upload``: a host array of that dtype and
+        shape (``n noun`` in its refusal) is uploaded; ``"later"``: only a host array is taken, and returned for the caller to upload."""
+        kind = str(torch_dtype).replace("torch.", "")
+        if v is None:
+            return None
+        if upload == "later" or (upload and not isinstance(v, torch.Tensor)):
+            h = np.ascontiguousarray(v)
+            if h.dtype != np.dtype(kind) or h.shape != (n,):
+                raise ProcessingError(f"{what}: {name} must be {n} {kind} {noun}", details=f"got {h.dtype} {h.shape}")
+            return h if upload == "later" else self._dev(h)
+        if v.dtype != torch_dtype or tuple(v.shape) != (n,) or not v.is_contiguous() or v.device != self.device:
+            raise ProcessingError(f"{what}: {name} must be a contiguous {typ or torch_dtype} [{n}] tensor on the engine's device",
+                                  details=f"got {v.dtype} {tuple(v.shape)} on {v.device}")
+        return v
+
     def _weights_check(self, what: str, weights: Optional[torch.Tensor], Cn: int) -> None:
-        if weights is not None and (weights.dtype != torch.float32 or tuple(weights.shape) != (Cn,) or not weights.is_contiguous()
-                                    or weights.device != self.device):
-            raise ProcessingError(f"{what}: the weights must be a contiguous float32 [{Cn}] tensor on the engine's "
-                                  f"device", details=f"got {weights.dtype} {tuple(weights.shape)} on {weights.device}")
+        self._cell_vector(what, "the weights", weights, torch.float32, Cn, typ="float32")
+
+    @staticmethod
+    def _area_q_check(what: str, q, Cn: int) -> np.ndarray:
+        """The host ``q``, contiguous: ``Cn`` non-negative int64 fixed-point areas whose sum, so any sum of them, is below 2^62."""
+        qh = np.ascontiguousarray(q)
+        if qh.dtype != np.int64 or qh.shape != (Cn,) or (qh < 0).any() or int(qh.max()) >= 2**62 or \
+                (int((qh >> 32).sum()) << 32) + int((qh & 0xFFFFFFFF).sum()) >= 2**62:  # the exact sum, in halves
+            raise ProcessingError(f"{what}: q must be {Cn} non-negative int64 areas whose sum stays below 2^62",
+                                  details=f"got {qh.dtype} {qh.shape}")
+        return qh
 
     def _thresholds_check(self, what: str, thr: Optional[torch.Tensor], doy, Cn: int, sentence: str) -> None:
         """``thr`` is float32 ``[n_doy, Cn]`` and ``doy`` comes with it; ``sentence`` is the refusal."""
@@ -1471,6 +1495,28 @@ class HotPath:
     def _slot_tables(self, tmin_h: np.ndarray, off: np.ndarray) -> dict:
         """The ``"tmin"``, ``"off"`` and ``"plan"`` entries of the accumulators over event slots."""
         return {"tmin": self._dev(np.clip(tmin_h, 0, 2**31 - 1).astype(np.int32)), "off": self._dev(off), "plan": off}
+
+    @staticmethod
+    def _slot_acc_check(what: str, acc: dict, slots: str, alloc: int, off, n_doy: Optional[int] = None, weighted: bool = False):
+        """The accumulators ``acc`` (``slots``: their entry by slot) were planned for these spans, ``n_doy`` rows and weights."""
+        there = int(acc[slots].shape[0])
+        same = there == alloc and np.array_equal(acc["plan"], off)
+        if n_doy is None and not same:
+            raise ProcessingError(f"{what}: the accumulators were planned for other spans", details=f"{there} slots there, {alloc} here")
+        if n_doy is not None and (not same or acc["n_doy"] != n_doy or (acc["area"] is not None) != weighted):
+            raise ProcessingError(f"{what}: the accumulators were planned for another call",
+                                  details=f"{there} slots and {acc['n_doy']} threshold rows there, {alloc} and {n_doy} here")
+
+    @staticmethod
+    def _slot_status(what: str, acc: dict, n_doy: Optional[int] = None) -> None:
+        """The host read of ``status``: cells outside their event's declared span and, with ``n_doy``, under a lost step label."""
+        status = [int(v) for v in acc["status"].cpu().numpy()]
+        if status[0]:
+            raise ProcessingError(f"{what}: {status[0]} cells belong to an event outside its declared span of timesteps",
+                                  details="ev_tmin / ev_tmax do not cover the field; the cells were counted, not accumulated")
+        if n_doy is not None and status[1]:
+            raise ProcessingError(f"{what}: {status[1]} event cells lie under a step label outside its range",
+                                  details=f"doy must hold 0 .. {n_doy - 1}; the cells were counted, nothing was read out of range")
 
     @staticmethod
     def _table_bytes(tabs: dict) -> int:
@@ -1529,18 +1575,14 @@ class HotPath:
             acc = {"cnt": self._zeros("int_cnt", (alloc, 2), torch.int64), "sums": self._zeros("int_sums", (alloc, 2), torch.float64),
                    "vmax": self._zeros("int_vmax", (alloc,), torch.int32), "status": self._zeros("int_status", (1,), torch.int64),
                    **self._slot_tables(tmin_h, off)}
-        elif tuple(acc["cnt"].shape) != (alloc, 2) or not np.array_equal(acc["plan"], off):
-            raise ProcessingError("event_intensity: the accumulators were planned for other spans",
-                                  details=f"{tuple(acc['cnt'].shape)[0]} slots there, {alloc} here")
+        else:
+            self._slot_acc_check("event_intensity", acc, "cnt", alloc, off)
         self.call("marex_event_intensity_f32", ids, anom, t0, Tb, Cn, n_ev, acc["tmin"], acc["off"], alloc, weights,
                   acc["cnt"], acc["sums"], acc["vmax"], acc["status"])
         out = {"off": off, "acc": acc}
         if not finish:
             return out
-        bad = int(acc["status"].item())
-        if bad:
-            raise ProcessingError(f"event_intensity: {bad} cells belong to an event outside its declared span of timesteps",
-                                  details="ev_tmin / ev_tmax do not cover the field; the cells were counted, not accumulated")
+        self._slot_status("event_intensity", acc)
         out.update(cnt=acc["cnt"][:n_slots].cpu().numpy(), sums=acc["sums"][:n_slots].cpu().numpy(),
                    vmax=key_float(acc["vmax"][:n_slots].cpu().numpy().view(np.uint32)))  # key 0: a NaN
         return out
@@ -1563,9 +1605,7 @@ class HotPath:
             raise ProcessingError(f"event_shapes: {Cn} cells per slice, ny * nx = {ny * nx}")
         for name, v, dt, n in (("mask", mask, torch.uint8, Cn), ("area_q", area_q, torch.int64, Cn),
                                ("ns_q", ns_q, torch.int64, ny + 1), ("ew_q", ew_q, torch.int64, ny)):
-            if v is not None and (v.dtype != dt or tuple(v.shape) != (n,) or not v.is_contiguous() or v.device != self.device):
-                raise ProcessingError(f"event_shapes: {name} must be a contiguous {dt} [{n}] tensor on the engine's device",
-                                      details=f"got {v.dtype} {tuple(v.shape)} on {v.device}")
+            self._cell_vector("event_shapes", name, v, dt, n)
         if (ns_q is None) != (ew_q is None):
             raise ProcessingError("event_shapes: ns_q and ew_q come together")
         tmin_h, n_ev, t0, off, n_slots, alloc = self._event_slots("event_shapes", ev_tmin, ev_tmax, t0)
@@ -1578,18 +1618,14 @@ class HotPath:
             box[:, 1::2] = -1
             acc = {"mom": self._zeros("shp_mom", (alloc, 16), torch.int64), "box": box,
                    "status": self._zeros("shp_status", (1,), torch.int64), **self._slot_tables(tmin_h, off)}
-        elif tuple(acc["mom"].shape) != (alloc, 16) or not np.array_equal(acc["plan"], off):
-            raise ProcessingError("event_shapes: the accumulators were planned for other spans",
-                                  details=f"{tuple(acc['mom'].shape)[0]} slots there, {alloc} here")
+        else:
+            self._slot_acc_check("event_shapes", acc, "mom", alloc, off)
         self.call("marex_event_shapes_i32", ids, t0, Tb, ny, nx, int(bool(regional)), n_ev, acc["tmin"], acc["off"], alloc,
                   mask, area_q, ns_q, ew_q, acc["mom"], acc["box"], acc["status"])
         out = {"off": off, "acc": acc}
         if not finish:
             return out
-        bad = int(acc["status"].item())
-        if bad:
-            raise ProcessingError(f"event_shapes: {bad} cells belong to an event outside its declared span of timesteps",
-                                  details="ev_tmin / ev_tmax do not cover the field; the cells were counted, not accumulated")
+        self._slot_status("event_shapes", acc)
         out.update(mom=acc["mom"][:n_slots].cpu().numpy(), box=acc["box"][:n_slots].cpu().numpy())
         return out
 
@@ -1624,11 +1660,8 @@ class HotPath:
                    "area": self._zeros("cat_area", (alloc, 6), torch.float64) if weighted else None,
                    "status": self._zeros("cat_status", (2,), torch.int64), **self._slot_tables(tmin_h, off),
                    "n_doy": n_doy, **self._upload_tables(tabs)}
-        elif tuple(acc["cnt"].shape) != (alloc, 7) or not np.array_equal(acc["plan"], off) or acc["n_doy"] != n_doy or \
-                (acc["area"] is not None) != weighted:
-            raise ProcessingError("event_categories: the accumulators were planned for another call",
-                                  details=f"{tuple(acc['cnt'].shape)[0]} slots and {acc['n_doy']} threshold rows there, {alloc} "
-                                          f"and {n_doy} here")
+        else:
+            self._slot_acc_check("event_categories", acc, "cnt", alloc, off, n_doy, weighted)
         if acc["len"]["doy"] < t0 + Tb:
             raise ProcessingError(f"event_categories: doy has {acc['len']['doy']} labels, the window ends at step {t0 + Tb}")
         self.call("marex_event_categories_f32", ids, anom, t0, Tb, Cn, n_ev, acc["tmin"], acc["off"], alloc, thr,
@@ -1636,13 +1669,7 @@ class HotPath:
         out: Dict[str, object] = {"off": off, "acc": acc}
         if not finish:
             return out
-        bad, lost = (int(v) for v in acc["status"].cpu().numpy())
-        if bad:
-            raise ProcessingError(f"event_categories: {bad} cells belong to an event outside its declared span of timesteps",
-                                  details="ev_tmin / ev_tmax do not cover the field; the cells were counted, not accumulated")
-        if lost:
-            raise ProcessingError(f"event_categories: {lost} event cells lie under a step label outside its range",
-                                  details=f"doy must hold 0 .. {n_doy - 1}; the cells were counted, nothing was read out of range")
+        self._slot_status("event_categories", acc, n_doy)
         out.update(cat_cnt=acc["cnt"][:n_slots].cpu().numpy(),
                    cat_area=acc["area"][:n_slots].cpu().numpy() if weighted else None)
         return out
@@ -2011,17 +2038,8 @@ class HotPath:
         plan = (T, R, Cn, n_doy, match, q is not None, wf is not None, anom is not None)
         if acc is None:
             tabs = label_tables("regional_series", (("reg", reg, Cn), ("doy", doy if cats else None, None)))
-            qh = wh = None
-            if q is not None:
-                qh = np.ascontiguousarray(q)
-                if qh.dtype != np.int64 or qh.shape != (Cn,) or (qh < 0).any() or int(qh.max()) >= 2**62 or \
-                        (int((qh >> 32).sum()) << 32) + int((qh & 0xFFFFFFFF).sum()) >= 2**62:  # the exact sum, in halves
-                    raise ProcessingError(f"regional_series: q must be {Cn} non-negative int64 areas whose sum stays below 2^62",
-                                          details=f"got {qh.dtype} {qh.shape}")
-            if wf is not None:
-                wh = np.ascontiguousarray(wf)
-                if wh.dtype != np.float32 or wh.shape != (Cn,):
-                    raise ProcessingError(f"regional_series: wf must be {Cn} float32 weights", details=f"got {wh.dtype} {wh.shape}")
+            qh = None if q is None else self._area_q_check("regional_series", q, Cn)  # checked here, uploaded once it fits
+            wh = self._cell_vector("regional_series", "wf", wf, torch.float32, Cn, upload="later", noun="weights")
             slots_b = self.regional_slot_bytes(T, R, anom is not None, cats, q is not None)
             self._check_fits(slots_b + 16 + self._table_bytes(tabs) + (8 * Cn if q is not None else 0) +
                              (4 * Cn if wf is not None else 0), "regional series",
@@ -2130,31 +2148,13 @@ class HotPath:
             raise ProcessingError("event_exposure: weights need the anomalies")
         if anom is not None:
             self._anomaly_window_check("event_exposure", anom, Tb, Cn)
-
-        def table(name, v, dt, tdt):  # a host vector is checked and uploaded, a tensor is checked
-            if v is None:
-                return None
-            if isinstance(v, torch.Tensor):
-                if v.dtype != tdt or tuple(v.shape) != (Cn,) or not v.is_contiguous() or v.device != self.device:
-                    raise ProcessingError(f"event_exposure: {name} must be a contiguous {tdt} [{Cn}] tensor on the engine's device",
-                                          details=f"got {v.dtype} {tuple(v.shape)} on {v.device}")
-                return v
-            h = np.ascontiguousarray(v)
-            if h.dtype != dt or h.shape != (Cn,):
-                raise ProcessingError(f"event_exposure: {name} must be {Cn} {np.dtype(dt).name} values", details=f"got {h.dtype} {h.shape}")
-            if name == "q" and ((h < 0).any() or int(h.max()) >= 2**62 or
-                                (int((h >> 32).sum()) << 32) + int((h & 0xFFFFFFFF).sum()) >= 2**62):  # the exact sum, in halves
-                raise ProcessingError(f"event_exposure: q must be {Cn} non-negative int64 areas whose sum stays below 2^62")
-            return self._dev(h)
-
-        reg_d = table("rank", rank, np.int32, torch.int32)
-        q_d = table("q", q, np.int64, torch.int64)
-        w_d = table("wf", wf, np.float32, torch.float32)
+        from .exposure import _no_records  # the front end of this method: it imports the engine only when it runs
+        if q is not None and not isinstance(q, torch.Tensor):  # a host vector is checked and uploaded, a tensor is checked
+            self._area_q_check("event_exposure", q, Cn)
+        reg_d, q_d, w_d = (self._cell_vector("event_exposure", name, v, dt, Cn, upload=True)
+                           for name, v, dt in (("rank", rank, torch.int32), ("q", q, torch.int64), ("wf", wf, torch.float32)))
         an, ar = anom is not None, q_d is not None
-        empty = {"t": np.zeros(0, np.int64), "rank": np.zeros(0, np.int32), "id": np.zeros(0, np.int32),
-                 "cells": np.zeros(0, np.int64), "finite": np.zeros(0, np.int64), "area": np.zeros(0, np.int64),
-                 "sums": np.zeros((0, 2), np.float64) if an else None, "vmax": np.zeros(0, np.float32) if an else None,
-                 "runs": 0, "cap": 0, "table_bytes": 0}
+        empty = dict(_no_records(an), runs=0, cap=0, table_bytes=0)
         status = self._buf(None, "exp_status", (8,), torch.int64, self.device)
         self.call("marex_event_exposure_count_i32", ids, Tb, Cn, reg_d, R, status)
         s = status.cpu().numpy()

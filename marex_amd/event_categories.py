@@ -15,9 +15,9 @@ from typing import Optional
 import numpy as np
 
 from . import _stream, calendar, occurrence as mo
-from ._stream import _I32_MAX, _Windows, _check_block_steps
-from .exceptions import ProcessingError, TrackingError
-from .intensity import _event_spans, _time_of_max_values, _validate
+from ._stream import _I32_MAX, _Windows, _check_block_steps, event_spans, pad_events, slot_index, tracker_time, walk_event_slots
+from .exceptions import TrackingError
+from .intensity import _time_of_max_values, _validate
 from .local_intensity import CATEGORIES, _device_thresholds, _threshold_layout, _thresholds_copied
 from .track import _tensor_of
 
@@ -27,12 +27,9 @@ SLOT_BYTES = 7 * 8 + 6 * 8
 
 def _plan(ID_field, dat_anomaly, thresholds, cell_areas, block_steps, time: Optional[tuple]):
     """Everything that can be refused or derived without a device."""
-    p = {"block_steps": _check_block_steps(block_steps)}
-    shape, tname, tv, w = _validate(ID_field, dat_anomaly, cell_areas)
-    tcoord = None
-    if time is not None:  # the tracker's own names: (time dimension, time coordinate, values)
-        tname, tcoord, tv = time
-    T, C = shape[0], int(np.prod(shape[1:]))
+    p = {"block_steps": _check_block_steps(block_steps), **_validate(ID_field, dat_anomaly, cell_areas)}
+    tracker_time(p, time)
+    shape, T, C, tv = p["shape"], p["T"], p["C"], p["tv"]
     dims = tuple(getattr(ID_field, "dims", ()) or ()) or tuple(getattr(dat_anomaly, "dims", ()) or ())
     kind = _threshold_layout(thresholds, shape[1:], dims[1:] if dims else None)
     doy = np.zeros(T, np.int32)
@@ -43,7 +40,7 @@ def _plan(ID_field, dat_anomaly, thresholds, cell_areas, block_steps, time: Opti
     if T and C and (C >= _I32_MAX or T >= _I32_MAX):
         raise TrackingError(f"event_categories: a timestep of {C} cells or a record of {T} steps reaches 2^31 - 1",
                             details="the field may hold any number of cells, a single timestep and the time axis may not")
-    p.update(shape=shape, T=T, C=C, tname=tname, tcoord=tcoord, tv=np.asarray(tv), w=w, kind=kind, doy=doy,
+    p.update(tv=np.asarray(tv), kind=kind, doy=doy,
              n_doy=1 if kind == "none" else calendar.N_DOY,
              sdims=dims[1:] if dims else (("y", "x") if len(shape) == 3 else ("cells",)))
     return p
@@ -75,9 +72,7 @@ def _device_pass(p, ID_field, dat_anomaly, thresholds, return_field: bool, devic
             "the device already", ["Pass return_field=False"] if return_field else [])
 
     B = plan(0)  # before anything is uploaded: the windows of both passes
-    wins = [(a, min(T, a + B)) for a in range(0, T, B)]
-    tmin, tmax, kept = _event_spans(eng, ids_w, wins)
-    N = int(tmin.size) - 1
+    N, tmin, tmax, wins, kept = event_spans(eng, ids_w, T, B)
     if N <= 0:
         field = torch.zeros((T, C), dtype=torch.uint8, device=eng.device) if return_field else None
         return 0, tmin, np.zeros(2, np.int64), np.zeros((0, 7), np.int64), None, field
@@ -85,12 +80,8 @@ def _device_pass(p, ID_field, dat_anomaly, thresholds, return_field: bool, devic
     thr = _device_thresholds(eng, thresholds, p["kind"], n_doy, C)
     wd = None if w is None else torch.from_numpy(w).to(eng.device)
     field = HotPath._buf(None, "cat_field", (T, C), torch.uint8, eng.device) if return_field else None
-    acc = r = None
-    for i, (a, b) in enumerate(wins):
-        x = kept if kept is not None else ids_w.get(a, b)
-        r = eng.event_categories(x, an_w.get(a, b), tmin, tmax, thr, p["doy"], wd, t0=a, field=field, acc=acc,
-                                 finish=i == len(wins) - 1)
-        acc = r["acc"]
+    r = walk_event_slots(ids_w, wins, kept, lambda x, a, b, acc, finish: eng.event_categories(
+        x, an_w.get(a, b), tmin, tmax, thr, p["doy"], wd, t0=a, field=field, acc=acc, finish=finish))
     return N, tmin, r["off"], r["cat_cnt"], r["cat_area"], field
 
 
@@ -112,8 +103,7 @@ def _finish(p, N: int, tmin, off, cnt, area, per_timestep: bool):
     idc = {"ID": ("ID", np.arange(1, N + 1, dtype=np.int32))}
     cc = {"category": ("category", np.array(CATEGORIES))}
     tid = {p["tcoord"] or tname: (tname, tv), **idc, **cc}
-    e_of = np.repeat(np.arange(N + 1), np.diff(off)[:N + 1])
-    t_of = np.arange(e_of.size) - off[e_of] + tmin[e_of]
+    e_of, t_of = slot_index(off, tmin, N)
     cnt = cnt.astype(np.int64)
     here = cnt.sum(axis=1) > 0
     peak = step_peak(cnt)
@@ -170,13 +160,7 @@ def _event_categories(ID_field, dat_anomaly, thresholds, cell_areas, per_timeste
         N, tmin, off, cnt, area, field = _device_pass(p, ID_field, dat_anomaly, thresholds, bool(return_field), device)
     if area is None and weighted:
         area = np.zeros((cnt.shape[0], 6), np.float64)
-    if n_events is not None:
-        if N > n_events:
-            raise ProcessingError(f"event_categories: the ID field holds event {N}, the events Dataset ends at {n_events}")
-        if N < n_events:  # trailing events without a cell: no slot
-            tmin = np.concatenate([tmin, np.full(n_events - N, _I32_MAX, np.int64)])
-            off = np.concatenate([off[:N + 2], np.full(n_events - N, off[N + 1], np.int64)])
-            N = n_events
+    N, tmin, off = pad_events("event_categories", N, n_events, tmin, off)
     ds = _finish(p, N, tmin, off, cnt, area, bool(per_timestep))
     if return_field:
         on_device = type(field).__module__.startswith("torch")  # an empty field has a NumPy one

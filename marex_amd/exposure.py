@@ -15,10 +15,10 @@ import numpy as np
 
 from . import _stream, occurrence as mo
 from ._keys import float_key, key_float
-from ._stream import _I32_MAX, _Windows, _check_block_steps
+from ._stream import _I32_MAX, _Windows, _check_block_steps, pad_events, tracker_time, weighted_mean
 from .exceptions import ProcessingError, create_data_validation_error
 from .intensity import _time_of_max_values
-from .regional import _spatial, area_weight_table, region_ranks
+from .regional import region_ranks
 
 
 def _plan(ID_field, regions, cell_areas, dat_anomaly, mask, block_steps, time=None):
@@ -30,27 +30,12 @@ def _plan(ID_field, regions, cell_areas, dat_anomaly, mask, block_steps, time=No
                                            details="the exposure of an event is keyed by its ID; track the mask first")
     if regions is None:
         raise create_data_validation_error("event_exposure needs regions", details="an integer map over the spatial shape")
-    if time is not None and p["tv"] is None and len(time[2]) == p["T"]:
-        p["tv"] = np.asarray(time[2])
-    C = p["C"]
+    tracker_time(p, time, names=False)
     rvals, rank = region_ranks(regions, mask, p)
     R = int(rvals.size)
-    p.update(rvals=rvals, rank=rank, R=R, e=0, q=None, wf=None)
-    if cell_areas is not None:
-        a = _spatial(cell_areas, p, "cell_areas", row_vector=True)
-        if a.dtype.kind not in "fiu":
-            raise create_data_validation_error("cell_areas must be numbers", details=f"Found dtype {a.dtype}")
-        if C:
-            p["e"], p["q"] = area_weight_table(a)
-            p["wf"] = np.ascontiguousarray(a, dtype=np.float32)
-    ok = rank >= 0
-    p["region_cells"] = np.bincount(rank[ok], minlength=R).astype(np.int64)
-    if p["q"] is not None:
-        ra = np.zeros(R, np.int64)
-        np.add.at(ra, rank[ok], p["q"][ok])
-        p["region_q"] = ra
-    else:
-        p["region_q"] = p["region_cells"]
+    p.update(rvals=rvals, rank=rank, R=R)
+    p["e"], p["q"], p["wf"] = _stream.area_tables(cell_areas, p)
+    p["region_cells"], p["region_q"] = _stream.region_denominators(rank, p["q"], R)
     return p
 
 
@@ -200,13 +185,12 @@ def _derive(rec, p, N: int, tv, per_timestep: bool) -> dict:
         first = np.minimum(_first_where(key == kmax[seg], st, n), max(n - 1, 0)) if P else np.zeros(0, np.int64)
         pw, psa = _seq_sum(W, seg, P), _seq_sum(SA, seg, P)
         pfin = np.add.reduceat(r["finite"], st) if P else np.zeros(0, np.int64)
-        with np.errstate(invalid="ignore", divide="ignore"):
-            d.update({"pair_intensity_max": (("pair",), np.where(has, key_float(kmax), np.float32(np.nan)).astype(np.float32)),
-                      "pair_time_of_intensity_max": (("pair",), _time_of_max_values(tv, r["t"][first] if P else first, has)),
-                      "pair_intensity_integral": (("pair",), psa),
-                      "pair_intensity_mean": (("pair",), np.where((pfin > 0) & (pw != 0), psa / np.where(pw != 0, pw, 1.0), np.nan)),
-                      "pair_invalid_cells": (("pair",), (np.add.reduceat(r["cells"] - r["finite"], st) if P
-                                                         else np.zeros(0, np.int64)))})
+        d.update({"pair_intensity_max": (("pair",), np.where(has, key_float(kmax), np.float32(np.nan)).astype(np.float32)),
+                  "pair_time_of_intensity_max": (("pair",), _time_of_max_values(tv, r["t"][first] if P else first, has)),
+                  "pair_intensity_integral": (("pair",), psa),
+                  "pair_intensity_mean": (("pair",), weighted_mean(pfin > 0, pw, psa)),
+                  "pair_invalid_cells": (("pair",), (np.add.reduceat(r["cells"] - r["finite"], st) if P
+                                                     else np.zeros(0, np.int64)))})
     # per event: the pairs of an event are consecutive and in ascending region
     pe = _starts(pid)
     pe_id = pid[pe]
@@ -228,11 +212,9 @@ def _derive(rec, p, N: int, tv, per_timestep: bool) -> dict:
         d.update({"pair_record_offsets": (("pair_edge",), off), "record_time": (("record",), times(r["t"])),
                   "record_cells": (("record",), r["cells"]), "record_area": (("record",), to_area(S.astype(np.float64)))})
         if an:
-            with np.errstate(invalid="ignore", divide="ignore"):
-                mean = np.where((r["finite"] > 0) & (W != 0), SA / np.where(W != 0, W, 1.0), np.nan)
             d.update({"record_intensity_max": (("record",), r["vmax"].astype(np.float32)),
                       "record_intensity_integral": (("record",), SA.astype(np.float64)),
-                      "record_intensity_mean": (("record",), mean),
+                      "record_intensity_mean": (("record",), weighted_mean(r["finite"] > 0, W, SA)),
                       "record_invalid_cells": (("record",), r["cells"] - r["finite"])})
     return d
 
@@ -242,15 +224,9 @@ def _event_exposure(ID_field, regions, cell_areas, dat_anomaly, mask, per_timest
 
     p = _plan(ID_field, regions, cell_areas, dat_anomaly, mask, block_steps, time)
     rec = _device_pass(p, ID_field, dat_anomaly, device)
-    T = p["T"]
-    tv = np.arange(T) if p["tv"] is None else np.asarray(p["tv"])
-    if time is not None and len(time[2]) == T:
-        tv = np.asarray(time[2])
-    N = int(rec["id"].max()) if rec["id"].size else 0
-    if n_events is not None:
-        if N > n_events:
-            raise ProcessingError(f"event_exposure: the ID field holds event {N}, the events Dataset ends at {n_events}")
-        N = int(n_events)
+    tracker_time(p, time, fitting=True)
+    tv = np.arange(p["T"]) if p["tv"] is None else np.asarray(p["tv"])
+    N = pad_events("event_exposure", int(rec["id"].max()) if rec["id"].size else 0, n_events)[0]
     if N == _I32_MAX:
         raise ProcessingError("event_exposure: the per-event variables run over ID = 1 .. N, and N is 2^31 - 1",
                               details="renumber sparse IDs densely")

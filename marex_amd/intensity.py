@@ -13,13 +13,14 @@ from typing import Optional
 import numpy as np
 
 from ._keys import float_key, key_float  # noqa: F401 -- public here
-from ._stream import _I32_MAX, _Windows, _check_block_steps, _dtype_name, _kind, _plan_windows, _time_of
-from .exceptions import ProcessingError, TrackingError, create_data_validation_error
-from .track import _host
+from ._stream import (_I32_MAX, _Windows, _check_block_steps, _dtype_name, _kind, _plan_windows, _time_of, event_spans,
+                      pad_events, slot_index, spatial, tracker_time, walk_event_slots, weighted_mean)
+from .exceptions import TrackingError, create_data_validation_error
 
 
 def _validate(ID_field, dat_anomaly, cell_areas):
-    """Everything that can be refused without a device: ``(shape, time name, time values, weights float32 [C] or None)``."""
+    """Everything that can be refused without a device: the plan -- ``shape``, ``T``, ``C``, the time axis ``tname`` / ``tv``
+    and the weights ``w``, float32 ``[C]`` or None."""
     shape = tuple(int(k) for k in ID_field.shape)
     if len(shape) not in (2, 3):
         raise create_data_validation_error("ID_field must be (time, y, x) or (time, cells)", details=f"got shape {shape}")
@@ -46,52 +47,16 @@ def _validate(ID_field, dat_anomaly, cell_areas):
     tv = tv if tv is not None else tv_a if tv_a is not None else np.arange(T)
     w = None
     if cell_areas is not None:
-        a = np.asarray(_host(cell_areas))
-        sp = shape[1:]
-        if a.dtype.kind not in "fiu":
-            raise create_data_validation_error("cell_areas must be numbers", details=f"Found dtype {a.dtype}")
-        a = a.astype(np.float32)
-        if len(sp) == 2 and a.ndim == 2 and d_i and tuple(getattr(cell_areas, "dims", ())) == (d_i[2], d_i[1]):
-            a = a.T
-        if a.shape == sp or a.shape == (int(np.prod(sp)),):
-            a = a.reshape(-1)
-        elif len(sp) == 2 and a.shape == (sp[0],):
-            a = np.broadcast_to(a[:, None], sp).reshape(-1)
-        else:
-            raise create_data_validation_error("cell_areas do not match the spatial shape of ID_field",
-                                               details=f"cell_areas {a.shape}, a timestep {sp}")
-        if not np.isfinite(a).all() or (a < 0).any():
+        w = spatial(cell_areas, {"shape": shape, "labelled": bool(d_i), "sdims": d_i[1:]}, "cell_areas", True,
+                    "cell_areas do not match the spatial shape of ID_field", numbers=True).astype(np.float32)
+        if not np.isfinite(w).all() or (w < 0).any():
             raise create_data_validation_error("cell_areas must be finite and non-negative",
-                                               details=f"{int((~np.isfinite(a)).sum())} non-finite, {int((a < 0).sum())} negative")
-        w = np.ascontiguousarray(a, dtype=np.float32)
-    return shape, tname, tv, w
+                                               details=f"{int((~np.isfinite(w)).sum())} non-finite, {int((w < 0).sum())} negative")
+    return {"shape": shape, "T": T, "C": int(np.prod(shape[1:])), "tname": tname, "tv": tv, "w": w}
 
 
-def _event_spans(eng, ids_w, wins):
-    """The first pass over the field: ``(tmin, tmax, kept)``, the first and last step of the events 0..N (int64, entry 0
-    unused) and the window itself where the field is taken whole."""
-    kept = None
-    tmin, tmax = np.zeros(1, np.int64), np.zeros(1, np.int64)
-    tmin[0], tmax[0] = _I32_MAX, -1
-    for a, b in wins:
-        x = ids_w.get(a, b)
-        sp = eng.id_spans(x)
-        if len(wins) == 1:
-            kept = x
-        if sp is None:
-            continue
-        lo, hi = sp[0].astype(np.int64), sp[1].astype(np.int64)
-        if lo.size > tmin.size:
-            grow = lo.size - tmin.size
-            tmin = np.concatenate([tmin, np.full(grow, _I32_MAX, np.int64)])
-            tmax = np.concatenate([tmax, np.full(grow, -1, np.int64)])
-        seen = hi >= 0
-        n = lo.size
-        tmin[:n] = np.where(seen, np.minimum(tmin[:n], lo + a), tmin[:n])
-        tmax[:n] = np.where(seen, np.maximum(tmax[:n], hi + a), tmax[:n])
-        del x
-    tmin[0], tmax[0] = _I32_MAX, -1
-    return tmin, tmax, kept
+def _no_slots():
+    return 0, np.zeros(1, np.int64), np.zeros(2, np.int64), np.zeros((0, 2), np.int64), np.zeros((0, 2)), np.zeros(0, np.float32)
 
 
 def _device_slots(eng, ID_field, dat_anomaly, w, T: int, C: int, block_steps):
@@ -101,17 +66,13 @@ def _device_slots(eng, ID_field, dat_anomaly, w, T: int, C: int, block_steps):
     ids_w = _Windows(eng, ID_field, T, C, np.int32, True)
     an_w = _Windows(eng, dat_anomaly, T, C, np.float32, False)
     B = _plan_windows(eng, T, C, ids_w.upload_bytes_per_step + an_w.upload_bytes_per_step, block_steps)
-    wins = [(a, min(T, a + B)) for a in range(0, T, B)]
-    tmin, tmax, kept = _event_spans(eng, ids_w, wins)
-    N = int(tmin.size) - 1
+
+    N, tmin, tmax, wins, kept = event_spans(eng, ids_w, T, B)
     if N <= 0:
-        return 0, tmin, np.zeros(2, np.int64), np.zeros((0, 2), np.int64), np.zeros((0, 2)), np.zeros(0, np.float32)
+        return _no_slots()
     wd = None if w is None else torch.from_numpy(w).to(eng.device)
-    acc, r = None, None
-    for i, (a, b) in enumerate(wins):
-        x = kept if kept is not None else ids_w.get(a, b)
-        r = eng.event_intensity(x, an_w.get(a, b), tmin, tmax, wd, t0=a, acc=acc, finish=i == len(wins) - 1)
-        acc = r["acc"]
+    r = walk_event_slots(ids_w, wins, kept, lambda x, a, b, acc, finish: eng.event_intensity(
+        x, an_w.get(a, b), tmin, tmax, wd, t0=a, acc=acc, finish=finish))
     return N, tmin, r["off"], r["cnt"], r["sums"], r["vmax"]
 
 
@@ -139,14 +100,12 @@ def _finish(N: int, T: int, tmin, off, cnt, sums, vmax, tname: str, tv, per_time
     ids = np.arange(1, N + 1, dtype=np.int32)
     idc = {"ID": ("ID", ids)}
     tid = {tcoord or tname: (tname, tv), **idc}
-    e_of = np.repeat(np.arange(N + 1), np.diff(off)[:N + 1])
-    t_of = np.arange(e_of.size) - off[e_of] + tmin[e_of]
+    e_of, t_of = slot_index(off, tmin, N)
     fin, bad = cnt[:, 0], cnt[:, 1]
     W, S = sums[:, 0], sums[:, 1]
     here = (fin + bad) > 0
     some = fin > 0
-    with np.errstate(invalid="ignore", divide="ignore"):
-        ratio = np.where(some & (W != 0), S / np.where(W != 0, W, 1.0), np.nan)
+    ratio = weighted_mean(some, W, S)
     data = {}
     if per_timestep:
         def dense(v, dt, fill):
@@ -173,8 +132,7 @@ def _finish(N: int, T: int, tmin, off, cnt, sums, vmax, tname: str, tv, per_time
     np.add.at(cum, e_of[ok], ratio[ok])
     has_w = np.zeros(N + 1, bool)
     has_w[e_of[ok]] = True
-    with np.errstate(invalid="ignore", divide="ignore"):
-        emean = np.where(has & (sW != 0), sS / np.where(sW != 0, sW, 1.0), np.nan)
+    emean = weighted_mean(has, sW, sS)
     invalid = np.zeros(N + 1, np.int64)
     np.add.at(invalid, e_of, bad)
     data["event_duration"] = DataArray(duration, dims=("ID",), coords=idc)
@@ -189,30 +147,20 @@ def _finish(N: int, T: int, tmin, off, cnt, sums, vmax, tname: str, tv, per_time
 def _event_intensity(ID_field, dat_anomaly, cell_areas, per_timestep, block_steps, device, n_events: Optional[int] = None,
                      time: Optional[tuple] = None):
     block_steps = _check_block_steps(block_steps)
-    shape, tname, tv, w = _validate(ID_field, dat_anomaly, cell_areas)
-    tcoord = None
-    if time is not None:  # the tracker's own names: (time dimension, time coordinate, values)
-        tname, tcoord, tv = time
-    T = shape[0]
-    C = int(np.prod(shape[1:]))
+    p = _validate(ID_field, dat_anomaly, cell_areas)
+    tracker_time(p, time)
+    T, C = p["T"], p["C"]
     if T == 0 or C == 0:
-        N, tmin, off, cnt, sums, vmax = 0, np.zeros(1, np.int64), np.zeros(2, np.int64), np.zeros((0, 2), np.int64), \
-            np.zeros((0, 2)), np.zeros(0, np.float32)
+        N, tmin, off, cnt, sums, vmax = _no_slots()
     else:
         if C >= _I32_MAX or T >= _I32_MAX:
             raise TrackingError(f"event_intensity: a timestep of {C} cells or a record of {T} steps reaches 2^31 - 1",
                                 details="the field may hold any number of cells, a single timestep and the time axis may not")
         from .detect import get_engine
 
-        N, tmin, off, cnt, sums, vmax = _device_slots(get_engine(device), ID_field, dat_anomaly, w, T, C, block_steps)
-    if n_events is not None:
-        if N > n_events:
-            raise ProcessingError(f"event_intensity: the ID field holds event {N}, the events Dataset ends at {n_events}")
-        if N < n_events:  # trailing events without a cell: no slot
-            tmin = np.concatenate([tmin, np.full(n_events - N, _I32_MAX, np.int64)])
-            off = np.concatenate([off[:N + 2], np.full(n_events - N, off[N + 1], np.int64)])
-            N = n_events
-    return _finish(N, T, tmin, off, cnt, sums, vmax, tname, tv, bool(per_timestep), tcoord)
+        N, tmin, off, cnt, sums, vmax = _device_slots(get_engine(device), ID_field, dat_anomaly, p["w"], T, C, block_steps)
+    N, tmin, off = pad_events("event_intensity", N, n_events, tmin, off)
+    return _finish(N, T, tmin, off, cnt, sums, vmax, p["tname"], p["tv"], bool(per_timestep), p["tcoord"])
 
 
 def event_intensity(ID_field, dat_anomaly, cell_areas=None, per_timestep: bool = True, block_steps=None, device: int = 0):

@@ -15,47 +15,11 @@ from __future__ import annotations
 import numpy as np
 
 from . import _stream, calendar, occurrence as mo
-from ._stream import _I32_MAX, _Windows, _check_block_steps
+from ._stream import _I32_MAX, _Windows, _check_block_steps, area_weight_table, spatial, tracker_time, weighted_mean  # noqa: F401
 from .exceptions import create_data_validation_error
 from .local_intensity import CATEGORIES, _device_thresholds, _threshold_layout, _thresholds_copied
-from .track import _host
 
 MAX_REGIONS = 32767
-
-
-def area_weight_table(cell_areas):
-    """``(e, q)``: the fixed-point areas of the cells, ``q = rint(a * 2^e)`` int64 in the shape of ``cell_areas`` with
-    ``a = float64(cell_areas)`` and ``e = 61 - ceil(log2(sum(a)))`` -- the rule, and the bits, of row 0 of
-    ``track_mesh.mesh_weight_tables``: the sum of ``q`` over any set of cells stays below 2^62, so 64-bit integer sums
-    cannot overflow, and an area is ``ldexp(float64(S), -e)`` of its integer sum ``S``.  :class:`DataValidationError` for
-    an area that is negative or not finite, or areas that sum to zero.  Needs no GPU."""
-    a = np.ascontiguousarray(np.asarray(_host(cell_areas), dtype=np.float64))
-    flat = a.reshape(-1)
-    if flat.size == 0 or not np.isfinite(flat).all() or (flat < 0).any():
-        raise create_data_validation_error("cell_areas must be finite and non-negative",
-                                           details=f"{int((~np.isfinite(flat)).sum())} non-finite and {int((flat < 0).sum())} "
-                                                   f"negative of {flat.size} values")
-    total = float(flat.sum())
-    if not (total > 0 and np.isfinite(total)):
-        raise create_data_validation_error("cell_areas must have a positive, finite sum", details=f"sum {total}")
-    e = 61 - int(np.ceil(np.log2(total)))
-    return e, np.rint(np.ldexp(flat, e)).astype(np.int64).reshape(a.shape)
-
-
-def _spatial(v, p: dict, name: str, row_vector: bool = False):
-    """``v`` flat over the cells of a timestep: given in the spatial shape, flat, transposed under the field's own
-    dimension names, or -- ``row_vector`` -- as a ``[y]`` vector broadcast along x."""
-    a = np.asarray(_host(v))
-    sp = p["shape"][1:]
-    d = tuple(getattr(v, "dims", ()) or ())
-    if len(sp) == 2 and a.ndim == 2 and d and p["labelled"] and d == (p["sdims"][1], p["sdims"][0]):
-        a = a.T
-    if a.shape == sp or a.shape == (p["C"],):
-        return np.ascontiguousarray(a).reshape(-1)
-    if row_vector and len(sp) == 2 and a.shape == (sp[0],):
-        return np.ascontiguousarray(np.broadcast_to(a[:, None], sp)).reshape(-1)
-    raise create_data_validation_error(f"{name} does not match the spatial shape of the field",
-                                       details=f"{name} {a.shape}, a timestep {sp}")
 
 
 def region_ranks(regions, mask, p: dict):
@@ -66,7 +30,7 @@ def region_ranks(regions, mask, p: dict):
     if regions is None:
         rvals, rank = np.zeros(1, np.int64), np.zeros(C, np.int32)
     else:
-        r = _spatial(regions, p, "regions")
+        r = spatial(regions, p, "regions")
         if r.dtype.kind not in "iu":
             raise create_data_validation_error("regions must be an integer map", details=f"Found dtype {r.dtype}")
         r = r.astype(np.int64)
@@ -77,7 +41,7 @@ def region_ranks(regions, mask, p: dict):
         rank = np.full(C, -1, np.int32)
         rank[r >= 0] = inv.reshape(-1).astype(np.int32)
     if mask is not None:
-        m = _spatial(mask, p, "mask")
+        m = spatial(mask, p, "mask")
         if m.dtype.kind not in "biu":
             raise create_data_validation_error("mask must be boolean or integer", details=f"Found dtype {m.dtype}")
         rank = np.where(m != 0, rank, np.int32(-1)).astype(np.int32)
@@ -88,9 +52,8 @@ def _plan(field, regions, cell_areas, dat_anomaly, thresholds, mask, by, event_i
     """Everything that can be refused or derived without a device.  ``time``: the tracker's ``(time dimension, time
     coordinate, values)``; its values stand in where the fields carry no time coordinate."""
     p = {"block_steps": _check_block_steps(block_steps), **_stream.plan_field(field, "regional_series", dat_anomaly)}
-    if time is not None and p["tv"] is None and len(time[2]) == p["T"]:
-        p["tv"] = np.asarray(time[2])
-    T, C, tv = p["T"], p["C"], p["tv"]
+    tracker_time(p, time, names=False)
+    T, tv = p["T"], p["tv"]
     p["match"] = 0
     if event_id is not None:
         if p["kind"] == "m":
@@ -104,14 +67,7 @@ def _plan(field, regions, cell_areas, dat_anomaly, thresholds, mask, by, event_i
     if rvals.size == 0:
         rvals = np.zeros(1, np.int64)
     p.update(rvals=rvals, rank=rank, R=R)
-    p["e"], p["q"], p["wf"] = 0, None, None
-    if cell_areas is not None:
-        a = _spatial(cell_areas, p, "cell_areas", row_vector=True)
-        if a.dtype.kind not in "fiu":
-            raise create_data_validation_error("cell_areas must be numbers", details=f"Found dtype {a.dtype}")
-        if C:
-            p["e"], p["q"] = area_weight_table(a)
-            p["wf"] = np.ascontiguousarray(a, dtype=np.float32)
+    p["e"], p["q"], p["wf"] = _stream.area_tables(cell_areas, p)
     p["thr"] = None
     if thresholds is not None:
         if dat_anomaly is None:
@@ -124,15 +80,7 @@ def _plan(field, regions, cell_areas, dat_anomaly, thresholds, mask, by, event_i
             doy = (calendar._to_year_doy(tv)[1].astype(np.int32) - 1) if T else doy
         p["thr"] = (kind, doy, 1 if kind == "none" else calendar.N_DOY)
     p["grp"] = None if by is None else mo.group_labels(by, tv, T)
-    # the denominators: the cells and the area of every region, exact host integers
-    ok = rank >= 0
-    p["region_cells"] = np.bincount(rank[ok], minlength=R).astype(np.int64)
-    if p["q"] is not None:
-        ra = np.zeros(R, np.int64)
-        np.add.at(ra, rank[ok], p["q"][ok])
-        p["region_q"] = ra
-    else:
-        p["region_q"] = p["region_cells"]
+    p["region_cells"], p["region_q"] = _stream.region_denominators(rank, p["q"], R)
     return p
 
 
@@ -176,11 +124,9 @@ def _regional_series(field, regions, cell_areas, dat_anomaly, thresholds, mask, 
     p = _plan(field, regions, cell_areas, dat_anomaly, thresholds, mask, by, event_id, block_steps, time)
     r = _device_pass(p, field, dat_anomaly, thresholds, device)
     T, R, e, _ratio = p["T"], p["R"], p["e"], mo._ratio
-    tname, tcoord = p["tname"], p["tname"]
+    tracker_time(p, time, fitting=True)
+    tname, tcoord = p["tname"], p["tcoord"] or p["tname"]
     tv = np.arange(T) if p["tv"] is None else np.asarray(p["tv"])
-    if time is not None:  # the tracker's own names: (time dimension, time coordinate, values)
-        tname, tcoord = time[0], time[1]
-        tv = np.asarray(time[2]) if len(time[2]) == T else tv
     an, cats, areas = r["sums"] is not None, r["cat_cnt"] is not None, p["q"] is not None
     rc = {"region": ("region", p["rvals"])}
     tc = {tcoord: (tname, tv), **rc}
@@ -202,8 +148,7 @@ def _regional_series(field, regions, cell_areas, dat_anomaly, thresholds, mask, 
     if an:
         W, SA = r["sums"][..., 0], r["sums"][..., 1]
         some = cells > 0
-        with np.errstate(invalid="ignore", divide="ignore"):
-            data["intensity_mean"] = series(np.where(some & (W != 0), SA / np.where(W != 0, W, 1.0), np.nan))
+        data["intensity_mean"] = series(weighted_mean(some, W, SA))
         data["intensity_max"] = series(r["vmax"].astype(np.float32))
         data["intensity_integral"] = series(np.where(some, SA, np.nan))
         data["invalid_cells"] = series(r["cnt"][..., 1].astype(np.int64))

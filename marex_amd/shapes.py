@@ -17,10 +17,10 @@ from typing import Optional
 
 import numpy as np
 
-from ._stream import _I32_MAX, _Windows, _check_block_steps, _dtype_name, _kind, _plan_windows, _time_of
-from .exceptions import ConfigurationError, ProcessingError, TrackingError, create_data_validation_error
-from .intensity import _event_spans, _time_of_max_values
-from .regional import area_weight_table
+from ._stream import (_I32_MAX, _Windows, _check_block_steps, _dtype_name, _kind, _plan_windows, _time_of, area_weight_table,
+                      event_spans, pad_events, slot_index, spatial, tracker_time, walk_event_slots)
+from .exceptions import ConfigurationError, TrackingError, create_data_validation_error
+from .intensity import _time_of_max_values
 from .track import _host, _tensor_of
 
 MAX_SIDE = 65536  # the second moments are 64-bit sums: nx^2 n < 2^63 needs nx <= 2^16 beside n < 2^31
@@ -109,32 +109,18 @@ def _validate(ID_field, mask, cell_areas, edge_lengths, lat, lon):
             raise create_data_validation_error("Object IDs must be non-negative", details=f"smallest ID {lo}; 0 is background",
                                                data_info={"min_id": lo, "max_id": int(h.max())})
     tname, tv = _time_of(ID_field, T)
+    dims = tuple(getattr(ID_field, "dims", ()) or ())
     p = {"shape": shape, "T": T, "ny": ny, "nx": nx, "C": C, "tname": tname, "tv": tv if tv is not None else np.arange(T),
-         "mask": None, "area": None, "edges": None, "lat": None, "lon": None}
+         "labelled": bool(dims), "sdims": dims[1:], "mask": None, "area": None, "edges": None, "lat": None, "lon": None}
     if mask is not None:
-        m = np.asarray(_host(mask))
+        m = spatial(mask, p, "mask", mismatch="mask does not match the spatial shape of ID_field")
         if m.dtype != bool and m.dtype.kind not in "iu":
             raise create_data_validation_error("mask must be boolean (True: inside the domain)", details=f"Found dtype {m.dtype}")
-        if m.shape == (C,):
-            m = m.reshape(ny, nx)
-        if m.shape != (ny, nx):
-            raise create_data_validation_error("mask does not match the spatial shape of ID_field",
-                                               details=f"mask {m.shape}, a timestep {(ny, nx)}")
-        p["mask"] = np.ascontiguousarray(m != 0).view(np.uint8).reshape(-1)
+        p["mask"] = np.ascontiguousarray(m != 0).view(np.uint8)
     if cell_areas is not None:
-        a = np.asarray(_host(cell_areas))
-        if a.dtype.kind not in "fiu":
-            raise create_data_validation_error("cell_areas must be numbers", details=f"Found dtype {a.dtype}")
-        a = a.astype(np.float64)
-        if a.shape == (ny, nx) or a.shape == (C,):
-            a = a.reshape(-1)
-        elif a.shape == (ny,):
-            a = np.broadcast_to(a[:, None], (ny, nx)).reshape(-1)
-        else:
-            raise create_data_validation_error("cell_areas do not match the spatial shape of ID_field",
-                                               details=f"cell_areas {a.shape}, a timestep {(ny, nx)}")
+        a = spatial(cell_areas, p, "cell_areas", True, "cell_areas do not match the spatial shape of ID_field", numbers=True)
         if C:
-            p["area"] = area_weight_table(np.ascontiguousarray(a))
+            p["area"] = area_weight_table(a)  # in float64, whatever type the areas came in
     if edge_lengths is not None and C:
         p["edges"] = edge_weight_tables(edge_lengths, ny, nx)
     if (lat is None) != (lon is None):
@@ -148,26 +134,25 @@ def _validate(ID_field, mask, cell_areas, edge_lengths, lat, lon):
     return p
 
 
+def _no_slots():
+    return 0, np.zeros(1, np.int64), np.zeros(2, np.int64), np.zeros((0, 16), np.int64), np.zeros((0, 6), np.int32)
+
+
 def _device_slots(eng, ID_field, p: dict, regional: bool, block_steps):
     """The two passes over the field: the events' spans, then the sums.  ``(N, tmin, off, mom, box)`` on the host."""
     T, C, ny, nx = p["T"], p["C"], p["ny"], p["nx"]
     ids_w = _Windows(eng, ID_field, T, C, np.int32, True)
     B = _plan_windows(eng, T, C, ids_w.upload_bytes_per_step, block_steps, "event_shapes",
                       f"the ID field of {T} timesteps of {C} cells, 4 bytes per cell, as far as it is not on the device already")
-    wins = [(a, min(T, a + B)) for a in range(0, T, B)]
-    tmin, tmax, kept = _event_spans(eng, ids_w, wins)
-    N = int(tmin.size) - 1
+    N, tmin, tmax, wins, kept = event_spans(eng, ids_w, T, B)
     if N <= 0:
-        return 0, tmin, np.zeros(2, np.int64), np.zeros((0, 16), np.int64), np.zeros((0, 6), np.int32)
+        return _no_slots()
     dev = {"mask": None if p["mask"] is None else eng._dev(p["mask"]),
-           "area_q": None if p["area"] is None else eng._dev(p["area"][1].reshape(-1)),
+           "area_q": None if p["area"] is None else eng._dev(p["area"][1]),
            "ns_q": None if p["edges"] is None else eng._dev(p["edges"][1]),
            "ew_q": None if p["edges"] is None else eng._dev(p["edges"][2])}
-    acc, r = None, None
-    for i, (a, b) in enumerate(wins):
-        x = kept if kept is not None else ids_w.get(a, b)
-        r = eng.event_shapes(x, ny, nx, tmin, tmax, regional=regional, t0=a, acc=acc, finish=i == len(wins) - 1, **dev)
-        acc = r["acc"]
+    r = walk_event_slots(ids_w, wins, kept, lambda x, a, b, acc, finish: eng.event_shapes(
+        x, ny, nx, tmin, tmax, regional=regional, t0=a, acc=acc, finish=finish, **dev))
     return N, tmin, r["off"], r["mom"], r["box"]
 
 
@@ -231,8 +216,7 @@ def _finish(p: dict, N: int, tmin, off, mom, box, regional: bool, per_timestep: 
     ids = np.arange(1, N + 1, dtype=np.int32)
     idc = {"ID": ("ID", ids)}
     tid = {tcoord or tname: (tname, tv), **idc}
-    e_all = np.repeat(np.arange(N + 1), np.diff(off)[:N + 1])
-    t_all = np.arange(e_all.size) - off[e_all] + tmin[e_all]
+    e_all, t_all = slot_index(off, tmin, N)
     mom = np.asarray(mom).astype(np.int64, copy=False).reshape(-1, 16)
     box = np.asarray(box).reshape(-1, 6)
     here = mom[:, _N] > 0
@@ -384,23 +368,15 @@ def _event_shapes(ID_field, mask, cell_areas, edge_lengths, lat, lon, regional_m
                   n_events: Optional[int] = None, time: Optional[tuple] = None):
     block_steps = _check_block_steps(block_steps)
     p = _validate(ID_field, mask, cell_areas, edge_lengths, lat, lon)
-    tname, tv, tcoord = p["tname"], p["tv"], None
-    if time is not None:  # the tracker's own names: (time dimension, time coordinate, values)
-        tname, tcoord, tv = time
+    tracker_time(p, time)
     if p["T"] == 0 or p["C"] == 0:
-        N, tmin, off, mom, box = 0, np.zeros(1, np.int64), np.zeros(2, np.int64), np.zeros((0, 16), np.int64), np.zeros((0, 6), np.int32)
+        N, tmin, off, mom, box = _no_slots()
     else:
         from .detect import get_engine
 
         N, tmin, off, mom, box = _device_slots(get_engine(device), ID_field, p, bool(regional_mode), block_steps)
-    if n_events is not None:
-        if N > n_events:
-            raise ProcessingError(f"event_shapes: the ID field holds event {N}, the events Dataset ends at {n_events}")
-        if N < n_events:  # trailing events without a cell: no slot
-            tmin = np.concatenate([tmin, np.full(n_events - N, _I32_MAX, np.int64)])
-            off = np.concatenate([off[:N + 2], np.full(n_events - N, off[N + 1], np.int64)])
-            N = n_events
-    return _finish(p, N, tmin, off, mom, box, bool(regional_mode), bool(per_timestep), tname, tv, tcoord)
+    N, tmin, off = pad_events("event_shapes", N, n_events, tmin, off)
+    return _finish(p, N, tmin, off, mom, box, bool(regional_mode), bool(per_timestep), p["tname"], p["tv"], p["tcoord"])
 
 
 def event_shapes(ID_field, mask=None, cell_areas=None, edge_lengths=None, lat=None, lon=None, regional_mode: bool = False,

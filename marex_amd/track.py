@@ -1664,9 +1664,9 @@ class tracker(_MeshStages):  # noqa: N801 -- the reference's public name (marEx.
                     cx = np.where(seam, cxs, cx)
             lat, lon = np.asarray(self.lat), np.asarray(self.lon)
             # slot -> (timestep, event): event e owns off[e] .. off[e + 1] - 1, one slot per step from ev_tmin[e] on
-            off = r["off"]
-            e_of = np.repeat(np.arange(N + 1), np.diff(off))
-            t_of = np.arange(e_of.size) - off[e_of] + ev_tmin[e_of]
+            from ._stream import slot_index  # _stream imports this module
+
+            e_of, t_of = slot_index(r["off"], ev_tmin, N)
             dense = []
             for v, dt in ((r["gid"], np.int32), (area, np.float32), (np.interp(cy, np.arange(len(lat)), lat), np.float64),
                           (np.interp(cx, np.arange(len(lon)), lon), np.float64)):
