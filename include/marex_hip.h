@@ -993,6 +993,42 @@ int marex_event_exposure_i32(marex_ctx* ctx, const int32_t* ids, int64_t Tb, int
                              uint64_t* out_cnt, int64_t* out_area, double* out_sums, uint32_t* out_vmax);
 int marex_event_exposure_layout(int32_t* out);
 
+/* The join of two tracked fields: per (timestep, event of A, event of B) the cells that the two share and their area, by the
+ * scheme of the exposure functions above with a second streamed field in the place of the region map.
+ *
+ * Both functions take ids_a and ids_b int32 [Tb][C], one window of two tracked fields over the same cells (a cell belongs to
+ * event ids > 0 of its field; a negative cell belongs to none).  A cell is present where either field holds an event; the
+ * pairs (a, 0) and (0, b), the cells of an event that the other field leaves uncovered, are kept like any other, and no pair
+ * is (0, 0).  The key of a cell is a << (bits_b + bits_step) | b << bits_step | row with widths that the caller passes at
+ * run time: one 64-bit word for one compare-and-swap, never two words, a lock or a spin.  As integers the keys sort by
+ * (a, b, row).  Equal pairs of consecutive cells of a row form a run.
+ *
+ * marex_event_matching_count_i32: status uint64 [8] is zeroed, then status[0] = negative cells of A, status[1] = negative
+ *   cells of B, status[2] = runs (an upper bound of the distinct keys), status[3] = the largest ID of A, status[4] = the
+ *   largest ID of B (0: none): what the caller plans the widths and the table from.
+ * marex_event_matching_i32: every run is added to the entry of its key in a table of cap entries (a power of two >= 64; the
+ *   caller chooses cap >= 2 runs), which the function zeroes: keys uint64 [cap] (0 = empty), cnt uint64 [cap] (the cells),
+ *   and area int64 [cap] with q int64 [C] (the sum of the fixed-point areas q of the cells, read under present cells only;
+ *   q, area and out_area come together or not at all).  The widths must each be at least 1 and sum to at most 64, and Tb
+ *   at most 2^bits_step.  A run whose a needs more than bits_a bits, or whose b more than bits_b, adds its cells to
+ *   status[6] and is dropped before a key is formed: it is never mis-keyed.  A run that finds no entry within cap probes
+ *   sets status[5] and is dropped: nothing spins, nothing is written outside the table.  Then the occupied entries are
+ *   copied, in no particular order, to out_keys, out_cnt and out_area (out_cap entries each); status[7] = the occupied
+ *   entries, of which only the first out_cap are written.  status[0] .. [4] are left as the count pass set them.
+ * marex_event_matching_layout: out int32 [6] (host) = the cells of a piece, of a wave and of a workgroup per row, the rows
+ *   between two of a workgroup's, the most bits an ID takes (31) and the fewest that remain for the row (2).  Needs no
+ *   context and no device.
+ *
+ * -1: null pointer, empty shape, widths below 1 or above 64 together, cap no power of two >= 64, out_cap <= 0, area
+ * arguments given in part; -4: Tb above 2^bits_step or C of 2^31 - 1 or more.  Asynchronous on the context's stream. */
+int marex_event_matching_count_i32(marex_ctx* ctx, const int32_t* ids_a, const int32_t* ids_b, int64_t Tb, int64_t C,
+                                   uint64_t* status);
+int marex_event_matching_i32(marex_ctx* ctx, const int32_t* ids_a, const int32_t* ids_b, int64_t Tb, int64_t C,
+                             const int64_t* q, int bits_a, int bits_b, int bits_step, int64_t cap, uint64_t* keys,
+                             uint64_t* cnt, int64_t* area, uint64_t* status, int64_t out_cap, uint64_t* out_keys,
+                             uint64_t* out_cnt, int64_t* out_area);
+int marex_event_matching_layout(int32_t* out);
+
 /* The partition kernels of the split-and-merge stage on an unstructured mesh (tracker.split_and_merge_objects_parallel,
  * marEx/track.py:3804-4814, 5246-5419).  A slice is int32 [C], values <= 0 are background, C below 2^31 - 1.  u: float64
  * [3][C], the unit vectors of the cells; pv: float64 [3][n], the unit vectors of the parents' centroids.  "Nearest" is the

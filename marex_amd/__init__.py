@@ -22,6 +22,9 @@ gives the side lengths of a regular lat-lon grid for perimeters in km.
 ``event_exposure`` and ``tracker.event_exposure`` join the tracked events with any integer region map: per (event, region)
 pair the steps, the cell-steps and area-steps, the largest extent and the intensity of the event inside the region, per
 event its main region and the share outside every region, per region the events it saw -- a keyed accumulation on the device.
+``event_matching`` and ``tracker.event_matching`` join the events of two trackings of the same cells: per pair of events the
+steps, the cell-steps and area-steps of their overlap, its share of either event, the intersection over union and the onset
+and end lags, per event its partners and its matched share, and the hit rate, false-alarm ratio and critical success index.
 """
 from .detect import (
     compute_normalised_anomaly,
@@ -50,6 +53,7 @@ from .composites import event_composites
 from .trends import cell_trends
 from .regional import regional_series
 from .exposure import event_exposure
+from .matching import event_matching
 from .shapes import event_shapes, grid_edge_lengths
 from .track import tracker
 from .xr_compat import DataArray, Dataset
@@ -60,6 +64,6 @@ __all__ = [
     "ProcessingError", "DependencyError", "create_data_validation_error", "DataArray", "Dataset",
     "tracker", "TrackingError", "event_intensity", "event_occurrence", "local_intensity",
     "cell_events", "event_categories", "compound_events", "cell_trends", "regional_series",
-    "event_composites", "event_shapes", "grid_edge_lengths", "event_exposure",
+    "event_composites", "event_shapes", "grid_edge_lengths", "event_exposure", "event_matching",
 ]
 __version__ = "0.1.0"

@@ -139,6 +139,9 @@ PROTOTYPES = {
     "marex_event_exposure_count_i32": (_i32, [_p, _p, _i64, _i64, _p, _i32, _p]),
     "marex_event_exposure_i32": (_i32, [_p, _p, _i64, _i64, _p, _i32, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _p]),
     "marex_event_exposure_layout": (_i32, [_p]),
+    "marex_event_matching_count_i32": (_i32, [_p, _p, _p, _i64, _i64, _p]),
+    "marex_event_matching_i32": (_i32, [_p, _p, _p, _i64, _i64, _p, _i32, _i32, _i32, _i64, _p, _p, _p, _p, _i64, _p, _p, _p]),
+    "marex_event_matching_layout": (_i32, [_p]),
 }
 
 KERNEL_IDS = {

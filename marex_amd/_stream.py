@@ -3,7 +3,8 @@
 engine: what a ``[time, space]`` field says without a device, the windows it is walked in -- with or without a part that
 stays for the whole call -- and the way back to its spatial dimensions.  For the first five also the parser of a map or of
 ``cell_areas`` over space, the area table, the regions' denominators and the tracker's ``time`` triple; for the statistics over
-(timestep, event) slots (the first three, ``track`` and ``exposure`` in part) the two-pass walk, the slot index and the padding."""
+(timestep, event) slots (the first three, ``track`` and ``exposure`` in part) the two-pass walk, the slot index and the padding;
+for the keyed joins (``exposure``, ``matching``) the segment helpers of their sorted records."""
 from __future__ import annotations
 
 from typing import Optional
@@ -339,6 +340,61 @@ def weighted_mean(some, W, SA):
     """``SA / W`` where ``some`` holds and ``W`` is not 0, NaN elsewhere."""
     with np.errstate(invalid="ignore", divide="ignore"):
         return np.where(some & (W != 0), SA / np.where(W != 0, W, 1.0), np.nan)
+
+
+def _starts(*keys):
+    """The first index of every run of equal key tuples in sorted vectors."""
+    n = keys[0].size
+    if n == 0:
+        return np.zeros(0, np.int64)
+    new = np.zeros(n, bool)
+    new[0] = True
+    for k in keys:
+        new[1:] |= k[1:] != k[:-1]
+    return np.flatnonzero(new).astype(np.int64)
+
+
+def _int_sum_f64(S, starts):
+    """The float64 of the exact sum of the non-negative int64 ``S`` over the segments that begin at ``starts``: the sum is
+    carried in two halves of 32 bits, so that any number of terms below 2^62 cannot overflow, and converted once."""
+    return _halves_f64(*_int_sum_halves(S, starts))
+
+
+def _int_sum_halves(S, starts):
+    """``(hi, lo)`` int64 with ``hi * 2^32 + lo`` the exact sum of the non-negative int64 ``S`` over the segments that begin
+    at ``starts`` and ``0 <= lo < 2^32``.  Sums and differences of such pairs stay exact: add or subtract the halves and
+    pass them through :func:`_halves_norm`."""
+    if starts.size == 0:
+        return np.zeros(0, np.int64), np.zeros(0, np.int64)
+    return _halves_norm(np.add.reduceat(S >> 32, starts), np.add.reduceat(S & 0xFFFFFFFF, starts))
+
+
+def _halves_norm(hi, lo):
+    """The same integer ``hi * 2^32 + lo`` with ``0 <= lo < 2^32`` (``lo`` may come in negative: the shift floors)."""
+    return hi + (lo >> 32), lo & 0xFFFFFFFF
+
+
+def _halves_f64(hi, lo):
+    """The float64 of the non-negative integer ``hi * 2^32 + lo`` (normalised halves), rounded once."""
+    if hi.size == 0:
+        return np.zeros(0, np.float64)
+    small = hi < 2**30  # the whole sum fits int64: its conversion rounds once
+    out = ((np.where(small, hi, 0) << 32) + lo).astype(np.float64)
+    for k in np.flatnonzero(~small):  # rare: a Python integer, rounded once by float()
+        out[k] = float((int(hi[k]) << 32) + int(lo[k]))
+    return out
+
+
+def _first_where(hit, starts, n):
+    """Per segment the first index at which ``hit`` holds (``n`` where none does)."""
+    return np.minimum.reduceat(np.where(hit, np.arange(n), n), starts) if starts.size else np.zeros(0, np.int64)
+
+
+def _seq_sum(v, seg, n_seg):
+    """Per segment the float64 sum of ``v``, one element after the other in the order given (ascending time)."""
+    out = np.zeros(n_seg, np.float64)
+    np.add.at(out, seg, v)
+    return out
 
 
 def event_spans(eng, ids_w, T: int, B: int):

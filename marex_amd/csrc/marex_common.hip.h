@@ -197,6 +197,45 @@ __device__ __forceinline__ u64 splitmix64(u64 k) {
     return k ^ (k >> 31);
 }
 
+// The keyed tables of marex_event_exposure.hip and marex_event_matching.hip: keys u64 [cap], cap a power of two, 0 = empty,
+// linear probing from the splitmix64 home.  The entry of `key` (claimed by one CAS if it is new), or -1 after cap probes:
+// bounded, so a full table is the caller's status and never a spin.
+__device__ __forceinline__ long table_claim(u64* __restrict__ keys, long cap, u64 key) {
+    const u64 mask = (u64)cap - 1;
+    u64 h = splitmix64(key) & mask;
+    long p = 0;
+    for (; p < cap; ++p) {
+        const u64 prev = atomicCAS(&keys[h], 0ull, key);
+        if (prev == 0ull || prev == key) break;
+        h = (h + 1) & mask;
+    }
+    return p < cap ? (long)h : -1L;
+}
+
+// The occupied entries of such a table -> the out arrays, in no particular order; status[ST_OUT] = how many there are (more
+// than out_cap: the caller's sizing error, nothing is written past out_cap).  area, and sums with vmax, may be absent.
+template <int ST_OUT>
+__global__ void __launch_bounds__(256)
+k_table_compact(long cap, const u64* __restrict__ keys, const u64* __restrict__ cnt, const u64* __restrict__ area,
+                const double* __restrict__ sums, const unsigned* __restrict__ vmax, long out_cap, u64* __restrict__ status,
+                u64* __restrict__ out_keys, u64* __restrict__ out_cnt, u64* __restrict__ out_area, double* __restrict__ out_sums,
+                unsigned* __restrict__ out_vmax) {
+    for (long h = (long)blockIdx.x * 256 + threadIdx.x; h < cap; h += (long)gridDim.x * 256) {
+        const u64 k = keys[h];
+        if (!k) continue;
+        const u64 p = atomicAdd(&status[ST_OUT], 1ull);
+        if (p >= (u64)out_cap) continue;
+        out_keys[p] = k;
+        out_cnt[p] = cnt[h];
+        if (area) out_area[p] = area[h];
+        if (sums) {
+            out_sums[2 * p] = sums[2 * h];
+            out_sums[2 * p + 1] = sums[2 * h + 1];
+            out_vmax[p] = vmax[h];
+        }
+    }
+}
+
 // blocks of 256 threads of a grid-stride loop over n items
 static inline unsigned stride_grid(long n) { return (unsigned)(n < 256L * 8192 ? (n + 255) / 256 : 8192); }
 

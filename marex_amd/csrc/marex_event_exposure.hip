@@ -61,15 +61,8 @@ k_exp_pass(const int* __restrict__ ids, long Tb, long C, const int* __restrict__
         if (!cur) return;
         ++runs;
         if (INSERT && lane == 0) {
-            const u64 mask = (u64)cap - 1;
-            u64 h = splitmix64(cur) & mask;
-            long p = 0;
-            for (; p < cap; ++p) {  // bounded: a full table is a status, not a spin
-                const u64 prev = atomicCAS(&keys[h], 0ull, cur);
-                if (prev == 0ull || prev == cur) break;
-                h = (h + 1) & mask;
-            }
-            if (p < cap) {
+            const long h = table_claim(keys, cap, cur);  // bounded: a full table is a status, not a spin
+            if (h >= 0) {
                 atomicAdd(&cnt[h], ((u64)rf << 32) | (u64)rc);  // a step holds fewer than 2^31 cells: no carry between the halves
                 if (area) atomicAdd(&area[h], (u64)ra);
                 if (ANOM && rf) {
@@ -171,29 +164,6 @@ k_exp_pass(const int* __restrict__ ids, long Tb, long C, const int* __restrict__
     }
 }
 
-// occupied table entries -> the out arrays, in no particular order; status[3] = how many there are (more than out_cap: the
-// caller's sizing error, nothing is written past out_cap)
-__global__ void __launch_bounds__(256)
-k_exp_compact(long cap, const u64* __restrict__ keys, const u64* __restrict__ cnt, const u64* __restrict__ area,
-              const double* __restrict__ sums, const unsigned* __restrict__ vmax, long out_cap, u64* __restrict__ status,
-              u64* __restrict__ out_keys, u64* __restrict__ out_cnt, u64* __restrict__ out_area, double* __restrict__ out_sums,
-              unsigned* __restrict__ out_vmax) {
-    for (long h = (long)blockIdx.x * 256 + threadIdx.x; h < cap; h += (long)gridDim.x * 256) {
-        const u64 k = keys[h];
-        if (!k) continue;
-        const u64 p = atomicAdd(&status[EXP_ST_OUT], 1ull);
-        if (p >= (u64)out_cap) continue;
-        out_keys[p] = k;
-        out_cnt[p] = cnt[h];
-        if (area) out_area[p] = area[h];
-        if (sums) {
-            out_sums[2 * p] = sums[2 * h];
-            out_sums[2 * p + 1] = sums[2 * h + 1];
-            out_vmax[p] = vmax[h];
-        }
-    }
-}
-
 static inline dim3 exp_grid(long Tb, long C) {
     return slice_grid(Tb, C, EXP_WG_CELLS, EXP_TSTRIDE);
 }
@@ -272,7 +242,7 @@ extern "C" int marex_event_exposure_i32(marex_ctx* ctx, const int32_t* ids, int6
     }
     {
         LaunchTimer lt(ctx, MAREX_K_MORPH);
-        hipLaunchKernelGGL(k_exp_compact, dim3(stride_grid(cap)), dim3(256), 0, ctx->stream, (long)cap, (const u64*)keys,
+        hipLaunchKernelGGL(k_table_compact<EXP_ST_OUT>, dim3(stride_grid(cap)), dim3(256), 0, ctx->stream, (long)cap, (const u64*)keys,
                            (const u64*)cnt, (const u64*)area, (const double*)sums, (const unsigned*)vmax, (long)out_cap,
                            (u64*)status, (u64*)out_keys, (u64*)out_cnt, (u64*)out_area, out_sums, (unsigned*)out_vmax);
     }

@@ -2207,6 +2207,126 @@ class HotPath:
             out.update(sums=out_s[:n].cpu().numpy()[order], vmax=self._key_max(out_v[:n].cpu().numpy().view(np.uint32)[order]))
         return out
 
+    @staticmethod
+    def matching_layout() -> Dict[str, int]:
+        """What the kernels of ``marex_event_matching_*`` were compiled with (``marex_event_matching_layout``): the cells of
+        a ``piece``, a ``wave`` and a workgroup (``wg``) per row, the rows between two of a workgroup's (``row_stride``),
+        the most bits an ID takes (``id_bits``) and the fewest that remain for the step (``min_step_bits``).  Needs no device."""
+        out = (C.c_int32 * 6)()
+        if _lib.load().marex_event_matching_layout(out) != 0:
+            raise ProcessingError("matching_layout: the library refused the call")
+        return dict(zip(("piece", "wave", "wg", "row_stride", "id_bits", "min_step_bits"), (int(v) for v in out)))
+
+    @staticmethod
+    def matching_widths(max_a: int, max_b: int, Tb: int) -> tuple:
+        """``(bits_a, bits_b, bits_step)`` of the key of :meth:`event_matching` for a window of ``Tb`` steps whose largest
+        IDs are ``max_a`` and ``max_b``: the bit lengths of the two (at least 1 each) and, for the step, what the window
+        needs (at least 1) or what is left of 64 bits -- at least 2.  A window of more than ``2^bits_step`` steps is run in
+        pieces of that many."""
+        max_a, max_b, Tb = int(max_a), int(max_b), int(Tb)
+        if not (0 <= max_a < 2**31 and 0 <= max_b < 2**31 and Tb >= 1):
+            raise ProcessingError("matching_widths: IDs lie in 0 .. 2^31 - 1 and a window holds at least one step",
+                                  details=f"max_a = {max_a}, max_b = {max_b}, Tb = {Tb}")
+        ba, bb = max(1, max_a.bit_length()), max(1, max_b.bit_length())
+        return ba, bb, min(64 - ba - bb, max(1, (Tb - 1).bit_length()))
+
+    @staticmethod
+    def matching_key(step, a, b, widths) -> np.ndarray:
+        """The uint64 keys of ``(step within the launch, ID of A, ID of B)`` under ``widths``:
+        ``a << (bits_b + bits_step) | b << bits_step | step``."""
+        _, bb, bs = (int(w) for w in widths)
+        s, x, y = (np.asarray(v).astype(np.uint64) for v in (step, a, b))
+        return (x << np.uint64(bb + bs)) | (y << np.uint64(bs)) | s
+
+    @staticmethod
+    def matching_entry_bytes(areas: bool) -> int:
+        """The bytes of one table entry of :meth:`event_matching`: key and cells (16), the area (8)."""
+        return 16 + (8 if areas else 0)
+
+    def event_matching(self, ids_a: torch.Tensor, ids_b: torch.Tensor, t0: int = 0, q=None, cap: Optional[int] = None) -> Dict[str, object]:
+        """The (timestep, event of A, event of B) records of one window of two tracked fields
+        (``marex_event_matching_count_i32`` / ``marex_event_matching_i32``): ``ids_a`` and ``ids_b`` int32 ``[Tb, C]`` (a
+        cell belongs to event ``ids > 0`` of its field), the rows ``t0 .. t0 + Tb - 1``.  A cell is present where either
+        field holds an event; the cells of an event that the other field leaves uncovered are kept under the partner 0.
+        ``q`` (int64 ``[C]``, the fixed-point areas of ``regional.area_weight_table``; None: 1 per cell) is a host array or
+        a tensor on the engine's device.  ``cap`` overrides the planned table size (tests).
+
+        The key is one 64-bit word whose widths (:meth:`matching_widths`) come from the largest IDs the count pass found;
+        a window of more steps than the key's step takes is run as sub-windows of ``2^bits_step`` rows.
+
+        Returns host arrays sorted by ``(a, b, t)``: ``t`` int64 (global steps), ``a`` and ``b`` int32, ``cells`` int64,
+        ``area`` int64 (the sum of ``q``, or the cells); and ``runs``, ``cap``, ``table_bytes`` and ``widths``, what the count
+        pass found, the table took and the key was laid out with.  A negative ID raises the trackers' "Object IDs must be
+        non-negative" error naming the field; a table that the keys do not fit raises :class:`ProcessingError` and leaves the
+        engine as it was."""
+        Tb, Cn = self._ids_check(ids_a)
+        if self._ids_check(ids_b) != (Tb, Cn):
+            raise ProcessingError("event_matching: the two ID fields differ in shape",
+                                  details=f"ids_a {tuple(ids_a.shape)}, ids_b {tuple(ids_b.shape)}")
+        t0 = int(t0)
+        if t0 < 0 or Tb == 0 or Cn == 0:
+            raise ProcessingError("event_matching: t0 must not be negative and a window must hold at least one step of at least one cell",
+                                  details=f"t0 = {t0}, Tb = {Tb}, C = {Cn}")
+        from .matching import _no_records  # the front end of this method: it imports the engine only when it runs
+        if q is not None and not isinstance(q, torch.Tensor):  # a host vector is checked and uploaded, a tensor is checked
+            self._area_q_check("event_matching", q, Cn)
+        q_d = self._cell_vector("event_matching", "q", q, torch.int64, Cn, upload=True)
+        ar = q_d is not None
+        empty = dict(_no_records(), runs=0, cap=0, table_bytes=0, widths=None)
+        status = self._buf(None, "mat_status", (8,), torch.int64, self.device)
+        self.call("marex_event_matching_count_i32", ids_a, ids_b, Tb, Cn, status)
+        s = status.cpu().numpy()
+        runs = int(s[2])
+        for neg, name in ((int(s[0]), "ID_field_a"), (int(s[1]), "ID_field_b")):
+            if neg:
+                raise create_data_validation_error("Object IDs must be non-negative",
+                                                   details=f"{name}: {neg} negative cells; 0 is background",
+                                                   data_info={"field": name, "negative_cells": neg})
+        if runs == 0:
+            return empty
+        widths = self.matching_widths(int(s[3]), int(s[4]), Tb)
+        sub = 1 << widths[2]
+        planned = self.exposure_cap(runs)
+        cap = planned if cap is None else int(cap)
+        if cap < 64 or cap & (cap - 1):
+            raise ProcessingError(f"event_matching: cap={cap} is not a power of two >= 64")
+        per = self.matching_entry_bytes(ar)
+        n_out = min(runs, cap)
+        nbytes = per * (cap + n_out)
+        self._check_fits(nbytes, "event matching", f"a hash table of {cap} entries of {per} bytes for {runs} runs of equal "
+                         f"(timestep, event of A, event of B) keys of {widths[0]} + {widths[1]} + {widths[2]} bits, and {n_out} "
+                         "compacted entries")
+        dev = self.device
+        keys, out_k = (self._buf(None, "mat_" + n, (m,), torch.int64, dev) for n, m in (("keys", cap), ("out_keys", n_out)))
+        cnt, out_c = (self._buf(None, "mat_" + n, (m,), torch.int64, dev) for n, m in (("cnt", cap), ("out_cnt", n_out)))
+        area, out_a = ((self._buf(None, "mat_" + n, (m,), torch.int64, dev) for n, m in (("area", cap), ("out_area", n_out)))
+                       if ar else (None, None))
+        ba, bb, bs = widths
+        parts = []
+        for r0 in range(0, Tb, sub):
+            r1 = min(Tb, r0 + sub)
+            self.call("marex_event_matching_i32", ids_a[r0:r1], ids_b[r0:r1], r1 - r0, Cn, q_d, ba, bb, bs, cap, keys, cnt, area,
+                      status, n_out, out_k, out_c, out_a)
+            s = status.cpu().numpy()
+            n = int(s[7])
+            if s[6] != 0:
+                raise ProcessingError(f"event_matching: {int(s[6])} cells hold an ID beyond the {ba} and {bb} bits of the key",
+                                      details="the widths come from the count pass of the same window: an internal error")
+            if s[5] != 0 or not 0 <= n <= n_out:
+                raise ProcessingError(f"event_matching: the table of {cap} entries does not hold the keys of {runs} runs",
+                                      details=f"{n} entries were taken; a table planned by the engine holds {planned}")
+            k = out_k[:n].cpu().numpy().view(np.uint64)
+            parts.append((k >> np.uint64(bs), (k & np.uint64((1 << bs) - 1)).astype(np.int64) + (t0 + r0),
+                          out_c[:n].cpu().numpy(), out_a[:n].cpu().numpy() if ar else None))
+        pair, t, cells, areas = (np.concatenate([p[j] for p in parts]) if parts[0][j] is not None else None for j in range(4))
+        if pair.size == 0:
+            raise ProcessingError(f"event_matching: no entry for {runs} runs (internal sizing error)")
+        order = np.lexsort((t, pair))  # (a, b) is one integer; the sub-windows are in ascending time
+        pair, t, cells = pair[order], t[order], cells[order].astype(np.int64)
+        return dict(empty, runs=runs, cap=cap, table_bytes=nbytes, widths=widths, t=t,
+                    a=(pair >> np.uint64(bb)).astype(np.int32), b=(pair & np.uint64((1 << bb) - 1)).astype(np.int32),
+                    cells=cells, area=areas[order] if ar else cells.copy())
+
     def cell_event_records(self, acc: dict) -> Dict[str, object]:
         """The record buffers of a second pass of :meth:`cell_events`, from the accumulators of a finished summary pass:
         ``off`` int64 ``[C + 1]`` (the exclusive scan of the events per cell, summed over the groups, on the device), ``n``

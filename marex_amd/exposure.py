@@ -15,7 +15,8 @@ import numpy as np
 
 from . import _stream, occurrence as mo
 from ._keys import float_key, key_float
-from ._stream import _I32_MAX, _Windows, _check_block_steps, pad_events, tracker_time, weighted_mean
+from ._stream import (_I32_MAX, _Windows, _check_block_steps, _first_where, _int_sum_f64, _seq_sum, _starts, pad_events, tracker_time,
+                      weighted_mean)
 from .exceptions import ProcessingError, create_data_validation_error
 from .intensity import _time_of_max_values
 from .regional import region_ranks
@@ -91,45 +92,6 @@ def _device_pass(p, ID_field, dat_anomaly, device):
         order = np.lexsort((rec["rank"], rec["id"]))
         rec = {k: (None if v is None else v[order]) for k, v in rec.items()}
     return rec
-
-
-def _starts(*keys):
-    """The first index of every run of equal key tuples in sorted vectors."""
-    n = keys[0].size
-    if n == 0:
-        return np.zeros(0, np.int64)
-    new = np.zeros(n, bool)
-    new[0] = True
-    for k in keys:
-        new[1:] |= k[1:] != k[:-1]
-    return np.flatnonzero(new).astype(np.int64)
-
-
-def _int_sum_f64(S, starts):
-    """The float64 of the exact sum of the non-negative int64 ``S`` over the segments that begin at ``starts``: the sum is
-    carried in two halves of 32 bits, so that any number of terms below 2^62 cannot overflow, and converted once."""
-    if starts.size == 0:
-        return np.zeros(0, np.float64)
-    hi = np.add.reduceat(S >> 32, starts)
-    lo = np.add.reduceat(S & 0xFFFFFFFF, starts)
-    hi, lo = hi + (lo >> 32), lo & 0xFFFFFFFF
-    small = hi < 2**30  # the whole sum fits int64: its conversion rounds once
-    out = ((np.where(small, hi, 0) << 32) + lo).astype(np.float64)
-    for k in np.flatnonzero(~small):  # rare: a Python integer, rounded once by float()
-        out[k] = float((int(hi[k]) << 32) + int(lo[k]))
-    return out
-
-
-def _first_where(hit, starts, n):
-    """Per segment the first index at which ``hit`` holds (``n`` where none does)."""
-    return np.minimum.reduceat(np.where(hit, np.arange(n), n), starts) if starts.size else np.zeros(0, np.int64)
-
-
-def _seq_sum(v, seg, n_seg):
-    """Per segment the float64 sum of ``v``, one element after the other in the order given (ascending time)."""
-    out = np.zeros(n_seg, np.float64)
-    np.add.at(out, seg, v)
-    return out
 
 
 def _derive(rec, p, N: int, tv, per_timestep: bool) -> dict:

@@ -1085,6 +1085,33 @@ class tracker(_MeshStages):  # noqa: N801 -- the reference's public name (marEx.
                                   details=f"{n} IDs from {np.asarray(events_ds['ID'].values)[:1]}")
         return _event_exposure(field, regions, time=(self.timedim, self.timecoord, self.time_values), n_events=n, **args)
 
+    def event_matching(self, events_ds, other, **kw):
+        """Which events of :meth:`run` are which events of a second tracking of the same cells
+        (:func:`marex_amd.matching.event_matching` has the arguments and the variables): ``events_ds["ID_field"]`` is field
+        A; ``other``, an events Dataset with ``ID_field`` or a bare field, is field B.  On this tracker's device and with
+        its time values, on grids and on meshes.  Unless passed, ``cell_areas`` are the tracker's areas, as in
+        :meth:`regional_series`.  The ``ID`` axes of the Datasets, where they exist, give ``Na`` and ``Nb`` and are checked
+        against what the pass found (:class:`ProcessingError`)."""
+        from .matching import _event_matching
+
+        kw.setdefault("device", self.device)
+        if "cell_areas" not in kw:
+            kw["cell_areas"] = np.asarray(_host(self.cell_area)) if self.unstructured_grid else getattr(self, "_cell_weights", None)
+        args = {k: kw.pop(k, d) for k, d in (("cell_areas", None), ("min_share", 0.0), ("per_timestep", False),
+                                             ("block_steps", None), ("device", None))}
+        if kw:
+            raise TypeError(f"event_matching() got an unexpected keyword argument {next(iter(kw))!r}")
+        fields, n = [], []
+        for ds, name in ((events_ds, "events"), (other, "other")):
+            is_ds = hasattr(ds, "data_vars")
+            fields.append(ds["ID_field"] if is_ds else ds)
+            n.append(int(np.asarray(ds["ID"].values).size) if is_ds and "ID" in ds else None)
+            if n[-1] is not None and not np.array_equal(np.asarray(ds["ID"].values), np.arange(1, n[-1] + 1)):
+                raise ProcessingError(f"event_matching: the ID axis of the {name} Dataset is not 1 .. N",
+                                      details=f"{n[-1]} IDs from {np.asarray(ds['ID'].values)[:1]}")
+        return _event_matching(fields[0], fields[1], time=(self.timedim, self.timecoord, self.time_values), n_events_a=n[0],
+                               n_events_b=n[1], **args)
+
     def _latlon_coords(self) -> dict:
         """The input's lat / lon as coordinate entries ``name -> (dims, host values)``."""
         ydim = self.xdim if self.unstructured_grid else self.ydim  # on a mesh lat runs over the cells too
