@@ -664,6 +664,39 @@ int marex_event_shapes_i32(marex_ctx* ctx, const int32_t* ids, int64_t t0, int64
                            const int64_t* area_q, const int64_t* ns_q, const int64_t* ew_q, uint64_t* mom, int32_t* box,
                            uint64_t* status);
 
+/* Shape of tracked events on an unstructured mesh of three-sided cells: per (timestep, event) the integer sums behind
+ * perimeter, coastal contact, axes on the sphere and centroid paths (this project's own definitions; the reference has
+ * nothing of the kind).
+ *
+ * marex_mesh_event_shapes_i64: ids int32 [Tb][C] are the rows t0 .. t0 + Tb - 1 of a mesh field; values outside 1 .. n_ev are
+ *   background.  n_ev, ev_tmin, ev_off, n_slots and the slot s of a cell as in marex_event_intensity_f32.  nbr int32 [3][C]:
+ *   the cell across the k-th side of cell c, 0-based; a value outside 0 .. C - 1 (-1 by convention) is "no neighbour" and is
+ *   never used as an index.  A side k of an event cell c with j = nbr[k][c] is exposed when there is no neighbour (then it is
+ *   also a border side) or when ids[j] of the same row differs from the cell's value as it stands (0 and numbers above n_ev
+ *   included); each of the three slots is tested on its own, so a neighbour listed twice counts twice.
+ *   mom uint64 [n_slots][16], per cell of the slot:
+ *     0 cells   1 .. 10 the sums of q[0][c] .. q[9][c] (q int64 [10][C]; rows 1 .. 9 are signed, the sums two's complement)
+ *     11 exposed sides   12 exposed sides without a neighbour (border)
+ *     13 exposed sides whose neighbour exists and is 0 in mask (uint8 [C], or NULL: none)
+ *     14 sum of len_q[k][c] over the exposed sides (int64 [3][C], or NULL: 0)
+ *     15 exposed sides whose neighbour holds a value above 0 (contact with another event)
+ *   box int32 [n_slots][6]: min and max of lat_k[c]; min and max of lon_k[c] over the cells with lon_k[c] < 0; min and max of
+ *   lon_k[c] over the cells with lon_k[c] >= 0 (lat_k, lon_k int32 [C], together or both NULL: box is left alone; atomic
+ *   minima and maxima; the caller fills the minima with INT_MAX and the maxima with INT_MIN first).
+ *   status uint64 [1].  The function only accumulates: the caller prepares mom (zero), box and status before the first block,
+ *   so a field is walked in time blocks into the same slots; the neighbours stay inside a row, so blocks need no halo.  A cell
+ *   whose event lies outside its declared span adds one to status[0] and nothing else: no slot index that was not
+ *   range-checked addresses mom or box.  The neighbours, the mask bytes, the table rows, the lengths and the keys are fetched
+ *   only under cells of an event.  Every sum is an integer: exact, and independent of any order and of the blocks.
+ *   Bounds: the caller scales q so that the sum of any row over any set of cells stays below 2^62 in magnitude, and len_q so
+ *   that the sum over any set of its entries does.
+ *   -1: null pointer, empty shape, t0 < 0, n_ev <= 0, n_slots <= 0, or lat_k / lon_k given in part; -4: C or t0 + Tb of
+ *   2^31 - 1 or more.  Asynchronous on the context's stream. */
+int marex_mesh_event_shapes_i64(marex_ctx* ctx, const int32_t* ids, int64_t t0, int64_t Tb, int64_t C, int n_ev,
+                                const int32_t* ev_tmin, const int64_t* ev_off, int64_t n_slots, const int32_t* nbr,
+                                const uint8_t* mask, const int64_t* q, const int64_t* len_q, const int32_t* lat_k,
+                                const int32_t* lon_k, uint64_t* mom, int32_t* box, uint64_t* status);
+
 /* Severity categories of tracked events (Hobday et al. 2018: moderate, strong, severe, extreme as multiples of the
  * threshold): the event field joined with the anomaly field and the day-of-year thresholds, per (timestep, event).
  *

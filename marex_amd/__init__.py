@@ -18,7 +18,10 @@ of every cell's events: count, sum, sum of squares, mean, standard deviation and
 ``event_shapes`` and ``tracker.event_shapes`` give the shape and the movement of every tracked event on a grid: bounding box
 and extent, exposed sides, perimeter and coastal contact, the axes, eccentricity and orientation of its second moments, and
 the path, displacement and speed of its centroid -- integer sums on the device, float64 on the host; ``grid_edge_lengths``
-gives the side lengths of a regular lat-lon grid for perimeters in km.
+gives the side lengths of a regular lat-lon grid for perimeters in km.  ``mesh_event_shapes`` -- and ``tracker.event_shapes`` of
+a mesh tracker -- give the same on an unstructured mesh of three-sided cells: exposed, border, coast and contact sides over
+the three neighbour slots, perimeter, a latitude / longitude box, axes from the second moments of the unit vectors on the
+sphere, and the great-circle path of the centroid.
 ``event_exposure`` and ``tracker.event_exposure`` join the tracked events with any integer region map: per (event, region)
 pair the steps, the cell-steps and area-steps, the largest extent and the intensity of the event inside the region, per
 event its main region and the share outside every region, per region the events it saw -- a keyed accumulation on the device.
@@ -55,6 +58,7 @@ from .regional import regional_series
 from .exposure import event_exposure
 from .matching import event_matching
 from .shapes import event_shapes, grid_edge_lengths
+from .shapes_mesh import mesh_event_shapes
 from .track import tracker
 from .xr_compat import DataArray, Dataset
 
@@ -65,5 +69,6 @@ __all__ = [
     "tracker", "TrackingError", "event_intensity", "event_occurrence", "local_intensity",
     "cell_events", "event_categories", "compound_events", "cell_trends", "regional_series",
     "event_composites", "event_shapes", "grid_edge_lengths", "event_exposure", "event_matching",
+    "mesh_event_shapes",
 ]
 __version__ = "0.1.0"

@@ -122,6 +122,7 @@ PROTOTYPES = {
     "marex_event_rename_i32": (_i32, [_p, _p, _i64, _i32, _i32, _p, _i64, _i32, _p, _p, _i64, _p, _p, _p, _p, _p]),
     "marex_event_intensity_f32": (_i32, [_p, _p, _p, _i64, _i64, _i64, _i32, _p, _p, _i64, _p, _p, _p, _p, _p]),
     "marex_event_shapes_i32": (_i32, [_p, _p, _i64, _i64, _i32, _i32, _i32, _i32, _p, _p, _i64, _p, _p, _p, _p, _p, _p, _p]),
+    "marex_mesh_event_shapes_i64": (_i32, [_p, _p, _i64, _i64, _i64, _i32, _p, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "marex_event_categories_f32": (_i32, [_p, _p, _p, _i64, _i64, _i64, _i32, _p, _p, _i64, _p, _p, _i32, _p, _p, _p, _p, _p]),
     "marex_occurrence_u8": (_i32, [_p, _p, _i64, _i64, _i64, _i32, _p, _i32, _p, _i32, _p, _i32, _p, _p, _p, _p]),
     "marex_occurrence_i32": (_i32, [_p, _p, _i64, _i64, _i64, _i32, _p, _i32, _p, _i32, _p, _i32, _p, _p, _p, _p]),

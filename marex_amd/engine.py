@@ -1629,6 +1629,49 @@ class HotPath:
         out.update(mom=acc["mom"][:n_slots].cpu().numpy(), box=acc["box"][:n_slots].cpu().numpy())
         return out
 
+    def mesh_event_shapes(self, ids: torch.Tensor, nbr: torch.Tensor, q: torch.Tensor, ev_tmin, ev_tmax,
+                          mask: Optional[torch.Tensor] = None, len_q: Optional[torch.Tensor] = None,
+                          lat_k: Optional[torch.Tensor] = None, lon_k: Optional[torch.Tensor] = None, t0: int = 0,
+                          acc: Optional[dict] = None, finish: bool = True) -> Dict[str, object]:
+        """Per (timestep, event) shape sums of the rows ``t0 .. t0 + Tb - 1`` of a tracked field on a mesh
+        (``marex_mesh_event_shapes_i64``): ``ids`` int32 ``[Tb, C]`` (events 1..n_ev, anything else background), the slots
+        declared by ``ev_tmin`` / ``ev_tmax`` as in :meth:`event_intensity`.  ``nbr``: int32 ``[3, C]``, 0-based, -1 for no
+        neighbour; ``q``: int64 ``[10, C]`` fixed-point weights; ``mask``: uint8 ``[C]`` (0: land) or None; ``len_q``: int64
+        ``[3, C]`` fixed-point side lengths or None; ``lat_k`` / ``lon_k``: int32 ``[C]`` coordinate keys, together or None
+        (``box`` then stays as it was filled).  The first block allocates the accumulators; a later block passes the
+        ``"acc"`` entry of the previous result, whatever the block length.  Returns ``off``, ``acc`` and -- unless ``finish``
+        is False -- ``mom`` int64 ``[n, 16]`` and ``box`` int32 ``[n, 6]`` (the layout of include/marex_hip.h).  A cell of an
+        event outside its declared span raises :class:`ProcessingError`."""
+        Tb, Cn = self._ids_check(ids)
+        for name, v, dt in (("mask", mask, torch.uint8), ("lat_k", lat_k, torch.int32), ("lon_k", lon_k, torch.int32)):
+            self._cell_vector("mesh_event_shapes", name, v, dt, Cn)
+        for name, v, dt, rows in (("nbr", nbr, torch.int32, 3), ("q", q, torch.int64, 10), ("len_q", len_q, torch.int64, 3)):
+            if v is not None and (v.dtype != dt or tuple(v.shape) != (rows, Cn) or not v.is_contiguous() or v.device != self.device):
+                raise ProcessingError(f"mesh_event_shapes: {name} must be a contiguous {dt} [{rows}, {Cn}] tensor on the engine's "
+                                      "device", details=f"got {v.dtype} {tuple(v.shape)} on {v.device}")
+        if nbr is None or q is None or (lat_k is None) != (lon_k is None):
+            raise ProcessingError("mesh_event_shapes: nbr and q are needed, and lat_k and lon_k come together")
+        tmin_h, n_ev, t0, off, n_slots, alloc = self._event_slots("mesh_event_shapes", ev_tmin, ev_tmax, t0)
+        if acc is None:
+            self._check_fits(152 * n_slots + 12 * (n_ev + 2), "mesh event shapes",
+                             f"{n_slots} (timestep, event) slots between each event's first and last timestep, 152 bytes each, "
+                             f"and the tables of {n_ev} events")
+            box = self._buf(None, "msh_box", (alloc, 6), torch.int32, self.device)
+            box[:, 0::2] = 2**31 - 1
+            box[:, 1::2] = -2**31
+            acc = {"mom": self._zeros("msh_mom", (alloc, 16), torch.int64), "box": box,
+                   "status": self._zeros("msh_status", (1,), torch.int64), **self._slot_tables(tmin_h, off)}
+        else:
+            self._slot_acc_check("mesh_event_shapes", acc, "mom", alloc, off)
+        self.call("marex_mesh_event_shapes_i64", ids, t0, Tb, Cn, n_ev, acc["tmin"], acc["off"], alloc, nbr, mask, q, len_q,
+                  lat_k, lon_k, acc["mom"], acc["box"], acc["status"])
+        out = {"off": off, "acc": acc}
+        if not finish:
+            return out
+        self._slot_status("mesh_event_shapes", acc)
+        out.update(mom=acc["mom"][:n_slots].cpu().numpy(), box=acc["box"][:n_slots].cpu().numpy())
+        return out
+
     def event_categories(self, ids: torch.Tensor, anom: torch.Tensor, ev_tmin, ev_tmax, thr: torch.Tensor, doy,
                          weights: Optional[torch.Tensor] = None, t0: int = 0, field: Optional[torch.Tensor] = None,
                          acc: Optional[dict] = None, finish: bool = False) -> Dict[str, object]:

@@ -88,7 +88,7 @@ def _validate(ID_field, mask, cell_areas, edge_lengths, lat, lon):
     if len(shape) == 2:
         raise ConfigurationError("event_shapes: shapes are gridded only",
                                  details=f"got a (time, cells) field of shape {shape}: a mesh has no rows, columns or cell "
-                                         "sides to measure; pass a (time, y, x) field")
+                                         "sides to measure; pass a (time, y, x) field, or measure a mesh with mesh_event_shapes")
     if len(shape) != 3:
         raise create_data_validation_error("ID_field must be (time, y, x)", details=f"got shape {shape}")
     if _kind(ID_field) != "i":

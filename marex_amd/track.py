@@ -999,13 +999,27 @@ class tracker(_MeshStages):  # noqa: N801 -- the reference's public name (marEx.
         variables) from ``events_ds["ID_field"]``, on this tracker's device and under its time names.  Unless passed:
         ``mask`` is the tracker's mask, ``regional_mode`` its own, ``cell_areas`` the float32 cell areas of the merge
         tracker's area pass (cells without them) and ``lat`` / ``lon`` the 1-D coordinates of the tracked field in degrees,
-        so that the path of the centroid comes in km.  Gridded trackers only (:class:`ConfigurationError` on a mesh).  The
-        ``ID`` axis of a merge tracker's Dataset is checked against what the pass found (:class:`ProcessingError`)."""
+        so that the path of the centroid comes in km.  The ``ID`` axis of a merge tracker's Dataset is checked against what
+        the pass found (:class:`ProcessingError`).  On a mesh tracker this is
+        :func:`marex_amd.shapes_mesh.mesh_event_shapes` (its variables and definitions) with the tracker's neighbours,
+        ``lat`` / ``lon`` in degrees, ``cell_areas`` and mask; ``edge_lengths``, ``radius_km``, ``per_timestep`` and
+        ``block_steps`` may be passed."""
         from .shapes import _event_shapes
 
         field = events_ds["ID_field"] if hasattr(events_ds, "data_vars") else events_ds
+        n = int(np.asarray(events_ds["ID"].values).size) if hasattr(events_ds, "data_vars") and "ID" in events_ds else None
         if self.unstructured_grid:
-            raise ConfigurationError("event_shapes: shapes are gridded only", details="this tracker works on an unstructured mesh")
+            from .shapes_mesh import _mesh_event_shapes
+
+            args = {k: kw.pop(k, d) for k, d in (("cell_areas", self.cell_area), ("edge_lengths", None), ("mask", self._mask_host),
+                                                 ("radius_km", 6371.0), ("per_timestep", True), ("block_steps", None),
+                                                 ("device", self.device))}
+            if kw:
+                raise TypeError(f"event_shapes() got an unexpected keyword argument {next(iter(kw))!r}")
+            return _mesh_event_shapes(field, self._nbr_host, np.asarray(self.lat), np.asarray(self.lon), args["cell_areas"],
+                                      args["edge_lengths"], args["mask"], args["radius_km"], args["per_timestep"],
+                                      args["block_steps"], args["device"], zero_based=True, n_events=n,
+                                      time=(self.timedim, self.timecoord, self.time_values))
         if "mask" not in kw:
             m = getattr(self, "_mask_host", None)
             kw["mask"] = m if m is not None else getattr(self, "mask", None)
@@ -1021,7 +1035,6 @@ class tracker(_MeshStages):  # noqa: N801 -- the reference's public name (marEx.
                                              ("block_steps", None), ("device", self.device))}
         if kw:
             raise TypeError(f"event_shapes() got an unexpected keyword argument {next(iter(kw))!r}")
-        n = int(np.asarray(events_ds["ID"].values).size) if hasattr(events_ds, "data_vars") and "ID" in events_ds else None
         return _event_shapes(field, args["mask"], args["cell_areas"], args["edge_lengths"], args["lat"], args["lon"],
                              args["regional_mode"], args["per_timestep"], args["block_steps"], args["device"], n_events=n,
                              time=(self.timedim, self.timecoord, self.time_values))
