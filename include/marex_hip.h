@@ -843,6 +843,55 @@ int marex_cell_events_u8(marex_ctx* ctx, const uint8_t* x, const float* anom, in
                          int32_t* rec_end, uint32_t* rec_vmax, int32_t* rec_tmax, double* rec_sum, uint32_t* rec_invalid,
                          uint64_t* status);
 
+/* Accumulated heat stress of a raw SST field x against a fixed per-cell threshold: the Degree Heating Week of NOAA Coral
+ * Reef Watch (Liu et al. 2014, Skirving et al. 2020) -- the monthly mean climatology whose maximum is the threshold m (the
+ * MMM), the HotSpot x - m counted from hotspot_min on, its running sum over `window` steps, the bleaching alert class of
+ * every step and the maxima per time group.  A lane owns a cell; nothing looks at a neighbour.
+ *
+ * marex_group_mean_f32: x float32 [Tb][C] are the rows t0 .. t0 + Tb - 1 of the field, lab int32 [T] (indexed by the global
+ *   step, must reach t0 + Tb) the label of every step: -1 skips the step, 0 .. G - 1 selects sum float64 [G][C] and cnt
+ *   uint32 [G][C]: cnt += 1 and sum += (double)x per finite sample.  Summation contract (that of marex_local_intensity_*):
+ *   the owning lane loads sum[g][c] when the first row or a change of the label begins a stretch, adds one term per step
+ *   and stores it when the stretch ends; no partial sum is ever added to memory.  sum[g][c] is therefore one sequence of
+ *   float64 additions in ascending step: the bits of a row-by-row loop, whatever the windows, also for labels that return.
+ *   Under a label outside -1 .. G - 1 a step addresses nothing: each of its C cells adds one to status uint64 [1].
+ *   The function only continues sum and cnt: the caller zeroes them before the first window.
+ *   -1: null pointer, empty shape, t0 < 0, G <= 0; -4: C or t0 + Tb of 2^31 - 1 or more.
+ *
+ * marex_heat_stress_f32: x points at row t0 - lead of the field, lead = min(window, t0) rows of history in front of the Tb
+ *   rows t0 .. t0 + Tb - 1 of the call; mmm float32 [C] is m.  Per step, with the float32 difference d = x[t] - m (one
+ *   rounding): the step is valid when x[t] and m are finite and |d| < 1024; h[t] = d where the step is valid and
+ *   d >= hotspot_min, else 0; S[t] = sum of h[k] over k = max(0, t - window + 1) .. t; dhw[t] = float32(S[t] /
+ *   steps_per_week), one float64 division and one rounding, NaN in every step of a cell whose m is not finite.
+ *   S is carried between calls in state float64 [C], zeroed by the caller before the first window, and updated as
+ *   S += h[t]; S -= h[t - window], the leaving step recomputed from x[t - window] and m by the same rule.  That is exact:
+ *   1 <= window <= 366 and 2^-10 <= hotspot_min < 1024 make every counted h a multiple of 2^-33 below 2^10, so any sum of
+ *   up to 512 of them is a float64; S[t] is the exact real sum whatever the order or the windows.
+ *   The alert class of a step, from d, hotspot_min and dhw[t] compared as float32 with levels float32 [L], 0 <= L <= 6,
+ *   ascending: 255 where the step is not valid, 0 for d <= 0, 1 for 0 < d < hotspot_min, else 2 + #{j : dhw[t] >= levels[j]}.
+ *   grp int32 [T] (global steps, must reach t0 + Tb; NULL with G == 1: every step is group 0) selects the accumulators of
+ *   a step, all given or all NULL: dhw_max uint32 [G][C], the largest ordered key (that of marex_event_intensity_f32; 0:
+ *   none) of dhw[t] over the steps of a cell with m; tmax int32 [G][C], the earliest global step that attains it
+ *   (meaningless where dhw_max is 0); hotspot_max uint32 [G][C], the largest key of d over the valid steps; alert_steps
+ *   uint32 [G][3 + L][C], the steps per alert class; invalid uint32 [G][C], the steps that are not valid; onset int32
+ *   [G][max(L, 1)][C] (addressed [g][j][c] with L rows per group), ONE PLUS the first global step of the group with
+ *   dhw[t] >= levels[j], 0: none.  The caller zeroes them; the lane loads them when a stretch begins and stores them when
+ *   it ends, as above.  Under a label outside 0 .. G - 1 a step addresses no accumulator: each of its C cells adds one to
+ *   status uint64 [1]; S and the field outputs do not depend on the labels.
+ *   dhw float32 and alert uint8 (each may be NULL) are the bases of the WHOLE [T][C] outputs, addressed with the global
+ *   step: the rows t0 .. t0 + Tb - 1 are written.  No atomic touches a per-cell output.  One cell per lane.
+ *   -1: null x, mmm, state or status, empty shape, t0 < 0, window outside 1 .. 366, lead != min(window, t0), hotspot_min
+ *   outside [2^-10, 1024), steps_per_week not positive and finite, L outside 0 .. 6, NULL levels with L > 0, G <= 0, NULL
+ *   grp with G != 1, accumulators given in part; -4: C or t0 + Tb of 2^31 - 1 or more (the fields are addressed with
+ *   64-bit offsets).  Nothing is launched then.  Both functions are asynchronous on the context's stream. */
+int marex_group_mean_f32(marex_ctx* ctx, const float* x, int64_t t0, int64_t Tb, int64_t C, const int32_t* lab, int G,
+                         double* sum, uint32_t* cnt, uint64_t* status);
+int marex_heat_stress_f32(marex_ctx* ctx, const float* x, const float* mmm, int64_t t0, int64_t lead, int64_t Tb, int64_t C,
+                          int window, float hotspot_min, double steps_per_week, const float* levels, int L,
+                          const int32_t* grp, int G, double* state, uint32_t* dhw_max, int32_t* tmax, uint32_t* hotspot_max,
+                          uint32_t* alert_steps, uint32_t* invalid, int32_t* onset, float* dhw, uint8_t* alert,
+                          uint64_t* status);
+
 /* Compound events of two presence fields A and B, from one streaming pass over both (the reference's guide builds the
  * joint mask on the host, docs/user_guide.rst:821-833: sst_extremes.extreme_events & salinity_extremes.extreme_events, and
  * leaves every statistic of it to the user).

@@ -134,6 +134,9 @@ PROTOTYPES = {
     "marex_local_intensity_i32": (_i32, [_p, _p, _p, _i64, _i64, _i64, _i32, _p, _i32, _p, _p, _i32, _p, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _p]),
     "marex_cell_events_u8": (_i32, [_p, _p, _p, _i64, _i64, _i64, _i32, _i32, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,
                                     _p, _p, _p, _p, _p]),
+    "marex_group_mean_f32": (_i32, [_p, _p, _i64, _i64, _i64, _p, _i32, _p, _p, _p]),
+    "marex_heat_stress_f32": (_i32, [_p, _p, _p, _i64, _i64, _i64, _i64, _i32, _f32, _f64, _p, _i32, _p, _i32, _p, _p, _p, _p, _p, _p,
+                                     _p, _p, _p, _p]),
     "marex_regional_series_u8": (_i32, [_p, _p, _i64, _i64, _i64, _i64, _i32, _p, _i32, _p, _p, _p, _p, _p, _i32, _p, _p, _p, _p, _p, _p, _p]),
     "marex_regional_layout": (_i32, [_i32, _p]),
     "marex_regional_series_i32": (_i32, [_p, _p, _i64, _i64, _i64, _i64, _i32, _p, _i32, _p, _p, _p, _p, _p, _i32, _p, _p, _p, _p, _p, _p, _p]),

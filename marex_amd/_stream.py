@@ -1,5 +1,5 @@
 """What the streaming statistics (``intensity``, ``event_categories``, ``shapes``, ``regional``, ``exposure``, ``occurrence``,
-``local_intensity``, ``cell_events``, ``compound``, ``composites``; ``trends`` for the free memory) share in front of the
+``local_intensity``, ``cell_events``, ``heat_stress``, ``compound``, ``composites``; ``trends`` for the free memory) share in front of the
 engine: what a ``[time, space]`` field says without a device, the windows it is walked in -- with or without a part that
 stays for the whole call -- and the way back to its spatial dimensions.  For the first five also the parser of a map or of
 ``cell_areas`` over space, the area table, the regions' denominators and the tracker's ``time`` triple; for the statistics over
@@ -73,12 +73,26 @@ def _time_of(field, T: int):
     return name, (v if v.shape == (T,) else None)
 
 
-def plan_field(field, what: str, partner=None, names=("field", "dat_anomaly"), presence_partner: bool = False) -> dict:
+def _float_kind(field, name: str) -> str:
+    """'f' for a floating-point field; anything else is refused under ``name``."""
+    if _kind(field) != "f":
+        raise create_data_validation_error(f"{name} must be a floating-point field", details=f"Found dtype {_dtype_name(field)}",
+                                           data_info={"actual_dtype": _dtype_name(field)})
+    return "f"
+
+
+def plan_float_field(field, what: str, name: str = "sst") -> dict:
+    """:func:`plan_field` of a float field that stands alone (``kind`` 'f'), called ``name`` in the refusals."""
+    return plan_field(field, what, names=(name, None), floats=True)
+
+
+def plan_field(field, what: str, partner=None, names=("field", "dat_anomaly"), presence_partner: bool = False,
+               floats: bool = False) -> dict:
     """What a presence field says without a device: ``shape``, ``T``, ``C``, ``kind`` ('m' mask, 'i' IDs), ``bool``, the
     time axis (``tname``, ``tv``), the spatial dimensions ``sdims`` and their coordinates ``scoords``.  ``partner``: the
     anomaly field, which must agree in shape, dimensions and time; its names and coordinates fill in what the field lacks.
     ``presence_partner``: the partner is a second presence field, not a float one (adds ``kind_b`` and ``bool_b``);
-    ``names``: what the errors call the two."""
+    ``names``: what the errors call the two.  ``floats``: the field is a float one itself (:func:`plan_float_field`)."""
     fname, pname = names
     shape = tuple(int(k) for k in field.shape)
     if len(shape) not in (2, 3):
@@ -93,7 +107,7 @@ def plan_field(field, what: str, partner=None, names=("field", "dat_anomaly"), p
         if dims and d_a and dims != d_a:
             raise create_data_validation_error(f"{fname} and {pname} differ in their dimensions",
                                                details=f"{fname} {dims}, {pname} {d_a}; the order must agree too")
-    kind = _field_kind(field)
+    kind = _float_kind(field, fname) if floats else _field_kind(field)
     kind_b = _field_kind(partner) if presence_partner and partner is not None else None
     if partner is not None and not presence_partner and _kind(partner) != "f":
         raise create_data_validation_error(f"{pname} must be a floating-point field",

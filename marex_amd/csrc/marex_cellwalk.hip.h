@@ -1,7 +1,7 @@
 #pragma once
 // marex_cellwalk.hip.h -- what the per-cell streaming kernels (marex_occurrence.hip, marex_local_intensity.hip,
-// marex_cell_events.hip, marex_compound.hip) share: a lane owns one cell, or four consecutive uint8 cells through one 32-bit
-// load, for the whole call and walks the rows.  The kernels, their unroll depths and what they keep per cell stay in their
+// marex_cell_events.hip, marex_compound.hip, marex_heat_stress.hip) share: a lane owns one cell, or four consecutive uint8
+// cells through one 32-bit load, for the whole call and walks the rows.  The kernels, their unroll depths and what they keep per cell stay in their
 // units (the register budgets differ).  The leaf helpers that the event kernels use too -- u64,
 // finite_bits, severity_class, wave_sum, cell_stream_limits -- are in marex_common.hip.h.
 #include "marex_common.hip.h"

@@ -1470,12 +1470,12 @@ class HotPath:
         return sect
 
     def _whole_output_check(self, what: str, name: str, out: Optional[torch.Tensor], Cn: int, end: int,
-                            second: Optional[bool] = None) -> None:
-        """``out`` (the ``name`` of the refusal) is the whole uint8 ``[T, Cn]`` output and reaches the window's end -- and, where
-        the caller has two passes, this is not the ``second``."""
-        if out is not None and (second or out.dtype != torch.uint8 or out.dim() != 2 or int(out.shape[1]) != Cn or
+                            second: Optional[bool] = None, dtype=torch.uint8) -> None:
+        """``out`` (the ``name`` of the refusal) is the whole ``dtype`` ``[T, Cn]`` output and reaches the window's end -- and,
+        where the caller has two passes, this is not the ``second``."""
+        if out is not None and (second or out.dtype != dtype or out.dim() != 2 or int(out.shape[1]) != Cn or
                                 int(out.shape[0]) < end or not out.is_contiguous() or out.device != self.device):
-            raise ProcessingError(f"{what}: the {name} must be the whole contiguous uint8 [T, {Cn}] output on the engine's "
+            raise ProcessingError(f"{what}: the {name} must be the whole contiguous {str(dtype).replace('torch.', '')} [T, {Cn}] output on the engine's "
                                   f"device, T >= {end}{'' if second is None else ', and belongs to the summary pass'}",
                                   details=f"got {out.dtype} {tuple(out.shape)} on {out.device}")
 
@@ -2021,6 +2021,125 @@ class HotPath:
         out.update(days=host(acc["days"], np.uint32), invalid=host(acc["invalid"], np.uint32), sum=host(acc["sum"], np.float64),
                    vmax=self._key_max(key), tmax=self._key_step(key, host(acc["tmax"], np.int32)),
                    cat_days=host(acc["cat_days"], np.uint32), sec_cnt=host(acc["sec_cnt"], np.uint64))
+        return out
+
+    def _float_window(self, what: str, x: torch.Tensor) -> tuple:
+        """``(rows, Cn)`` of a window of a float32 field."""
+        if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.dtype != torch.float32 or not x.is_contiguous() or x.device != self.device:
+            raise ProcessingError(f"{what}: the field must be a contiguous float32 [T, C] tensor on the engine's device",
+                                  details=f"got {getattr(x, 'dtype', type(x))} {tuple(getattr(x, 'shape', ()))} on "
+                                          f"{getattr(x, 'device', 'the host')}")
+        return int(x.shape[0]), int(x.shape[1])
+
+    def group_mean(self, x: torch.Tensor, lab, G: int, t0: int = 0, acc: Optional[dict] = None, finish: bool = True) -> Dict[str, object]:
+        """Per (label, cell) the count and the sequential float64 sum of the finite samples of the rows ``t0 .. t0 + Tb - 1``
+        (``marex_group_mean_f32``): ``x`` float32 ``[Tb, C]``, ``lab`` int ``[T]`` by the global step, -1 (the step is
+        skipped) or ``0 .. G - 1``.  The first window allocates zeroed accumulators and uploads the labels; a later window
+        passes the ``"acc"`` entry of the previous result -- the window lengths do not matter, not even to the last bit of
+        ``sum``.  Returns ``acc`` and, with ``finish``, ``sum`` float64 and ``cnt`` uint32 ``[G, C]``.  A label outside
+        ``-1 .. G - 1`` raises :class:`ProcessingError`; its cells were counted, nothing was written out of range."""
+        Tb, Cn = self._float_window("group_mean", x)
+        t0, G = int(t0), int(G)
+        if t0 < 0 or G <= 0 or lab is None:
+            raise ProcessingError("group_mean: t0 must not be negative, G must be positive, and the steps need labels",
+                                  details=f"t0 = {t0}, G = {G}, labels {'given' if lab is not None else 'missing'}")
+        plan = (G, Cn)
+        if acc is None:
+            tabs = label_tables("group_mean", (("lab", lab, None),))
+            self._check_fits(12 * G * Cn + 8 + self._table_bytes(tabs), "group mean",
+                             f"{G} x {Cn} cells of 12 bytes (sum, count) and the label table")
+            acc = {"sum": self._zeros("gm_sum", (G, Cn), torch.float64), "cnt": self._zeros("gm_cnt", (G, Cn), torch.int32),
+                   "status": self._zeros("gm_status", (1,), torch.int64), "plan": plan, **self._upload_tables(tabs)}
+        self._window_check("group_mean", acc, plan, ("lab",), t0, Tb, Cn)
+        self.call("marex_group_mean_f32", x, t0, Tb, Cn, acc["tabs"]["lab"], G, acc["sum"], acc["cnt"], acc["status"])
+        out: Dict[str, object] = {"acc": acc}
+        if not finish:
+            return out
+        lost = int(acc["status"].cpu().numpy()[0])
+        if lost:
+            raise ProcessingError(f"group_mean: {lost} cells lie under a step label outside its range",
+                                  details=f"lab must hold -1 .. {G - 1}; the cells were counted, nothing was written out of range")
+        out.update(sum=self._host(acc["sum"], np.float64), cnt=self._host(acc["cnt"], np.uint32))
+        return out
+
+    #: the most alert levels and the longest window of :meth:`heat_stress`
+    HEAT_STRESS_MAX_LEVELS, HEAT_STRESS_MAX_WINDOW = 6, 366
+
+    def heat_stress(self, x: torch.Tensor, mmm, t0: int = 0, lead: int = 0, window: int = 84, hotspot_min: float = 1.0,
+                    steps_per_week: float = 7.0, levels=(4.0, 8.0), grp=None, G: int = 1, dhw: Optional[torch.Tensor] = None,
+                    alert: Optional[torch.Tensor] = None, summary: bool = True, acc: Optional[dict] = None,
+                    finish: bool = True) -> Dict[str, object]:
+        """Accumulated heat stress of the rows ``t0 .. t0 + Tb - 1`` (``marex_heat_stress_f32``): ``x`` float32
+        ``[lead + Tb, C]`` begins ``lead = min(window, t0)`` rows before the window -- the history that leaves the running
+        sum -- and ``mmm`` is the float32 ``[C]`` threshold (a host array is uploaded).  ``grp`` (int ``[T]``, global steps,
+        or None with ``G == 1``) labels the steps.  ``dhw`` / ``alert``: the WHOLE float32 / uint8 ``[T, C]`` outputs, or
+        None.  The first window allocates the zeroed carried sum and accumulators and uploads the tables; a later window
+        passes the ``"acc"`` entry of the previous result and must begin where that ended -- the window lengths do not
+        matter to any bit.  Returns ``acc`` and, with ``finish`` and ``summary``, ``dhw_max`` and ``hotspot_max`` float32
+        (NaN: none), ``tmax`` int32 (-1: none), ``invalid`` uint32 ``[G, C]``, ``alert_steps`` uint32 ``[G, 3 + L, C]`` and
+        ``onset`` int32 ``[G, L, C]`` (-1: none).  A step label outside ``0 .. G - 1`` raises :class:`ProcessingError`; its
+        cells were counted, nothing was written out of range."""
+        rows, Cn = self._float_window("heat_stress", x)
+        t0, lead, G = int(t0), int(lead), int(G)
+        lev = np.asarray(levels, dtype=np.float32).reshape(-1)
+        L = int(lev.size)
+        hmin, spw = float(np.float32(hotspot_min)), float(steps_per_week)
+        if isinstance(window, bool) or not isinstance(window, (int, np.integer)) or not 1 <= window <= self.HEAT_STRESS_MAX_WINDOW or \
+                not 2.0 ** -10 <= hmin < 1024.0 or not (spw > 0 and np.isfinite(spw)) or L > self.HEAT_STRESS_MAX_LEVELS or \
+                not np.isfinite(lev).all() or not (np.diff(lev) > 0).all():
+            raise ProcessingError(f"heat_stress: window must be an integer in 1 .. {self.HEAT_STRESS_MAX_WINDOW}, hotspot_min in "
+                                  f"[2^-10, 1024), steps_per_week positive and finite, levels at most "
+                                  f"{self.HEAT_STRESS_MAX_LEVELS} finite, strictly increasing values",
+                                  details=f"window = {window!r}, hotspot_min = {hotspot_min!r}, steps_per_week = "
+                                          f"{steps_per_week!r}, levels = {lev.tolist()}")
+        window = int(window)
+        if t0 < 0 or lead != min(window, t0) or G <= 0 or (grp is None and G != 1):
+            raise ProcessingError("heat_stress: t0 must not be negative, lead must be min(window, t0), G must be positive, and "
+                                  "G > 1 needs labels",
+                                  details=f"t0 = {t0}, lead = {lead}, window = {window}, G = {G}, labels "
+                                          f"{'given' if grp is not None else 'missing'}")
+        Tb = rows - lead
+        end = t0 + max(Tb, 0)
+        self._whole_output_check("heat_stress", "dhw output", dhw, Cn, end, dtype=torch.float32)
+        self._whole_output_check("heat_stress", "alert output", alert, Cn, end)
+        plan = (G, Cn, window, hmin, spw, tuple(lev.tolist()), bool(summary))
+        if acc is None:
+            tabs = label_tables("heat_stress", (("grp", grp, None),))
+            per = 16 + 4 * (3 + L) + 4 * max(L, 1) if summary else 0
+            self._check_fits(8 * Cn + G * Cn * per + 8 + self._table_bytes(tabs), "heat stress",
+                             f"{Cn} cells of 8 bytes of carried sum, {G} x {Cn} cells of accumulators, {per} bytes each, and the "
+                             "label table")
+            acc = {"state": self._zeros("hs_state", (Cn,), torch.float64), "status": self._zeros("hs_status", (1,), torch.int64),
+                   "mmm": self._cell_vector("heat_stress", "mmm", mmm, torch.float32, Cn, upload=True, typ="float32"),
+                   "levels": self._dev(lev if L else np.zeros(1, np.float32)), "plan": plan, "next": t0,
+                   **{k: None for k in ("dhw_max", "tmax", "hotspot_max", "alert_steps", "invalid", "onset")},
+                   **self._upload_tables(tabs)}
+            if summary:
+                for k in ("dhw_max", "tmax", "hotspot_max", "invalid"):
+                    acc[k] = self._zeros("hs_" + k, (G, Cn), torch.int32)
+                acc["alert_steps"] = self._zeros("hs_alert_steps", (G, 3 + L, Cn), torch.int32)
+                acc["onset"] = self._zeros("hs_onset", (G, max(L, 1), Cn), torch.int32)
+        self._window_check("heat_stress", acc, plan, ("grp",), t0, Tb, Cn)
+        if Tb < 0 or t0 != acc["next"]:
+            raise ProcessingError("heat_stress: the windows must follow each other, each with its history rows in front",
+                                  details=f"the window begins at step {t0} with {rows} rows and lead {lead}; step {acc['next']} is next")
+        self.call("marex_heat_stress_f32", x, acc["mmm"], t0, lead, Tb, Cn, window, hmin, spw, acc["levels"], L, acc["tabs"]["grp"], G,
+                  acc["state"], acc["dhw_max"], acc["tmax"], acc["hotspot_max"], acc["alert_steps"], acc["invalid"], acc["onset"],
+                  dhw, alert, acc["status"])
+        acc["next"] = t0 + Tb
+        out: Dict[str, object] = {"acc": acc}
+        if not finish:
+            return out
+        lost = int(acc["status"].cpu().numpy()[0])
+        if lost:
+            raise ProcessingError(f"heat_stress: {lost} cells lie under a step label outside its range",
+                                  details=f"grp must hold 0 .. {G - 1}; the cells were counted, nothing was written out of range")
+        if summary:
+            host = self._host
+            key, on = host(acc["dhw_max"], np.uint32), host(acc["onset"], np.int32)[:, :L]
+            out.update(dhw_max=self._key_max(key), tmax=self._key_step(key, host(acc["tmax"], np.int32)),
+                       hotspot_max=self._key_max(host(acc["hotspot_max"], np.uint32)), invalid=host(acc["invalid"], np.uint32),
+                       alert_steps=host(acc["alert_steps"], np.uint32), onset=(on - 1).astype(np.int32))
         return out
 
     #: the most regions of :meth:`regional_series`
