@@ -132,6 +132,12 @@ class DeviceCalendar:
     plan: CalendarPlan
 
 
+def pair_table_cap(runs: int) -> int:
+    """Entries of the overlap pair table for ``runs`` runs of equal pairs: a power of two of at least 64 with a load
+    factor <= 1/2 even if every run were a distinct pair."""
+    return max(64, 1 << (2 * runs - 1).bit_length())
+
+
 class HotPath:
     def __init__(self, device: int | torch.device = 0, own_stream: bool = False):
         if not torch.cuda.is_available():
@@ -973,7 +979,7 @@ class HotPath:
         runs = int(stats[1].item())
         if runs == 0:
             return empty
-        cap = max(64, 1 << (2 * runs - 1).bit_length())  # load factor <= 1/2 even if every run were a distinct pair
+        cap = pair_table_cap(runs)
         self._check_fits(16 * cap + 16 * runs, "overlap pairs", f"a hash table of {cap} entries for {runs} runs of equal pairs")
         keys = self._buf(None, "ovl_keys", (cap,), torch.int64, self.device)
         counts = self._buf(None, "ovl_counts", (cap,), torch.int64, self.device)
@@ -1118,7 +1124,7 @@ class HotPath:
         runs = int(stats[1].item())
         if runs == 0:
             return empty
-        cap = max(64, 1 << (2 * runs - 1).bit_length())  # load factor <= 1/2 even if every run were a distinct pair
+        cap = pair_table_cap(runs)
         self._check_fits(24 * cap + 24 * runs, "mesh overlap pairs", f"a hash table of {cap} entries for {runs} runs of equal pairs")
         keys = self._buf(None, "movl_keys", (cap,), torch.int64, self.device)
         sums = self._buf(None, "movl_sums", (cap, 2), torch.int64, self.device)
