@@ -892,6 +892,46 @@ int marex_heat_stress_f32(marex_ctx* ctx, const float* x, const float* mmm, int6
                           uint32_t* alert_steps, uint32_t* invalid, int32_t* onset, float* dhw, uint8_t* alert,
                           uint64_t* status);
 
+/* Nearest-cell resampling between two geometries on the sphere: the exact nearest source cell of every target, and the gather
+ * of a [time, cells] field through such an index.  Vectors are float64 unit vectors laid out [3][N] (x row, y row, z row);
+ * the host computes them, the device calls no transcendental.  The squared chord of a source and a target is
+ * q = (dx * dx + dy * dy) + dz * dz, dx = xs - xt etc., each operation rounded on its own; the answer of a target is the
+ * source that is smallest in the order (q, cell number): independent of search structure, bucket order, lane and wave.
+ *
+ * marex_nearest_brute_f64: src [3][N] with the cell numbers ids int32 [N] (NULL: 0 .. N - 1), dst [3][M].  Without sel
+ *   (K == M) every target is searched; with sel int32 [K], 1 <= K <= M, only the targets it lists (an entry outside
+ *   0 .. M - 1 addresses nothing).  index int32 [M] and q float64 [M] of a searched target receive the winner and its q,
+ *   those of the other targets are left as they are.  A target with a NaN
+ *   coordinate, or without a source, gets index -1 and q = +inf.
+ * marex_voxel_count_f64: count int32 [n^3] (zeroed by the caller) += the sources per voxel of the n^3 grid of edge 2 / n over
+ *   [-1, 1]^3; the voxel of a point is (vz * n + vy) * n + vx with v = clamp(int((p + 1) * (n / 2)), 0, n - 1) per axis.
+ * marex_voxel_scatter_f64: off int32 [n^3 + 1] is the exclusive prefix sum of count, cursor int32 [n^3] zeroed by the caller;
+ *   writes sorted [3][N] and sorted_ids [N], the vectors and cell numbers in voxel order (the order inside a voxel is not
+ *   determined).  A position outside 0 .. N - 1 (an offset table of other sources) is not written.
+ * marex_nearest_voxel_f64: one target per lane searches the Chebyshev rings r = 0 .. max_rings of voxels around its own.  It
+ *   stops after ring r >= 1 when its best q < ((r h)^2) * (1 - 2^-32), h = 2 / n (marex_nearest.hip derives the margin: n <= 1024),
+ *   when that bound exceeds qmax (q above qmax is of no interest to the caller; +inf: no limit), or when the rings cover
+ *   the grid: flag uint8 [M] = 0 and index / q are final.  A target still open after max_rings gets flag 1 and the best pair
+ *   so far: the caller searches it again with marex_nearest_brute_f64.  NaN targets: index -1, q +inf, flag 0.
+ * marex_resample_nearest_u8 / _i32 / _f32: out [Tb][M] = x [Tb][C] at index int32 [M]; fill where index < 0 (an index of C
+ *   or more reads nothing and gives fill too).  64-bit offsets: Tb * C and Tb * M are not bounded, C and M stay below 2^31 - 1.
+ *   No atomics; every element of out is written exactly once.
+ *   -1: null pointer, empty shape, K or n or max_rings or qmax or fill (u8: 0 .. 255) out of range; -4: 2^31 - 1 or more
+ *   cells or rows.  Nothing is launched then.  All are asynchronous on the context's stream. */
+int marex_nearest_brute_f64(marex_ctx* ctx, const double* src, const int32_t* ids, int64_t N, const double* dst, int64_t M,
+                            const int32_t* sel, int64_t K, int32_t* index, double* q);
+int marex_voxel_count_f64(marex_ctx* ctx, const double* src, int64_t N, int n, int32_t* count);
+int marex_voxel_scatter_f64(marex_ctx* ctx, const double* src, const int32_t* ids, int64_t N, int n, const int32_t* off,
+                            int32_t* cursor, double* sorted, int32_t* sorted_ids);
+int marex_nearest_voxel_f64(marex_ctx* ctx, const double* sorted, const int32_t* sorted_ids, int64_t N, const int32_t* off, int n,
+                            const double* dst, int64_t M, int max_rings, double qmax, int32_t* index, double* q, uint8_t* flag);
+int marex_resample_nearest_u8(marex_ctx* ctx, const uint8_t* x, int64_t Tb, int64_t C, const int32_t* index, int64_t M, int fill,
+                              uint8_t* out);
+int marex_resample_nearest_i32(marex_ctx* ctx, const int32_t* x, int64_t Tb, int64_t C, const int32_t* index, int64_t M, int fill,
+                               int32_t* out);
+int marex_resample_nearest_f32(marex_ctx* ctx, const float* x, int64_t Tb, int64_t C, const int32_t* index, int64_t M, float fill,
+                               float* out);
+
 /* Compound events of two presence fields A and B, from one streaming pass over both (the reference's guide builds the
  * joint mask on the host, docs/user_guide.rst:821-833: sst_extremes.extreme_events & salinity_extremes.extreme_events, and
  * leaves every statistic of it to the user).

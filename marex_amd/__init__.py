@@ -52,6 +52,7 @@ from .occurrence import event_occurrence
 from .local_intensity import local_intensity
 from .cell_events import cell_events
 from .heat_stress import heat_stress, monthly_maximum_climatology
+from .resample import nearest_cell_index, resample_nearest
 from .compound import compound_events
 from .composites import event_composites
 from .trends import cell_trends
@@ -70,6 +71,6 @@ __all__ = [
     "tracker", "TrackingError", "event_intensity", "event_occurrence", "local_intensity",
     "cell_events", "event_categories", "compound_events", "cell_trends", "regional_series",
     "event_composites", "event_shapes", "grid_edge_lengths", "event_exposure", "event_matching",
-    "mesh_event_shapes", "heat_stress", "monthly_maximum_climatology",
+    "mesh_event_shapes", "heat_stress", "monthly_maximum_climatology", "nearest_cell_index", "resample_nearest",
 ]
 __version__ = "0.1.0"

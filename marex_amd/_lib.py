@@ -137,6 +137,13 @@ PROTOTYPES = {
     "marex_group_mean_f32": (_i32, [_p, _p, _i64, _i64, _i64, _p, _i32, _p, _p, _p]),
     "marex_heat_stress_f32": (_i32, [_p, _p, _p, _i64, _i64, _i64, _i64, _i32, _f32, _f64, _p, _i32, _p, _i32, _p, _p, _p, _p, _p, _p,
                                      _p, _p, _p, _p]),
+    "marex_nearest_brute_f64": (_i32, [_p, _p, _p, _i64, _p, _i64, _p, _i64, _p, _p]),
+    "marex_voxel_count_f64": (_i32, [_p, _p, _i64, _i32, _p]),
+    "marex_voxel_scatter_f64": (_i32, [_p, _p, _p, _i64, _i32, _p, _p, _p, _p]),
+    "marex_nearest_voxel_f64": (_i32, [_p, _p, _p, _i64, _p, _i32, _p, _i64, _i32, _f64, _p, _p, _p]),
+    "marex_resample_nearest_u8": (_i32, [_p, _p, _i64, _i64, _p, _i64, _i32, _p]),
+    "marex_resample_nearest_i32": (_i32, [_p, _p, _i64, _i64, _p, _i64, _i32, _p]),
+    "marex_resample_nearest_f32": (_i32, [_p, _p, _i64, _i64, _p, _i64, _f32, _p]),
     "marex_regional_series_u8": (_i32, [_p, _p, _i64, _i64, _i64, _i64, _i32, _p, _i32, _p, _p, _p, _p, _p, _i32, _p, _p, _p, _p, _p, _p, _p]),
     "marex_regional_layout": (_i32, [_i32, _p]),
     "marex_regional_series_i32": (_i32, [_p, _p, _i64, _i64, _i64, _i64, _i32, _p, _i32, _p, _p, _p, _p, _p, _i32, _p, _p, _p, _p, _p, _p, _p]),

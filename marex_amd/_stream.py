@@ -1,5 +1,5 @@
 """What the streaming statistics (``intensity``, ``event_categories``, ``shapes``, ``regional``, ``exposure``, ``occurrence``,
-``local_intensity``, ``cell_events``, ``heat_stress``, ``compound``, ``composites``; ``trends`` for the free memory) share in front of the
+``local_intensity``, ``cell_events``, ``heat_stress``, ``resample``, ``compound``, ``composites``; ``trends`` for the free memory) share in front of the
 engine: what a ``[time, space]`` field says without a device, the windows it is walked in -- with or without a part that
 stays for the whole call -- and the way back to its spatial dimensions.  For the first five also the parser of a map or of
 ``cell_areas`` over space, the area table, the regions' denominators and the tracker's ``time`` triple; for the statistics over

@@ -11,7 +11,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 UNITS = ["marex_context", "marex_synth", "marex_shifting", "marex_thresholds", "marex_mask", "marex_anomalies",
-         "marex_quantiles", "marex_morphology", "marex_objects", "marex_mesh_objects", "marex_merge", "marex_mesh_merge", "marex_intensity", "marex_event_shapes", "marex_mesh_event_shapes", "marex_event_categories", "marex_occurrence", "marex_local_intensity", "marex_cell_events", "marex_heat_stress", "marex_compound", "marex_composites", "marex_trends", "marex_regional", "marex_event_exposure", "marex_event_matching", "marex_blosc", "marex_tails", "marex_zstd"]
+         "marex_quantiles", "marex_morphology", "marex_objects", "marex_mesh_objects", "marex_merge", "marex_mesh_merge", "marex_intensity", "marex_event_shapes", "marex_mesh_event_shapes", "marex_event_categories", "marex_occurrence", "marex_local_intensity", "marex_cell_events", "marex_heat_stress", "marex_nearest", "marex_compound", "marex_composites", "marex_trends", "marex_regional", "marex_event_exposure", "marex_event_matching", "marex_blosc", "marex_tails", "marex_zstd"]
 SRC = [os.path.join(HERE, u + ".hip") for u in UNITS]
 HEADERS = [os.path.join(HERE, "marex_common.hip.h"), os.path.join(HERE, "marex_tails.hip.h"),
            os.path.join(HERE, "marex_cellwalk.hip.h"), os.path.join(ROOT, "include", "marex_hip.h")]

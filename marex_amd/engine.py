@@ -2148,6 +2148,138 @@ class HotPath:
                        alert_steps=host(acc["alert_steps"], np.uint32), onset=(on - 1).astype(np.int32))
         return out
 
+    #: the largest voxel grid of :meth:`voxel_table` (the stopping margin of marex_nearest.hip is derived for it)
+    NEAREST_MAX_VOXELS = 1024
+
+    def _unit_vectors(self, what: str, name: str, v) -> torch.Tensor:
+        """``v`` as the contiguous float64 ``[3, N]`` table on the engine's device (a host array is uploaded)."""
+        if not isinstance(v, torch.Tensor):
+            h = np.ascontiguousarray(v)
+            if h.dtype != np.float64 or h.ndim != 2 or h.shape[0] != 3:
+                raise ProcessingError(f"{what}: {name} must be float64 [3, N] unit vectors", details=f"got {h.dtype} {h.shape}")
+            v = self._dev(h)
+        if v.dtype != torch.float64 or v.dim() != 2 or int(v.shape[0]) != 3 or int(v.shape[1]) < 1 or not v.is_contiguous() or \
+                v.device != self.device:
+            raise ProcessingError(f"{what}: {name} must be a contiguous, non-empty float64 [3, N] tensor on the engine's device",
+                                  details=f"got {v.dtype} {tuple(v.shape)} on {v.device}")
+        return v
+
+    def nearest_brute(self, src, ids, dst, sel=None, index: Optional[torch.Tensor] = None, q: Optional[torch.Tensor] = None):
+        """The exact nearest source of every target (``marex_nearest_brute_f64``): ``src`` float64 ``[3, N]`` unit vectors with
+        their cell numbers ``ids`` int32 ``[N]`` (None: ``0 .. N - 1``), ``dst`` float64 ``[3, M]``.  ``sel`` (int32 ``[K]``
+        device tensor) restricts the search to the targets it lists and needs ``index`` and ``q``, which keep every other
+        entry.  Returns the device tensors ``(index int32 [M], q float64 [M])``: the smallest ``(q, cell number)``, -1 and
+        +inf for a target with a NaN coordinate."""
+        what = "nearest_brute"
+        src, dst = self._unit_vectors(what, "the sources", src), self._unit_vectors(what, "the targets", dst)
+        N, M = int(src.shape[1]), int(dst.shape[1])
+        ids = self._cell_vector(what, "the cell numbers", ids, torch.int32, N, upload=True, typ="int32")
+        if sel is None:
+            index, q, K = self._buf(None, "nn_index", (M,), torch.int32, self.device), self._buf(None, "nn_q", (M,), torch.float64, self.device), M
+        else:
+            self._cell_vector(what, "the index", index, torch.int32, M, typ="int32")
+            self._cell_vector(what, "q", q, torch.float64, M, typ="float64")
+            K = int(sel.numel())
+            if index is None or q is None or sel.dtype != torch.int32 or sel.dim() != 1 or not 1 <= K <= M:
+                raise ProcessingError(f"{what}: a target list needs 1 .. M int32 entries and the index and q it continues",
+                                      details=f"got {sel.dtype} {tuple(sel.shape)} for {M} targets")
+        self.call("marex_nearest_brute_f64", src, ids, N, dst, M, sel, K, index, q)
+        return index, q
+
+    def voxel_table(self, src, ids, n: int) -> Dict[str, object]:
+        """The sources binned into ``n^3`` voxels over ``[-1, 1]^3`` (``marex_voxel_count_f64``, a prefix sum,
+        ``marex_voxel_scatter_f64``): ``sorted`` float64 ``[3, N]`` and ``ids`` int32 ``[N]`` in voxel order, ``off`` int32
+        ``[n^3 + 1]``, ``n``.  The table is dense: ``16 n^3`` bytes while it is built (counts, their int64 prefix sum, offsets),
+        ``4 n^3`` afterwards."""
+        what = "voxel_table"
+        src = self._unit_vectors(what, "the sources", src)
+        N = int(src.shape[1])
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= n <= self.NEAREST_MAX_VOXELS:
+            raise ProcessingError(f"{what}: the voxel grid must have 1 .. {self.NEAREST_MAX_VOXELS} voxels per axis", details=f"n = {n!r}")
+        n = int(n)
+        ids = self._cell_vector(what, "the cell numbers", ids, torch.int32, N, upload=True, typ="int32")
+        self._check_fits(16 * n ** 3 + 28 * N, "voxel table",
+                         f"{n}^3 voxels of 16 bytes while the table is built (counts, their 64-bit prefix sum, offsets) and {N} sources of 28 bytes")
+        count = self._zeros("nn_count", (n ** 3,), torch.int32)
+        self.call("marex_voxel_count_f64", src, N, n, count)
+        off = torch.zeros((n ** 3 + 1,), dtype=torch.int32, device=self.device)
+        off[1:] = torch.cumsum(count, 0)  # plumbing: N < 2^31, so the int64 sums fit int32
+        count.zero_()
+        srt, sid = self._buf(None, "nn_sorted", (3, N), torch.float64, self.device), self._buf(None, "nn_sorted_ids", (N,), torch.int32, self.device)
+        self.call("marex_voxel_scatter_f64", src, ids, N, n, off, count, srt, sid)
+        return {"sorted": srt, "ids": sid, "off": off, "n": n}
+
+    def nearest_voxel(self, table: dict, dst, max_rings: int, qmax: float = float("inf")):
+        """The ring search of ``marex_nearest_voxel_f64`` over a :meth:`voxel_table`: the device tensors ``(index int32 [M],
+        q float64 [M], flag uint8 [M])``; ``flag`` 1 marks a target still open after ``max_rings`` rings."""
+        what = "nearest_voxel"
+        dst = self._unit_vectors(what, "the targets", dst)
+        M, N, n = int(dst.shape[1]), int(table["sorted"].shape[1]), int(table["n"])
+        max_rings, qmax = int(max_rings), float(qmax)
+        if max_rings < 0 or not qmax >= 0 or tuple(table["off"].shape) != (n ** 3 + 1,) or tuple(table["ids"].shape) != (N,):
+            raise ProcessingError(f"{what}: max_rings and qmax must not be negative, and the table must be that of voxel_table",
+                                  details=f"max_rings = {max_rings}, qmax = {qmax}, offsets {tuple(table['off'].shape)} for n = {n}")
+        index, q = self._buf(None, "nn_index", (M,), torch.int32, self.device), self._buf(None, "nn_q", (M,), torch.float64, self.device)
+        flag = self._buf(None, "nn_flag", (M,), torch.uint8, self.device)
+        self.call("marex_nearest_voxel_f64", table["sorted"], table["ids"], N, table["off"], n, dst, M, max_rings, qmax, index, q, flag)
+        return index, q, flag
+
+    def nearest_index(self, src, ids, dst, method: str = "brute", voxels: Optional[int] = None, max_rings: Optional[int] = None,
+                      qmax: float = float("inf")) -> Dict[str, object]:
+        """The nearest eligible source cell of every target, on the host: ``index`` int32 ``[M]`` (a cell number of ``ids``,
+        -1: none) and ``q`` float64 ``[M]`` (its squared chord, +inf: none), ``fallback`` (the targets the ring search left
+        to the brute kernel) and ``voxels``.  ``method``: ``"brute"``, or ``"voxel"`` with ``voxels`` per axis and
+        ``max_rings`` (None: ``voxels``, the rings that always cover the grid).  ``qmax``: the ring search may give up on a
+        target whose nearest source has ``q > qmax``; what it then reports for that target is not defined beyond that."""
+        if method not in ("brute", "voxel"):
+            raise ProcessingError("nearest_index: the method is 'brute' or 'voxel'", details=f"method = {method!r}")
+        src, dst = self._unit_vectors("nearest_index", "the sources", src), self._unit_vectors("nearest_index", "the targets", dst)
+        fallback = 0
+        if method == "brute":
+            index, q = self.nearest_brute(src, ids, dst)
+            voxels = 0
+        else:
+            table = self.voxel_table(src, ids, voxels)
+            index, q, flag = self.nearest_voxel(table, dst, table["n"] if max_rings is None else max_rings, qmax)
+            sel = torch.nonzero(flag).reshape(-1).to(torch.int32)  # a synchronising compaction: plumbing
+            fallback = int(sel.numel())
+            if fallback:
+                self.nearest_brute(table["sorted"], table["ids"], dst, sel=sel, index=index, q=q)
+        return {"index": self._host(index, np.int32), "q": self._host(q, np.float64), "fallback": fallback, "voxels": int(voxels)}
+
+    def resample_nearest(self, x: torch.Tensor, index: torch.Tensor, out: torch.Tensor, fill) -> None:
+        """``out [Tb, M] = x [Tb, C]`` gathered through ``index`` int32 ``[M]``, ``fill`` where the index is negative
+        (``marex_resample_nearest_u8`` / ``_i32`` / ``_f32`` by the dtype of ``x``: uint8, int32 or float32).  ``out`` is a
+        contiguous tensor of that dtype, for instance the rows of a window in the whole output."""
+        what = "resample_nearest"
+        names = {torch.uint8: "marex_resample_nearest_u8", torch.int32: "marex_resample_nearest_i32", torch.float32: "marex_resample_nearest_f32"}
+        if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.dtype not in names or not x.is_contiguous() or x.device != self.device:
+            raise ProcessingError(f"{what}: the field must be a contiguous uint8, int32 or float32 [T, C] tensor on the engine's device",
+                                  details=f"got {getattr(x, 'dtype', type(x))} {tuple(getattr(x, 'shape', ()))} on "
+                                          f"{getattr(x, 'device', 'the host')}")
+        Tb, Cn = int(x.shape[0]), int(x.shape[1])
+        if not isinstance(index, torch.Tensor) or index.dtype != torch.int32 or index.dim() != 1 or index.device != self.device:
+            raise ProcessingError(f"{what}: the index must be an int32 [M] tensor on the engine's device",
+                                  details=f"got {getattr(index, 'dtype', type(index))} {tuple(getattr(index, 'shape', ()))}")
+        M = int(index.shape[0])
+        if not isinstance(out, torch.Tensor) or out.dtype != x.dtype or tuple(out.shape) != (Tb, M) or not out.is_contiguous() or \
+                out.device != self.device:
+            raise ProcessingError(f"{what}: the output must be a contiguous {x.dtype} [{Tb}, {M}] tensor on the engine's device",
+                                  details=f"got {getattr(out, 'dtype', type(out))} {tuple(getattr(out, 'shape', ()))}")
+        if x.dtype == torch.float32:
+            fill = float(fill)
+        else:
+            lo, hi = (0, 255) if x.dtype == torch.uint8 else (-2 ** 31, 2 ** 31 - 1)
+            if isinstance(fill, float) and not fill.is_integer() or not lo <= int(fill) <= hi:
+                raise ProcessingError(f"{what}: the fill of a {x.dtype} field must be an integer in {lo} .. {hi}", details=f"fill = {fill!r}")
+            fill = int(fill)
+        if Tb == 0 or M == 0:
+            return
+        if Cn == 0:
+            out.fill_(fill)
+            return
+        self.call(names[x.dtype], x, Tb, Cn, index, M, fill, out)
+
     #: the most regions of :meth:`regional_series`
     REGIONAL_MAX_REGIONS = 32767
 
